@@ -19,8 +19,11 @@ Conv/ResNet/VAE stages of the UNets are stock MIOpen/hipBLASLt work outside the 
 Inputs are what the reference's caller hands the processors (inference/test.py:61-83): fp32 module weights, fp32
 token activations (LayerNorm output), ``torch.autocast`` to the 16-bit compute dtype - the cast to 16 bit is part of the
 step.  The timed steps REPLAY one hipGraph of the two-stream step (captured once during warm-up: same launches, same work,
-no CPU launch gaps; ``--graph 0`` times eager launches, and a failed capture falls back to them and says so).  Next to
-the headline the line carries, labelled, under ``config.extras``: the same step with eager launches on one and on two
+no CPU launch gaps; ``--graph 0`` times eager launches, and a failed capture falls back to them and says so).
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if ``--dump-outputs DIR`` is given and
+prints the line (``roofline``, ``cpu_baseline`` and ``config.extras`` null).  With ``--full`` the line also carries the
+roofline block, the CPU baseline and, labelled, under ``config.extras``: the same step with eager launches on one and on two
 streams, a second graph capture compared bit for bit with eager, the step with cached reference K/V, an
 end-to-end leg on the attention-topology host with the stage names of pix2pix_turbo.py:288-336, and the batch
 scatter / gather of SURVEY 8e over the process group (RCCL when N > 1).  None of them is ``value``.
@@ -70,22 +73,27 @@ def build_workload(cfg, train_input, dev, seed, act_fp32=True):
     g = torch.Generator(device="cpu").manual_seed(seed)
     layers = []
     idx = 0
-    for (L, C, H) in layer_classes(px):
-        for _ in range(3):
-            def mk(proc):
-                a = Attention(query_dim=C, heads=H, dim_head=64, processor=proc)
-                with torch.no_grad():
-                    for lin in (a.to_q, a.to_k, a.to_v, a.to_out[0]):
-                        lin.weight.copy_(torch.randn(lin.weight.shape, generator=g) / C ** 0.5)
-                return a.to(dev) if act_fp32 else a.to(dev, dtype)   # test.py:61-63: the model stays fp32 under autocast
-            kv_attn = mk(AttnProcessor())
-            main_attn = mk(SharedAttnProcessor(self_attn_idx=idx, use_adain=use_adain, train_input=train_input))
-            # token activations entering the two attentions (LayerNorm output in the real UNet)
-            act = torch.float32 if act_fp32 else dtype
-            h_ref = torch.randn(B * N, L, C, generator=g).to(dev, act)
-            h_main = torch.randn(B, L, C, generator=g).to(dev, act)
-            layers.append(dict(L=L, C=C, H=H, kv_attn=kv_attn, main_attn=main_attn, h_ref=h_ref, h_main=h_main))
-            idx += 1
+    # the modules' default initialisation (the to_out bias keeps it) draws from torch's global CPU generator: seeded here as
+    # well, so that the same arguments give the same inputs run to run; the caller's CPU generator state is left as it was
+    # and no device generator is touched
+    with torch.random.fork_rng(devices=[]):
+        torch.default_generator.manual_seed(seed)     # the CPU generator only: the modules are initialised on the CPU
+        for (L, C, H) in layer_classes(px):
+            for _ in range(3):
+                def mk(proc):
+                    a = Attention(query_dim=C, heads=H, dim_head=64, processor=proc)
+                    with torch.no_grad():
+                        for lin in (a.to_q, a.to_k, a.to_v, a.to_out[0]):
+                            lin.weight.copy_(torch.randn(lin.weight.shape, generator=g) / C ** 0.5)
+                    return a.to(dev) if act_fp32 else a.to(dev, dtype)   # test.py:61-63: the model stays fp32 under autocast
+                kv_attn = mk(AttnProcessor())
+                main_attn = mk(SharedAttnProcessor(self_attn_idx=idx, use_adain=use_adain, train_input=train_input))
+                # token activations entering the two attentions (LayerNorm output in the real UNet)
+                act = torch.float32 if act_fp32 else dtype
+                h_ref = torch.randn(B * N, L, C, generator=g).to(dev, act)
+                h_main = torch.randn(B, L, C, generator=g).to(dev, act)
+                layers.append(dict(L=L, C=C, H=H, kv_attn=kv_attn, main_attn=main_attn, h_ref=h_ref, h_main=h_main))
+                idx += 1
     return layers, (B, N, px, dtype, use_adain)
 
 
@@ -1032,13 +1040,16 @@ def control_plane_only(args):
         dist.barrier()
     t0 = time.perf_counter()
     time.sleep(0.01 * (rank + 1))                          # stands for the K timed steps: rank r takes (r + 1) * 10 ms
+    own = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)   # before the barrier: not the wait for the slowest rank
     if world > 1:
         dist.barrier()
-    t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
-    per_rank_ms = [float(t.item()) * 1e3 / args.steps]
+    # the MAX is taken over the same per-rank times, so max_over_ranks_s and per_rank_ms_per_step agree by construction (the GPU
+    # path's headline MAX is of the time bracketed by the closing barrier; the per-rank figures are own times in both)
+    t = own.clone()
+    per_rank_ms = [float(own.item()) * 1e3 / args.steps]
     if world > 1:
-        gathered = [torch.zeros_like(t) for _ in range(world)]
-        dist.all_gather(gathered, t)                       # every rank's own time, as the GPU path reports them
+        gathered = [torch.zeros_like(own) for _ in range(world)]
+        dist.all_gather(gathered, own)                     # every rank's own time beside the MAX
         per_rank_ms = [float(g.item()) * 1e3 / args.steps for g in gathered]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     # small images: control flow, not a measurement (one rank: the leg's HIP image kernels would need the GPU)
@@ -1057,6 +1068,23 @@ def control_plane_only(args):
     if world > 1:
         dist.destroy_process_group()
     return 0
+
+
+def dump_outputs(outs, out_dir, budget_bytes=60 << 20, seed=0):
+    """--dump-outputs: the step's nine shared-attention outputs (B, L, C) as DIR/shared_attn_out_<i>.npy, float32.  An output
+    larger than its share of the budget keeps a sample of its token rows - the same sorted rows for every identity and
+    channel, drawn from a generator seeded by ``seed + i`` - so that two builds are compared element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget_bytes // (4 * len(outs))        # float32 elements per output
+    for i, o in enumerate(outs):
+        o = o.detach()
+        if o.numel() > share:
+            rows = max(1, share // (o.numel() // o.shape[1]))
+            g = torch.Generator(device="cpu").manual_seed(seed + i)
+            idx = torch.randperm(o.shape[1], generator=g)[:rows].sort().values
+            o = o.index_select(1, idx.to(o.device))
+        np.save(os.path.join(out_dir, "shared_attn_out_%d.npy" % i), o.float().cpu().numpy())
 
 
 def main():
@@ -1083,7 +1111,21 @@ def main():
     ap.add_argument("--ref-early-exit", action="store_true",
                     help="stop the reference UNet after the K/V projections of its last capturing layer (its output is "
                          "discarded by the inference caller); off for the headline number")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the roofline and per-kernel-class figures, the "
+                         "CPU baseline, the labelled extra legs (one stream, second graph capture, cached K/V, power, probs dump, "
+                         "cfg1gpu, end-to-end host, scatter / gather) and, at N = 1, the one-rank RCCL communicator.  Off "
+                         "(default): set up, warm up, time the K steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the nine shared-attention outputs of the last timed step to "
+                         "DIR/shared_attn_out_<i>.npy (float32; a fixed, seeded sample of token rows where an output is large)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    # what only --full runs; the --no-* switches still narrow a --full run
+    no_roofline = args.no_roofline or not args.full
+    no_cpu_baseline = args.no_cpu_baseline or not args.full
+    no_extras = args.no_extras or not args.full
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own (the shape of the driver's N = 1 command): become the launcher - one rank per
@@ -1092,6 +1134,12 @@ def main():
         sys.exit(self_launch(args.gpus))
     if os.environ.get("IR_BENCH_CONTROL_ONLY") == "1":
         sys.exit(control_plane_only(args))
+
+    # the result line is the only thing on stdout: what libraries print there through C stdio (librccl announces its versions)
+    # goes to stderr, and the line is written to a duplicate of the original descriptor
+    sys.stdout.flush()
+    line_out = os.fdopen(os.dup(1), "w")
+    os.dup2(2, 1)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1115,7 +1163,7 @@ def main():
                                     timeout=datetime.timedelta(seconds=float(os.environ.get("IR_BENCH_RCCL_TIMEOUT", "300"))))
         else:
             dist.init_process_group(backend=backend)
-    elif os.environ.get("IR_BENCH_FORCE_DIST", "1") == "1" and backend == "nccl":
+    elif args.full and os.environ.get("IR_BENCH_FORCE_DIST", "1") == "1" and backend == "nccl":
         # N = 1 (round 5): the barrier, the MAX-over-ranks reduction and the scatter / gather leg run through
         # a real one-rank RCCL communicator, so that the first 8-GPU run is not also the first RCCL run.  Never at the price of
         # the headline: any failure falls back to the plain single-process path and is reported in extras.scatter_gather.
@@ -1163,7 +1211,7 @@ def main():
         from instantrestore_amd import ops as _ops_mod
         top_l = layers[-1]["L"]
         in_step = []
-        if rank == 0 and not args.no_roofline and cap is None:
+        if rank == 0 and not no_roofline and cap is None:
             _ops_mod.EVENT_SINK = (lambda q, rk, ad: rk is not None and q.shape[1] == top_l, in_step)
         t0 = time.perf_counter()
         if cap is not None:
@@ -1173,10 +1221,14 @@ def main():
         else:
             for _ in range(args.steps):
                 outs = hot_path_step(layers, B, N, args.ref_early_exit, bool(args.two_streams))
+        torch.cuda.synchronize()
+        own = time.perf_counter() - t0      # this rank's own K steps, before it waits for the other ranks at the barrier
         barrier()   # synchronize + barrier + synchronize: the K steps are bracketed on both sides
         elapsed = time.perf_counter() - t0
         _ops_mod.EVENT_SINK = None
-        if rank == 0 and not args.no_roofline and cap is not None and args.two_streams:
+        if rank == 0 and args.dump_outputs:     # before anything else runs on the layers: the last timed step's results
+            dump_outputs(outs, args.dump_outputs)
+        if rank == 0 and not no_roofline and cap is not None and args.two_streams:
             _ops_mod.EVENT_SINK = (lambda q, rk, ad: rk is not None and q.shape[1] == top_l, in_step)
             for _ in range(args.steps):
                 hot_path_step(layers, B, N, False, True)
@@ -1185,17 +1237,18 @@ def main():
         in_step_ms = [a.elapsed_time(b) for a, b in in_step]
     assert all(torch.isfinite(o).all() for o in outs)
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
-    per_rank_ms = [elapsed / args.steps * 1e3]
+    per_rank_ms = [own / args.steps * 1e3]
     if use_dist:
-        gathered = [torch.zeros_like(t) for _ in range(dist.get_world_size())]
-        dist.all_gather(gathered, t)            # every rank's own time for its K steps (the line reports them beside the MAX)
+        own_t = torch.tensor([own], dtype=torch.float64, device=t.device)
+        gathered = [torch.zeros_like(own_t) for _ in range(dist.get_world_size())]
+        dist.all_gather(gathered, own_t)        # every rank's own time for its K steps (the line reports them beside the MAX)
         per_rank_ms = [float(g.item()) / args.steps * 1e3 for g in gathered]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
 
     roof = cpu = None
     if rank == 0:
-        if not args.no_roofline:
+        if not no_roofline:
             # `achieved`: the dominant kernel's average launch duration INSIDE timed steps, HIP events on its
             # launch stream - over a second timed region of the same K steps run on ONE stream, because with two
             # streams the reference UNet's kernels share the chip with it and the in-situ time stops being the
@@ -1239,11 +1292,11 @@ def main():
                 roof["traffic_unit"] = "bytes/launch (PMC in THIS run: 2*FETCH_SIZE + WRITE_SIZE, two counter-only rocprofv3 passes of tools/prof_attn.py)"
             else:
                 roof["traffic_live_error"] = detail
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and not no_cpu_baseline:
             cpu = cpu_baseline(N, px, train_input, use_adain, seed=99, dtype=dtype, dev=dev)
     extras = None
     hung = False
-    if not args.no_extras:
+    if not no_extras:
         extras = {}
         if rank == 0:
             with torch.no_grad():
@@ -1370,7 +1423,7 @@ def main():
                                     "layer i of its own UNet and only the two UNets overlap (the one-stream figure under extras is the no-overlap bound)",
                 "rccl_ranks": (dist.get_world_size() if use_dist else 1),
                 "per_rank_ms_per_step": [round(x, 4) for x in per_rank_ms],
-                "rccl_communicator": ("real (%d ranks)" % dist.get_world_size()) if use_dist else "none: %s" % ((single_rank_comm or {}).get("error") or "IR_BENCH_FORCE_DIST=0"),
+                "rccl_communicator": ("real (%d ranks)" % dist.get_world_size()) if use_dist else "none: %s" % ((single_rank_comm or {}).get("error") or ("IR_BENCH_FORCE_DIST=0" if args.full else "one rank, no --full")),
                 "scatter_gather_ms": None if not extras else extras.get("scatter_gather", {}).get("scatter_gather_ms"),
                 "extras": extras,
                 **{k: round(v, 1) for k, v in summary(N, train_input, px).items()},
@@ -1378,15 +1431,7 @@ def main():
             "roofline": roof,
             "cpu_baseline": cpu,
         }
-        print(json.dumps(line), flush=True)
-    if use_dist:
-        # librccl announces itself ("Librccl path : ...") through C stdio on STDOUT, buffered until exit when stdout is a pipe:
-        # the one JSON line is out and flushed, whatever the C runtime still holds goes to stderr
-        sys.stdout.flush()
-        try:
-            os.dup2(2, 1)
-        except OSError:
-            pass
+        print(json.dumps(line), file=line_out, flush=True)
     if leave_hard:      # a helper thread is still inside the RCCL bring-up: no interpreter teardown behind it
         sys.stdout.flush()
         os._exit(0)

@@ -1,4 +1,4 @@
-"""print the headline, the dominant kernel and the per-class table of a bench.py JSON line.  usage: gpu_bench_summary.py <file>"""
+"""print the headline, the dominant kernel and the per-class table of a `bench.py --full` JSON line.  usage: gpu_bench_summary.py <file>"""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(d["config"]["workload"][:80], "|", d["value"], d["unit"], d["ms_per_step"], "ms/step | dominant", d["roofline"]["frac"], d["roofline"]["ms_per_launch"], "ms")
