@@ -139,10 +139,12 @@ typedef struct ir_shared_attn_args {
 #define IR_TUNE_W64X8 13
 #define IR_TUNE_PIPE32_EARLYQK 14
 #define IR_TUNE_W128 16            /* round 6: one wave per SIMD, 128 query rows per wave, hand-placed instruction stream; needs
-                                      IR_FLAG_Q_PRESCALED, segment lengths that are multiples of 64, no valid_refs / seg_mass */
+                                      IR_FLAG_Q_PRESCALED and segment lengths that are multiples of 64; takes valid_refs and
+                                      seg_mass (the default dispatch still keeps calls that carry either on the kernel it chose
+                                      before: IR_ATTN_W128=1 in the environment sends them to this one) */
 #define IR_TUNE_W64_ABL_FIRST 20 /* 20 ... : development builds (-DIR_ABLATIONS) only - energy / timing ablations of the 64-row kernel
-                                    (WRONG results: one class of work removed per bit; tools/gpu_energy_probe.py).  Values 16 / 17
-                                    (rounds 2-3: one-wave-per-SIMD and three-stage experiments) are retired. */
+                                    (WRONG results: one class of work removed per bit; tools/gpu_energy_probe.py).  Value 17
+                                    (rounds 2-3: a three-stage experiment) is retired. */
 #define IR_TUNE_PIPE32_POSTCHECK 18   /* 32-row kernel, pre-scaled Q, reference checked after the exponentials (needs
                                          IR_FLAG_Q_PRESCALED; parity-green, same speed as PIPE32_PRESCALE_Q: opt-in) */
 

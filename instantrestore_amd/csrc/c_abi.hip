@@ -87,7 +87,7 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
   p->ws = (float*)a->workspace;
   p->ws_bytes = a->workspace != nullptr ? (size_t)a->workspace_bytes : 0;
   if (a->tuning == IR_TUNE_W128 && !ir_attn_w128_supports(*p))
-    return fail(IR_ERR_UNSUPPORTED, "IR_TUNE_W128 takes segment lengths that are multiples of 64 keys, no valid_refs and no seg_mass");
+    return fail(IR_ERR_UNSUPPORTED, "IR_TUNE_W128 takes segment lengths that are multiples of 64 keys (valid_refs and seg_mass included)");
   const int64_t blocks = (int64_t)a->batch * a->heads * ((a->len_q + 127) / 128);
   if (blocks > 0x7fffffffLL) return fail(IR_ERR_UNSUPPORTED, "grid too large");
   return IR_OK;
@@ -107,12 +107,24 @@ const char* ir_last_error_string(void) { return g_err; }
 const char* ir_shared_attn_kernel_name(const ir_shared_attn_args* args) {
   AttnKParams p;
   if (build_attn_params(args, &p, false) != IR_OK) return "";
+  // the launch takes seg_mass only with an output (need_out); for reporting the by-product counts wherever it is asked for - it
+  // decides the 128-row kernel's form and whether the default rule takes that kernel.  Never dereferenced here
+  p.seg_cum = (float*)args->seg_mass;
   const int v = args->tuning & 31;
   const bool fold = p.aa != nullptr;
   const bool w64 = (v == 0 && ir_attn_default_is_w64(p)) || v == 13;
-  if ((v == 16 || (v == 0 && ir_attn_default_is_w128(p))) && ir_attn_w128_supports(p))
-    return fold ? "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, AdaIN ratio-frame fold>"
-                : "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q>";
+  if ((v == 16 || (v == 0 && ir_attn_default_is_w128(p))) && ir_attn_w128_supports(p)) {
+    static const char* const names[8] = {
+        "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q>",
+        "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, AdaIN ratio-frame fold>",
+        "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, zero suffix in closed form>",
+        "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, AdaIN ratio-frame fold, zero suffix in closed form>",
+        "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, segment masses>",
+        "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, AdaIN ratio-frame fold, segment masses>",
+        "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, zero suffix in closed form, segment masses>",
+        "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, AdaIN ratio-frame fold, zero suffix in closed form, segment masses>"};
+    return names[(fold ? 1 : 0) | (p.valid != nullptr ? 2 : 0) | (p.seg_cum != nullptr ? 4 : 0)];
+  }
   if (p.q_prescaled) {   // the dispatch of ir_launch_shared_attn_fwd, restated for reporting
     if (w64) return fold ? "shared_attn_fwd_w64_kernel<64 rows/wave, 8 waves, pre-scaled Q (reference through the MFMA C operand, checked after the exponentials), AdaIN ratio-frame fold>"
                          : "shared_attn_fwd_w64_kernel<64 rows/wave, 8 waves, pre-scaled Q (reference through the MFMA C operand, checked after the exponentials)>";

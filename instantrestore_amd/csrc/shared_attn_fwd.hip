@@ -435,7 +435,7 @@ bool ir_attn_variant_available(int variant) {
   return (base <= 18 && base != 8 && base != 15 && base != 17) || (base >= 20 && base < 20 + ir_w64_abl_count());
 #else
   if ((variant >> 5) != 0) return false;
-  return base == 0 || base == 7 || (base >= 10 && base <= 14) || base == 16 || base == 18;   // 16 (SP64) and 17 (TP32): development builds, like 1-6, 8, 9, 15
+  return base == 0 || base == 7 || (base >= 10 && base <= 14) || base == 16 || base == 18;   // (17, TP32: retired, like 1-6, 8, 9, 15 development builds)
 #endif
 }
 
@@ -446,13 +446,16 @@ bool ir_attn_default_is_w64(const AttnKParams& p) {
   return p.Lq >= 4096 && (items512 >= 256 || p.ntiles >= 128);
 }
 
-// Round 6: where the 64-row kernel would run AND the call is in the 128-row kernel's domain (pre-scaled Q, whole tiles, no
-// valid_refs / seg_mass) the one-wave-per-SIMD kernel takes it.  IR_ATTN_W128=0 / 1 overrides the rule for A/B runs.
+// Round 6: where the 64-row kernel would run AND the call is in the 128-row kernel's domain (pre-scaled Q, whole tiles) the
+// one-wave-per-SIMD kernel takes it.  IR_ATTN_W128=0 / 1 overrides the rule for A/B runs.  Calls with valid_refs or seg_mass: the
+// 128-row kernel CAN take them (ir_attn_w128_supports; IR_TUNE_W128 or IR_ATTN_W128=1 sends them there), but the default rule keeps
+// them on the kernel it chose before that kernel learned them, so that no existing output changes its bits
 bool ir_attn_default_is_w128(const AttnKParams& p) {
   static const int env = [] { const char* e = getenv("IR_ATTN_W128"); return e == nullptr ? -1 : (e[0] == '0' ? 0 : 1); }();
   if (env == 0) return false;
   if (!ir_attn_w128_supports(p)) return false;
   if (env == 1) return p.Lq >= 1024;
+  if (p.valid != nullptr || p.seg_cum != nullptr) return false;
   if (IR_W128_DEFAULT == 0) return false;
   if (ir_attn_default_is_w64(p)) return true;
   // 32x32-token class (1024 <= Lq < 4096; cfg 4's and cfg 5's shapes - at cfg 2's own the two kernels measure equal and the 32-row
@@ -493,9 +496,10 @@ hipError_t ir_launch_shared_attn_fwd(const AttnKParams& p, int dtype, int varian
   if (!ir_attn_variant_available(variant)) return hipErrorInvalidValue;
   if (p.seg_cum != nullptr) {
     // by-product of the 64-row and the pipelined 32-row kernels (every product kernel); the development-only experiments never learned it
-    // (the 8-wave 64-row kernel and the 32-row kernel's two default forms carry the MASS instantiation: tuning 0, 11, 13, 14)
+    // (the 8-wave 64-row kernel and the 32-row kernel's two default forms carry the MASS instantiation, the 128-row kernel its
+    // FORMS instantiation: tuning 0, 11, 13, 14, 16)
     const int b0 = variant & 31;
-    if ((variant >> 5) != 0 || !(b0 == 0 || b0 == 11 || b0 == 13 || b0 == 14)) return hipErrorInvalidValue;   // (16 has no MASS form)
+    if ((variant >> 5) != 0 || !(b0 == 0 || b0 == 11 || b0 == 13 || b0 == 14 || b0 == 16)) return hipErrorInvalidValue;
   }
   const hipError_t e = launch_attn_kernel(p, dtype, variant, s);
   if (e != hipSuccess || p.seg_cum == nullptr) return e;

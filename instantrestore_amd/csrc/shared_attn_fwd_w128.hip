@@ -56,7 +56,11 @@ static __device__ __forceinline__ void static_for(F&& f) {
 constexpr int A_O = 0, A_Q = 128, A_M = 192, A_L = 196, A_LD = 200;
 constexpr int FOLD_MAX_SEG = 16;   // segment lists up to 16 entries take their fold coefficients from the LDS table (longer ones: from global memory)
 
-template <typename T, bool FOLD>
+// FORMS: the two forms the default instantiations do not carry, both chosen at run time between runs and in the epilogue (the
+// walk itself is the same stream): zero-filled references in closed form (ABI v8 valid_refs, p.valid) and the cumulative
+// log-sum-exp per segment (ABI v9 seg_mass, p.seg_cum).  Instantiated in an object of its own (shared_attn_fwd_w128_forms.hip), so
+// the <T, FOLD> kernels of the default dispatch are compiled from exactly the code they were.
+template <typename T, bool FOLD, bool FORMS = false>
 __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(1, 1))) shared_attn_fwd_w128_kernel(const AttnKParams p) {
   using v4 = typename ElemTraits<T>::v4;
   // K ring of 2, V ring of 2 (32 KiB, at LDS offset 0); FOLD: behind it the fold coefficients of every segment boundary
@@ -83,8 +87,16 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(1,
   if (item_local >= p.sk_ix || lin >= p.sk_items) return;
   const int bh = lin / p.nqb, qb = lin - bh * p.nqb;
   const int b = bh / p.H, h = bh - b * p.H;
-  const int tile_begin = (int)(((long)p.ntiles * piece) / npiece);
-  const int tile_end = (int)(((long)p.ntiles * (piece + 1)) / npiece);
+  // FORMS, valid_refs (as the 64-row kernel): references n >= valid[b] are all-zero, so this item's K/V range ends after reference
+  // nref - 1 and the piece that owns the end of the range adds that suffix in closed form before the epilogue
+  int nref = p.N;
+  if (FORMS && p.valid != nullptr) {
+    const int vb = p.valid[b];
+    nref = vb < 0 ? 0 : (vb < p.N ? vb : p.N);
+  }
+  const int ntiles_b = FORMS ? p.tiles_self + nref * p.tiles_ref : p.ntiles;
+  const int tile_begin = (int)(((long)ntiles_b * piece) / npiece);
+  const int tile_end = (int)(((long)ntiles_b * (piece + 1)) / npiece);
   const int NTILES = tile_end - tile_begin;
 
   // ---- lane constants of the run statement -----------------------------------------------------------------------------------
@@ -161,6 +173,41 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(1,
       });
     });
   };
+
+  // FORMS, seg_mass: the cumulative log-sum-exp through segment s of row block B_ (log2 units, a number the running reference
+  // cancels out of) goes to seg_cum[b,h,row,s] in natural-log units - or, for a K/V-range piece, to its slot of ws_cum in log2
+  // units (the combine kernel merges the pieces).  Segment ends only: nothing here is on the per-tile path.  What the forms need
+  // of the parameters is read where it is used, through a pointer the compiler cannot see through (as in the 64-row kernel):
+  // held in SGPRs across the runs it spilled the default kernels' scalars into VGPR lanes
+  typedef const __attribute__((address_space(4))) AttnKParams* KArgs;
+  auto cold = [&]() -> KArgs { KArgs q = (KArgs)__builtin_amdgcn_kernarg_segment_ptr(); asm volatile("" : "+s"(q)); return q; };
+  auto cum_store = [&](int B_, int s, float v2) {
+    const KArgs kc = cold();
+    if (hi != 0) return;
+    if (npiece > 1) {
+      const int64_t prow = ((int64_t)((xcd * (kc->sk_ix - kc->sk_full) + (item_local - kc->sk_full)) * npiece + piece)) * QB + wid * 128 + 32 * B_ + lq;
+      kc->ws_cum[prow * kc->nseg_out + s] = v2;
+    } else {
+      const int qrow = qb * QB + wid * 128 + 32 * B_ + lq;
+      if (qrow < kc->Lq) kc->seg_cum[(((int64_t)b * kc->H + h) * kc->Lq + qrow) * kc->nseg_out + s] = v2 * 0.69314718f;
+    }
+  };
+  auto cum_run_end = [&](int sc) {   // behind the run that closes segment sc (or stops inside it): m + log2(l_total)
+    static_for<4>([&](auto blk) {
+      constexpr int B_ = decltype(blk)::value;
+      const float lt = FOLD ? pair_sum(acc_get<A_L + B_>()) + acc_get<A_LD + B_>() : pair_sum(acc_get<A_L + B_>());
+      cum_store(B_, sc, acc_get<A_M + B_>() + __log2f(lt));
+    });
+  };
+  auto seg_of = [&](int t) {   // the segment of tile t of the item's walk
+    const KArgs kc = cold();
+    return (kc->include_self && t < kc->tiles_self) ? 0 : kc->include_self + (t - kc->tiles_self) / kc->tiles_ref;
+  };
+  auto want_mass = [&]() { return FORMS && cold()->seg_cum != nullptr; };
+  if (want_mass() && npiece > 1 && NTILES > 0) {   // segments before this piece's range: nothing of them (an empty piece: the tail below)
+    const int s_first = seg_of(tile_begin);
+    for (int sg = 0; sg < s_first; ++sg) static_for<4>([&](auto blk) { cum_store(decltype(blk)::value, sg, -INFINITY); });
+  }
 
   // ---- the K/V walk: runs of consecutive tiles of one segment ---------------------------------------------------------------
   // The DMA stream runs across runs (stream v2): while a run computes its last tile, its last DMA slot fetches the FIRST tile
@@ -294,23 +341,84 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(1,
       gt += cur.n;
       prefetched = has_next;
       if (FOLD) fold_boundary(cur.seg, t < tile_end);   // a piece that stops inside a segment closes what it has
+      if (want_mass()) cum_run_end(cur.seg);
       cur = nx;
     }
   }
 
   // ---- epilogue (per row block), as the 64-row kernel's --------------------------------------------------------------------------
+  // FORMS: this piece owns the end of the item's range and a zero-filled suffix follows it (valid count read again, see cold())
+  int nref_e = 0, N_e = 0;
+  if (FORMS) {
+    const KArgs kc = cold();
+    N_e = kc->N;
+    nref_e = N_e;
+    if (kc->valid != nullptr) {
+      const int vb = kc->valid[b];
+      nref_e = vb < 0 ? 0 : (vb < N_e ? vb : N_e);
+    }
+  }
+  const bool zsuffix = FORMS && nref_e < N_e && piece == npiece - 1;
   static_for<4>([&](auto blk) {
     constexpr int B_ = decltype(blk)::value;
     const int qrow = qrow0 + 32 * B_;
-    const float l_fin = FOLD ? acc_get<A_LD + B_>() : pair_sum(acc_get<A_L + B_>());
-    const float m_run = acc_get<A_M + B_>();
-    const float m_raw = m_run / p.scale_log2;   // the combine kernel and the LSE work in raw-score units
+    float l_fin = FOLD ? acc_get<A_LD + B_>() : pair_sum(acc_get<A_L + B_>());
+    float m_run = acc_get<A_M + B_>();
+    float m_raw = m_run / p.scale_log2;   // the combine kernel and the LSE work in raw-score units
     f32x16 o0, o1;
     static_for<16>([&](auto r_) {
       constexpr int r = decltype(r_)::value;
       o0[r] = acc_get<A_O + 32 * B_ + r>();
       o1[r] = acc_get<A_O + 32 * B_ + 16 + r>();
     });
+    if (FORMS) {
+      // Zero-filled references in closed form (FORMS, valid_refs; the 64-row kernel's zero_suffix): the (N - nref) Lr keys of the
+      // suffix all score exactly 0, which weighs 2^(-m) against the running reference m (log2 units).  The reference first moves up
+      // to 0 if it is below (O and the row sum rescaled), then the row sum takes (N - nref) Lr 2^(-m) and - with the AdaIN fold - O
+      // takes that weight times the sum of the suffix's shifts b (a * 0 + b per key; O is the true total here: the last fold
+      // boundary closed the ratio frame with a_next = 1).  Without the fold the value rows are 0 and only the row sum moves.
+      const KArgs kc = cold();
+      float l_pre = l_fin, pz = 0.f;
+      if (zsuffix) {
+        const float e = -m_run;
+        const float up = e > 0.f ? e : 0.f;
+        const float alpha = fast_exp2(-up);
+        o0 *= alpha;
+        o1 *= alpha;
+        l_fin *= alpha;
+        m_run += up;
+        pz = fast_exp2(e - up) * (float)kc->Lr;
+        l_pre = l_fin;
+        l_fin += pz * (float)(N_e - nref_e);
+        if (FOLD) {
+#pragma unroll
+          for (int g4 = 0; g4 < 4; ++g4) {
+            f32x4 bs0 = {0.f, 0.f, 0.f, 0.f}, bs1 = bs0;
+            for (int n = nref_e; n < N_e; ++n) {
+              const int64_t ao = ((int64_t)(b * N_e + n) * kc->H + h) * 64 + 4 * hi;
+              bs0 += *(const f32x4*)(kc->ab + ao + 8 * g4);
+              bs1 += *(const f32x4*)(kc->ab + ao + 32 + 8 * g4);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              o0[4 * g4 + i] = __builtin_fmaf(pz, bs0[i], o0[4 * g4 + i]);
+              o1[4 * g4 + i] = __builtin_fmaf(pz, bs1[i], o1[4 * g4 + i]);
+            }
+          }
+        }
+      }
+      if (want_mass()) {
+        // segments behind the last one this piece walked: its total - and, on the piece that owns the zero suffix, the row sum
+        // before the suffix plus j zero segments (an empty piece: from segment 0 on)
+        const int s_next = NTILES > 0 ? seg_of(tile_end - 1) + 1 : 0;
+        const int sz = kc->include_self + nref_e;
+        for (int sg = s_next; sg < kc->nseg_out; ++sg) {
+          const int j = sg - sz + 1;
+          cum_store(B_, sg, m_run + __log2f(l_pre + pz * (float)(j > 0 ? j : 0)));
+        }
+      }
+      m_raw = m_run / p.scale_log2;
+    }
     if (npiece > 1) {
       const int64_t prow = ((int64_t)((xcd * (p.sk_ix - p.sk_full) + (item_local - p.sk_full)) * npiece + piece)) * QB + wid * 128 + 32 * B_ + lq;
       float* wo = p.ws_o + prow * 64;
@@ -323,7 +431,7 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(1,
         *(f32x4*)(wo + 32 + 8 * g4 + 4 * hi) = x1;
       }
       if (hi == 0) {
-        p.ws_ml[prow * 2] = NTILES == 0 ? -INFINITY : m_raw;   // an empty piece stays out of the merge's maximum
+        p.ws_ml[prow * 2] = NTILES == 0 && !zsuffix ? -INFINITY : m_raw;   // an empty piece stays out of the merge's maximum (unless it owns the zero suffix)
         p.ws_ml[prow * 2 + 1] = l_fin;
       }
       return;
@@ -352,7 +460,7 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(1,
   });
 }
 
-template <typename T, bool FOLD>
+template <typename T, bool FOLD, bool FORMS = false>
 hipError_t launch(const AttnKParams& p0, hipStream_t s) {
   AttnKParams p = p0;
   p.nqb = (p.Lq + QB - 1) / QB;
@@ -363,7 +471,7 @@ hipError_t launch(const AttnKParams& p0, hipStream_t s) {
   int rem = p.sk_ix - full;
   int k = 1;
   if (p.ws != nullptr && rem > 0) {
-    const size_t piece_bytes = (size_t)QB * 66 * sizeof(float);
+    const size_t piece_bytes = (size_t)QB * (66 + (p.seg_cum != nullptr ? p.nseg_out : 0)) * sizeof(float);
     k = ir_pick_split(rem, slots_x, p.ntiles / 8 /* pieces of at least 8 tiles */, (long)(p.ws_bytes / piece_bytes / 8));
   }
   if (k <= 1) { full = p.sk_ix; rem = 0; k = 1; }
@@ -371,9 +479,9 @@ hipError_t launch(const AttnKParams& p0, hipStream_t s) {
   p.sk_k = k;
   p.ws_o = p.ws;
   p.ws_ml = p.ws + (size_t)8 * rem * k * QB * 64;
-  p.ws_cum = nullptr;
+  p.ws_cum = p.seg_cum != nullptr ? p.ws_ml + (size_t)8 * rem * k * QB * 2 : nullptr;
   const int grid = 8 * (full + rem * k);
-  hipLaunchKernelGGL((shared_attn_fwd_w128_kernel<T, FOLD>), dim3(grid), dim3(NW * 64), 0, s, p);
+  hipLaunchKernelGGL((shared_attn_fwd_w128_kernel<T, FOLD, FORMS>), dim3(grid), dim3(NW * 64), 0, s, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || k <= 1) return e;
   return ir_launch_shared_attn_combine(p, std::is_same<T, __bf16>::value ? 1 : 0, QB, rem, s);
@@ -381,10 +489,18 @@ hipError_t launch(const AttnKParams& p0, hipStream_t s) {
 
 }  // namespace
 
-// What this kernel takes (everything else stays with the 64-row kernel): pre-scaled Q, whole 64-key tiles in every segment,
-// no valid_refs closed form, no seg_mass by-product
+#if IR_W128_FORMS
+// valid_refs / seg_mass (FORMS = true): shared_attn_fwd_w128_forms.hip compiles this file once more with IR_W128_FORMS=1
+hipError_t ir_launch_shared_attn_fwd_w128_forms(const AttnKParams& p, int dtype, hipStream_t s) {
+  if (p.aa != nullptr) return dtype == 1 ? launch<__bf16, true, true>(p, s) : launch<_Float16, true, true>(p, s);
+  return dtype == 1 ? launch<__bf16, false, true>(p, s) : launch<_Float16, false, true>(p, s);
+}
+#else
+// What this kernel takes (everything else stays with the 64-row kernel): pre-scaled Q, whole 64-key tiles in every segment.
+// valid_refs and seg_mass go to the FORMS instantiations; whether the default dispatch CHOOSES this kernel for them is
+// ir_attn_default_is_w128's business
 bool ir_attn_w128_supports(const AttnKParams& p) {
-  if (!p.q_prescaled || p.valid != nullptr || p.seg_cum != nullptr) return false;
+  if (!p.q_prescaled) return false;
   if (p.include_self && (p.Ls % KVB) != 0) return false;
   if (p.N > 0 && (p.Lr % KVB) != 0) return false;
   return p.ntiles > 0;
@@ -392,6 +508,8 @@ bool ir_attn_w128_supports(const AttnKParams& p) {
 
 hipError_t ir_launch_shared_attn_fwd_w128(const AttnKParams& p, int dtype, hipStream_t s) {
   if (!ir_attn_w128_supports(p)) return hipErrorInvalidValue;
+  if (p.valid != nullptr || p.seg_cum != nullptr) return ir_launch_shared_attn_fwd_w128_forms(p, dtype, s);
   if (p.aa != nullptr) return dtype == 1 ? launch<__bf16, true>(p, s) : launch<_Float16, true>(p, s);
   return dtype == 1 ? launch<__bf16, false>(p, s) : launch<_Float16, false>(p, s);
 }
+#endif

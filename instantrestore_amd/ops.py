@@ -276,11 +276,16 @@ def shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, s
 @_on_tensor_device
 def time_shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, scale: float,
                           include_self: bool = True, adain=None, iters: int = 10, split: bool = True,
-                          q_prescaled: bool = False) -> float:
-    """Average ms per launch measured with HIP events on the launch stream (``bench.py``)."""
+                          q_prescaled: bool = False, valid_refs: Optional[torch.Tensor] = None, return_mass: bool = False) -> float:
+    """Average ms per launch measured with HIP events on the launch stream (``bench.py``); ``valid_refs`` / ``return_mass`` as
+    in :func:`shared_attention` (the masses' finishing kernel is part of the timed launch)."""
     q, k_self, v_self, ref_k, ref_v = _prep(q, k_self, v_self, ref_k, ref_v, heads, include_self, adain)
     out = torch.empty((q.shape[0], q.shape[1], heads * HEAD_DIM), dtype=q.dtype, device=q.device)
-    args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, None, split, q_prescaled)
+    args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, None, split, q_prescaled, valid_refs)
+    if return_mass:
+        nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
+        mass = torch.empty((q.shape[0], heads, q.shape[1], nseg), dtype=torch.float32, device=q.device)
+        args.seg_mass = mass.data_ptr()
     ms = C.c_float(0.0)
     _lib.check(_lib.lib().ir_time_shared_attn_fwd(C.byref(args), int(iters), _stream(), C.byref(ms)),
                "ir_time_shared_attn_fwd")
@@ -304,11 +309,17 @@ def bench_mfma_stream(dtype: torch.dtype = torch.bfloat16, zero_operands: bool =
 
 
 def shared_attention_kernel_name(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, scale: float,
-                                 include_self: bool = True, adain=None, q_prescaled: bool = False) -> str:
-    """which kernel the dispatcher launches for these tensors (reporting only)"""
+                                 include_self: bool = True, adain=None, q_prescaled: bool = False,
+                                 valid_refs: Optional[torch.Tensor] = None, return_mass: bool = False) -> str:
+    """which kernel the dispatcher launches for these tensors (reporting only; ``valid_refs`` / ``return_mass`` as in
+    :func:`shared_attention` - they decide the 128-row kernel's form and whether the default rule takes it)"""
     q, k_self, v_self, ref_k, ref_v = _prep(q, k_self, v_self, ref_k, ref_v, heads, include_self, adain)
     out = torch.empty((q.shape[0], q.shape[1], heads * HEAD_DIM), dtype=q.dtype, device=q.device)
-    args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, None, True, q_prescaled)
+    args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, None, True, q_prescaled, valid_refs)
+    if return_mass:   # never written: the name is all this call computes
+        nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
+        mass = torch.empty((q.shape[0], heads, q.shape[1], nseg), dtype=torch.float32, device=q.device)
+        args.seg_mass = mass.data_ptr()
     return _lib.lib().ir_shared_attn_kernel_name(C.byref(args)).decode()
 
 

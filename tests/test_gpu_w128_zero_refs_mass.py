@@ -1,0 +1,313 @@
+"""The 128-row kernel (IR_TUNE_W128 = 16) with zero-filled references in closed form (ABI v8 ``valid_refs``) and the segment
+masses as a by-product of the launch (ABI v9 ``seg_mass``): its FORMS instantiation (csrc/shared_attn_fwd_w128.hip).
+
+Held to what the 64-row kernel's forms are held to (tests/test_gpu_valid_refs.py, tests/test_gpu_seg_mass.py): the float64 oracle
+on the ZERO-FILLED tensors (zeroed, not masked) through tests/parity_bounds.py; the same kernel walking the zero tiles within
+twice the tolerance; masses against the oracle's block sums (abs 2e-3) and the second-pass kernel (abs 1e-4), rows summing to 1;
+the output BIT-identical with and without the by-product; the K/V-range pieces of the remainder split at the cfg-2 / cfg-4 top
+layers; determinism; and the plugin surface with IR_ATTN_W128=1 against the default dispatch.  All calls: pre-scaled Q."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import shared_attn_oracle as O
+from parity_bounds import check_parity
+
+pytestmark = pytest.mark.gpu
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+QC = 0.125 * 1.4426950408889634
+TOL = {torch.float16: 1e-3, torch.bfloat16: 8e-3}
+W128 = 16
+
+
+@pytest.fixture(scope="module")
+def ops():
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    from instantrestore_amd import ops as _ops
+    _ops._lib.lib()
+    return _ops
+
+
+def _np64(t):
+    return t.float().cpu().numpy().astype(np.float64)
+
+
+def _inputs(B, H, L, Ls, N, Lr, dtype, seed, valid):
+    """pre-scaled Q (one rounding, as the fused projection hands it over); references n >= valid[b] zero-filled"""
+    g = torch.Generator().manual_seed(seed)
+    C = H * 64
+    q = (torch.randn(B, L, C, generator=g) * 1.2 * QC).to(dtype)
+    k, v = (torch.randn(B, Ls, C, generator=g) * 1.2).to(dtype), (torch.randn(B, Ls, C, generator=g) * 0.8 + 0.3).to(dtype)
+    rk = (torch.randn(B, N, Lr, C, generator=g) * 1.2).to(dtype)
+    rv = (torch.randn(B, N, Lr, C, generator=g) * 1.3 - 0.2).to(dtype)
+    for b, nv in enumerate(valid):
+        rk[b, max(nv, 0):] = 0
+        rv[b, max(nv, 0):] = 0
+    return [t.cuda() for t in (q, k, v, rk, rv)]
+
+
+def _call(ops, q, k, v, rk, rv, H, inc, aff, valid=None, variant=W128, **kw):
+    prev = ops.set_attn_variant(variant)
+    try:
+        return ops.shared_attention(q, k, v, rk, rv, heads=H, scale=0.125, include_self=inc, adain=aff, q_prescaled=True,
+                                    valid_refs=valid, **kw)
+    finally:
+        ops.set_attn_variant(prev)
+
+
+def _name(ops, q, k, v, rk, rv, H, inc, aff, valid=None, mass=False, variant=W128):
+    prev = ops.set_attn_variant(variant)
+    try:
+        return ops.shared_attention_kernel_name(q, k, v, rk, rv, heads=H, scale=0.125, include_self=inc, adain=aff, q_prescaled=True,
+                                                valid_refs=valid, return_mass=mass)
+    finally:
+        ops.set_attn_variant(prev)
+
+
+def _edges(Ls, N, Lr, inc):
+    return [0] + ([Ls] if inc else []) + [(Ls if inc else 0) + (n + 1) * Lr for n in range(N)]
+
+
+def _oracle(q, k, v, rk, rv, H, inc, adain, rows=None, probs=False):
+    qn = _np64(q) / QC
+    if rows is not None:
+        qn = qn[:, rows]
+    return O.shared_attention_np(qn, _np64(k), _np64(v), _np64(rk), _np64(rv), H, 0.125, adain, inc, return_probs=probs)
+
+
+SMALL = [
+    # B, H, L, Ls, N, Lr, include_self, valid
+    (3, 2, 512, 512, 4, 512, True, [4, 2, 0]),           # all valid / half / none (self segment only)
+    (3, 2, 512, 512, 4, 256, False, [1, 3, 0]),          # no self segment: valid 0 = an item that owns no tile at all
+    (2, 1, 1024, 1024, 4, 1024, True, [3, 1]),           # 32x32-token class
+    (2, 2, 576, 128, 3, 192, True, [5, -1]),             # counts outside [0, N]: clamped; query axis not a multiple of 512
+    (9, 2, 1024, 1024, 4, 1024, True, [4, 3, 2, 1, 0, 1, 2, 3, 4]),   # remainder split with per-item K/V ranges
+    # a short self segment before long references, none valid: the split plans its pieces from the FULL tile count, the item has
+    # one tile - most pieces are empty and the LAST one owns no tile but the closed form
+    (1, 2, 128, 64, 5, 384, True, [0]),
+    (2, 1, 64, 64, 5, 384, False, [0, 1]),
+]
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
+@pytest.mark.parametrize("adain", [False, True], ids=["plain", "adain"])
+@pytest.mark.parametrize("case", SMALL, ids=[f"B{c[0]}H{c[1]}L{c[2]}Ls{c[3]}N{c[4]}Lr{c[5]}s{int(c[6])}" for c in SMALL])
+def test_closed_form_against_the_oracle_and_the_walk(ops, case, adain, dtype):
+    B, H, L, Ls, N, Lr, inc, valid = case
+    q, k, v, rk, rv = _inputs(B, H, L, Ls, N, Lr, dtype, 41 + L + N, valid)
+    aff = ops.adain_stats(v, rv, heads=H) if adain else None
+    vt = torch.tensor(valid, dtype=torch.int32, device="cuda")
+    name = _name(ops, q, k, v, rk, rv, H, inc, aff, vt)
+    assert "w128" in name and "zero suffix in closed form" in name, name
+    out, lse = _call(ops, q, k, v, rk, rv, H, inc, aff, vt, return_lse=True)
+    ref = _oracle(q, k, v, rk, rv, H, inc, adain)
+    check_parity(out, ref, dtype, "w128 valid_refs closed form vs the oracle on the zero-filled tensors")
+    walked, lse_w = _call(ops, q, k, v, rk, rv, H, inc, aff, return_lse=True)
+    bound = TOL[dtype] * max(1.0, float(np.abs(ref).max()))
+    assert float((out.float() - walked.float()).abs().max()) <= 2 * bound
+    assert float((lse - lse_w).abs().max()) <= 2e-3
+
+
+def test_reference_far_below_zero_moves_up_to_the_zero_score(ops):
+    """every real score hugely negative (q ~ -k): the zero keys own the softmax; the closed form moves the running reference up
+    to 0 instead of weighing them with 2^(+large)"""
+    dtype = torch.bfloat16
+    B, H, L, N = 1, 1, 256, 2
+    g = torch.Generator().manual_seed(5)
+    base = torch.randn(B, L, 64, generator=g)
+    q = (base * 3 * QC).to(dtype).cuda()
+    k = (-base * 3).to(dtype).cuda()
+    v = torch.randn(B, L, 64, generator=g).to(dtype).cuda()
+    rk = (-base * 3).reshape(B, 1, L, 64).repeat(1, N, 1, 1).to(dtype).cuda()
+    rv = torch.randn(B, N, L, 64, generator=g).to(dtype).cuda()
+    rk[:, 1:] = 0
+    rv[:, 1:] = 0
+    vt = torch.tensor([1], dtype=torch.int32, device="cuda")
+    for adain in (False, True):
+        aff = ops.adain_stats(v, rv, heads=H) if adain else None
+        out = _call(ops, q, k, v, rk, rv, H, True, aff, vt)
+        ref = _oracle(q, k, v, rk, rv, H, True, adain)
+        got = _np64(out)
+        assert np.isfinite(got).all()
+        assert np.abs(got - ref).max() <= TOL[dtype] * max(1.0, np.abs(ref).max())
+
+
+MASS_CASES = [
+    # B, H, L, Ls, N, Lr, include_self, valid (None: no valid_refs)
+    (2, 2, 512, 512, 4, 256, True, None),
+    (2, 2, 512, 512, 4, 256, False, None),
+    (3, 2, 512, 256, 4, 128, True, [4, 1, 0]),
+    (3, 2, 512, 256, 4, 128, False, [4, 1, 0]),
+    (2, 1, 1024, 1024, 2, 1024, True, [1, 2]),
+]
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
+@pytest.mark.parametrize("adain", [False, True], ids=["plain", "adain"])
+@pytest.mark.parametrize("case", MASS_CASES, ids=[f"B{c[0]}L{c[2]}Ls{c[3]}N{c[4]}Lr{c[5]}s{int(c[6])}v{int(c[7] is not None)}" for c in MASS_CASES])
+def test_masses_against_the_oracle_and_the_second_pass(ops, case, adain, dtype):
+    B, H, L, Ls, N, Lr, inc, valid = case
+    q, k, v, rk, rv = _inputs(B, H, L, Ls, N, Lr, dtype, 7 + L + N, valid or [N] * B)
+    aff = ops.adain_stats(v, rv, heads=H) if adain else None
+    vt = torch.tensor(valid, dtype=torch.int32, device="cuda") if valid is not None else None
+    name = _name(ops, q, k, v, rk, rv, H, inc, aff, vt, mass=True)
+    assert "w128" in name and "segment masses" in name, name
+    out0, lse0 = _call(ops, q, k, v, rk, rv, H, inc, aff, vt, return_lse=True)
+    out, lse, mass = _call(ops, q, k, v, rk, rv, H, inc, aff, vt, return_lse=True, return_mass=True)
+    assert torch.equal(out, out0) and torch.equal(lse, lse0), "the by-product changed the attention result"
+    _, p_ref = _oracle(q, k, v, rk, rv, H, inc, adain, probs=True)
+    edges = _edges(Ls, N, Lr, inc)
+    m_ref = np.stack([p_ref[..., a:b].sum(-1) for a, b in zip(edges[:-1], edges[1:])], axis=-1)
+    m = mass.cpu().numpy()
+    assert m.shape == m_ref.shape and np.isfinite(m).all()
+    assert np.abs(m - m_ref).max() <= 2e-3, np.abs(m - m_ref).max()
+    assert np.abs(m.sum(-1) - 1.0).max() <= 1e-5
+    assert m.min() >= -1e-6
+    second = ops.attn_segment_mass(q, k, rk, lse, heads=H, scale=0.125, include_self=inc, q_prescaled=True)
+    assert float((mass - second).abs().max()) <= 1e-4, float((mass - second).abs().max())
+
+
+SPLIT_SHAPES = [("cfg2", 8, 5, 4096, 4), ("cfg4", 8, 5, 4096, 8)]   # top layers: B, H, L, N (cfg 4: eight references)
+
+
+@pytest.mark.parametrize("inc", [True, False], ids=["self", "noself"])
+@pytest.mark.parametrize("adain", [True, False], ids=["adain", "plain"])
+@pytest.mark.parametrize("shape", SPLIT_SHAPES, ids=[s[0] for s in SPLIT_SHAPES])
+def test_remainder_split_at_the_top_layer_shapes(ops, shape, adain, inc):
+    """the items of the last, partially filled round are cut into K/V-range pieces (workspace given); every valid count occurs in
+    the batch.  Masses: against the unsplit launch and the second pass; output: against the oracle on sampled rows"""
+    _, B, H, L, N = shape
+    dtype = torch.bfloat16
+    valid = [(b % (N + 1)) for b in range(B)] if N == 4 else [4, 8, 0, 4, 4, 1, 4, 7]
+    q, k, v, rk, rv = _inputs(B, H, L, L, N, L, dtype, 3 + N, valid)
+    aff = ops.adain_stats(v, rv, heads=H) if adain else None
+    vt = torch.tensor(valid, dtype=torch.int32, device="cuda")
+    out, lse, mass = _call(ops, q, k, v, rk, rv, H, inc, aff, vt, return_lse=True, return_mass=True)
+    nosplit = _call(ops, q, k, v, rk, rv, H, inc, aff, vt, return_mass=True, split=False)[1]
+    second = ops.attn_segment_mass(q, k, rk, lse, heads=H, scale=0.125, include_self=inc, q_prescaled=True)
+    assert float((mass - nosplit).abs().max()) <= 1e-4, float((mass - nosplit).abs().max())
+    assert float((mass - second).abs().max()) <= 1e-4, float((mass - second).abs().max())
+    assert float((mass.sum(-1) - 1).abs().max()) <= 1e-5
+    rows = np.array(sorted(set(np.random.default_rng(3).integers(0, L, 48).tolist() + [0, 511, 512, L - 1])))
+    ref = _oracle(q, k, v, rk, rv, H, inc, adain, rows=rows)
+    check_parity(_np64(out)[:, rows], ref, dtype, "w128 closed form + masses through the remainder split")
+
+
+def test_seeded_sweep(ops):
+    """whole-tile shapes, random counts, mass on and off: closed form against the same kernel walking the zeros, masses
+    against the second pass (IR_SWEEP_CASES / IR_SWEEP_SEED widen it)"""
+    seed = int(os.environ.get("IR_SWEEP_SEED", "4242"))
+    rng = np.random.default_rng(seed)
+    for case in range(int(os.environ.get("IR_SWEEP_CASES", "40"))):
+        B, H = int(rng.integers(1, 4)), int(rng.integers(1, 4))
+        L = int(rng.integers(1, 1600))
+        N = int(rng.integers(1, 7))
+        Lr = 64 * int(rng.integers(1, 9))
+        inc = bool(rng.integers(0, 2))
+        Ls = 64 * int(rng.integers(1, 17))
+        adain = bool(rng.integers(0, 2))
+        want_mass = bool(rng.integers(0, 2))
+        dtype = [torch.float16, torch.bfloat16][case % 2]
+        valid = [int(x) for x in rng.integers(0, N + 1, B)]
+        q, k, v, rk, rv = _inputs(B, H, L, Ls, N, Lr, dtype, seed + case, valid)
+        aff = ops.adain_stats(v, rv, heads=H) if adain else None
+        vt = torch.tensor(valid, dtype=torch.int32, device="cuda")
+        what = f"case {case}: B{B} H{H} L{L} Ls{Ls} N{N} Lr{Lr} self {inc} adain {adain} mass {want_mass} valid {valid} {dtype}"
+        res = _call(ops, q, k, v, rk, rv, H, inc, aff, vt, return_lse=True, return_mass=want_mass)
+        walked = _call(ops, q, k, v, rk, rv, H, inc, aff, return_lse=True, return_mass=want_mass)
+        omax = max(1.0, float(walked[0].float().abs().max()))
+        assert torch.isfinite(res[0].float()).all(), what
+        assert float((res[0].float() - walked[0].float()).abs().max()) <= 2 * TOL[dtype] * omax, what
+        assert float((res[1] - walked[1]).abs().max()) <= 2e-3, what
+        if want_mass:
+            second = ops.attn_segment_mass(q, k, rk, res[1], heads=H, scale=0.125, include_self=inc, q_prescaled=True)
+            assert float((res[2] - second).abs().max()) <= 1e-4, what
+            assert float((res[2] - walked[2]).abs().max()) <= 1e-4, what
+            assert float((res[2].sum(-1) - 1).abs().max()) <= 1e-5, what
+
+
+def test_determinism_including_the_split(ops):
+    B, H, L, N = 8, 5, 4096, 4
+    valid = [4, 3, 2, 1, 4, 3, 2, 1]
+    q, k, v, rk, rv = _inputs(B, H, L, L, N, L, torch.bfloat16, 99, valid)
+    aff = ops.adain_stats(v, rv, heads=H)
+    vt = torch.tensor(valid, dtype=torch.int32, device="cuda")
+    first = _call(ops, q, k, v, rk, rv, H, True, aff, vt, return_lse=True, return_mass=True)
+    for _ in range(9):
+        again = _call(ops, q, k, v, rk, rv, H, True, aff, vt, return_lse=True, return_mass=True)
+        assert all(torch.equal(a, b) for a, b in zip(first, again))
+
+
+_HOST = r"""
+import sys
+sys.path.insert(0, sys.argv[1])
+import torch
+from types import SimpleNamespace
+from face_replace.models.attn_processors import SharedAttnProcessor, register_attention_processor, register_attention_processor_kv_unet
+from instantrestore_amd import ops
+from instantrestore_amd.kv_harvest import get_conditioning_keys_values
+from instantrestore_amd.unet_host import AttnTopologyUNet
+dev = torch.device("cuda:0")
+names = {}
+_orig = ops.shared_attention
+def _spy(q, k, v, rk=None, rv=None, **kw):   # the kernel each call of the processors lands on
+    if rk is not None:
+        nk = {x: kw[x] for x in ("heads", "scale", "include_self", "adain", "q_prescaled", "valid_refs") if x in kw}
+        names.setdefault(q.shape[1], set()).add(ops.shared_attention_kernel_name(q, k, v, rk, rv, return_mass=kw.get("return_mass", False), **nk))
+    res = _orig(q, k, v, rk, rv, **kw)
+    if rk is not None and kw.get("return_mass"):
+        masses.append(res[-1].cpu())   # in call order
+    return res
+masses = []
+ops.shared_attention = _spy
+torch.manual_seed(0)
+cfg = SimpleNamespace(use_adain=True, train_input=True, condition_on_face_embeds=False)
+kv_unet, unet = AttnTopologyUNet(seed=1).to(dev), AttnTopologyUNet(seed=2).to(dev)
+kv_unet.set_attn_processor({n: SharedAttnProcessor(self_attn_idx=None) for n in kv_unet.attn_processors})
+register_attention_processor_kv_unet(kv_unet)
+register_attention_processor(unet, cfg)
+shared = [p for p in unet.attn_processors.values() if type(p) == SharedAttnProcessor and p.self_attn_idx is not None]
+for p in shared:
+    p.save_attention_mass = True
+Bi, Nr, S = 2, 4, 32
+text = torch.randn(1, 77, 1024, device=dev)
+refs, x = torch.randn(Bi * Nr, 4, S, S, device=dev), torch.randn(Bi, 4, S, S, device=dev)
+with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+    keys, vals, valid = get_conditioning_keys_values(kv_unet, refs, None, text.repeat(Bi * Nr, 1, 1), Nr, [4, 2], with_valid=True)
+    y = unet(x, None, encoder_hidden_states=text.repeat(Bi, 1, 1),
+             cross_attention_kwargs={"ref_keys": keys, "ref_values": vals, "ref_valid": valid}).sample
+torch.cuda.synchronize()
+torch.save({"y": y.float().cpu(), "valid": None if valid is None else valid.cpu(), "mass": masses,
+            "names": {k_: sorted(v_) for k_, v_ in names.items()}}, sys.argv[2])
+"""
+
+
+def test_plugin_surface_with_the_override(tmp_path):
+    """two-UNet host, 32x32 latent (top class 1024 tokens), ref_valid and save_attention_mass: IR_ATTN_W128=1 sends the top class to
+    the 128-row kernel's forms; latents and masses against the default dispatch's run.  The two runs are separate processes whose
+    activations differ by 16-bit roundings upstream of most layers, so the masses are held to 5e-3 per layer (measured: 1.6e-3 at a
+    64-token layer); the kernel-level bound of 1e-4 is checked on identical inputs by the tests above"""
+    res = {}
+    for tag, w in (("default", None), ("w128", "1")):
+        env = {k_: v_ for k_, v_ in os.environ.items() if k_ != "IR_ATTN_W128"}
+        if w is not None:
+            env["IR_ATTN_W128"] = w
+        path = str(tmp_path / f"{tag}.pt")
+        r = subprocess.run([sys.executable, "-c", _HOST, REPO, path], capture_output=True, text=True, env=env, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        res[tag] = torch.load(path)
+    d, w = res["default"], res["w128"]
+    assert d["valid"] is not None and d["valid"].tolist() == [4, 2]
+    assert 1024 in w["names"] and all("w128" in n and "zero suffix" in n and "segment masses" in n for n in w["names"][1024]), w["names"]
+    assert not any("w128" in n for n in d["names"][1024]), d["names"]
+    bound = 2 * TOL[torch.bfloat16] * max(1.0, float(d["y"].abs().max()))
+    assert float((w["y"] - d["y"]).abs().max()) <= bound
+    assert len(w["mass"]) == len(d["mass"]) > 0
+    for a, b in zip(w["mass"], d["mass"]):
+        assert a.shape == b.shape and float((a - b).abs().max()) <= 5e-3
+        assert float((a.sum(-1) - 1).abs().max()) <= 1e-5
