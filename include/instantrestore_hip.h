@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define IR_ABI_VERSION 9
+#define IR_ABI_VERSION 10
 #define IR_HEAD_DIM 64
 
 typedef enum ir_status {
@@ -53,6 +53,13 @@ typedef enum ir_dtype { IR_DTYPE_F16 = 0, IR_DTYPE_BF16 = 1 } ir_dtype;
 #define IR_FLAG_OUT_F32 4u      /* out is fp32 (strides in fp32 elements): the result of the SAME kernel the call would launch
                                    otherwise, stored BEFORE its rounding to the 16-bit type - parity instrumentation
                                    (tests show the pre-rounding error of the kernel that ships) */
+#define IR_FLAG_BATCH_INVARIANT 8u /* ABI v10, opt-in: the bytes of every output of batch entry b (out, lse, seg_mass) depend on
+                                   entry b's own inputs and the per-entry parameters only (dtype, len_q, heads, segment lengths,
+                                   n_refs, INCLUDE_SELF, AdaIN on/off, Q_PRESCALED, valid_refs given or not, OUT_F32) - not on
+                                   the batch size, the entry's position, other entries, the stream, graph capture, the workspace,
+                                   whether lse / seg_mass are asked for, IR_ATTN_W128 or the device's CU count.  The kernel and a
+                                   fixed cut of every item into K/V-range pieces (merged in piece order) are chosen from those
+                                   parameters alone (ir_shared_attn_plan).  Not combinable with a non-zero `tuning`. */
 
 /*
  * ir_shared_attn_fwd - fused extended self-attention (flash-style, no probability matrix).
@@ -164,6 +171,28 @@ const char* ir_shared_attn_kernel_name(const ir_shared_attn_args* args);
 int ir_shared_attn_fwd(const ir_shared_attn_args* args, void* stream);
 
 /*
+ * Batch-invariant plan (ABI v10, IR_FLAG_BATCH_INVARIANT; host only, no GPU touched).  Every (batch entry, head, query block)
+ * work item runs `pieces_per_item` K/V-range pieces whose tile boundaries depend on that item alone, merged in piece order
+ * (1: whole items, no merge pass, no workspace - always so for plain attention, n_refs == 0).  Scratch: ir_shared_attn_workspace_bytes_for(args) bytes cover one launch
+ * over the whole batch; a smaller workspace runs the batch as several launches of `batch_per_launch` entries (same per-item
+ * plan, same bytes); a workspace that cannot hold one entry's pieces makes ir_shared_attn_fwd fail with IR_ERR_WORKSPACE.
+ * Without IR_FLAG_BATCH_INVARIANT the plan query returns IR_ERR_INVALID_ARG (the default dispatch plans inside each launch).
+ */
+typedef struct ir_shared_attn_plan_info {
+  uint32_t struct_size;      /* = sizeof(ir_shared_attn_plan_info) */
+  int32_t kernel;            /* IR_TUNE_* value of the kernel family the plan launches (W128, W64X8, PIPE32_PRESCALE_Q, PIPE32_EARLYQK) */
+  int32_t rows_per_item;     /* query rows per work item */
+  int32_t items_per_batch;   /* work items per batch entry: heads * ceil(len_q / rows_per_item) */
+  int32_t pieces_per_item;   /* K/V-range pieces per work item */
+  int32_t batch_per_launch;  /* batch entries per launch with the args' workspace (0: one entry does not fit) */
+  uint64_t workspace_bytes;  /* = ir_shared_attn_workspace_bytes_for(args) */
+} ir_shared_attn_plan_info;
+int ir_shared_attn_plan(const ir_shared_attn_args* args, ir_shared_attn_plan_info* plan);
+/* scratch bytes ir_shared_attn_fwd can use for these arguments in one launch: the batch-invariant plan's pieces with the flag,
+ * ir_shared_attn_workspace_bytes() without it; 0 if the arguments are invalid or the plan needs none */
+size_t ir_shared_attn_workspace_bytes_for(const ir_shared_attn_args* args);
+
+/*
  * ir_attn_probs - materialise attention_probs (B, H, len_q, Lkv) for the dump path.
  *
  * Replaces `self.attention_probs = attention_probs.reshape(B, heads, L, Lkv)`
@@ -185,6 +214,10 @@ int ir_attn_probs(const ir_shared_attn_args* args, void* probs, void* stream);
 #define IR_PROBS_LINES64_K128 5  /* 64 rows x 128 keys */
 #define IR_PROBS_LINES32_K256 6  /* 32 rows x 256 keys (512 B per row and store batch) */
 int ir_attn_probs_ex(const ir_shared_attn_args* args, void* probs, int32_t kernel, void* stream);
+/* IR_FLAG_BATCH_INVARIANT (ABI v10) is accepted by ir_attn_probs[_ex] and ir_attn_segment_mass: every probability and every
+ * mass is computed from its own row of q and the keys of its own batch entry in an order fixed by the per-entry parameters
+ * (IR_PROBS_AUTO: the line kernel when every segment length is a multiple of 8 keys, 64 rows per wave from len_q >= 256,
+ * else the 2-byte-store kernel), so given an invariant lse they are batch invariant. */
 
 /*
  * ir_attn_segment_mass (ABI v8, opt-in) - attention mass per K/V segment without the probability matrix.
@@ -367,11 +400,16 @@ int ir_linear_fwd_scaled(int32_t dtype, int32_t x_is_f32, int64_t m, int32_t n, 
                                    workgroup; 7 and 8 with 64 x 128 per wave), 9: 128x128 with the contraction split over two wave
                                    groups of the workgroup (K / 64 even; partial sums meet in LDS in a fixed order: deterministic, but
                                    not the same fp32 rounding as the single-pass tiles) */
+#define IR_LIN_BATCH_INVARIANT 16 /* ABI v10: ONE kernel per (N, K, bias) for every M, never a split of the contraction - row r of y
+                                     depends on row r of x, on w and on the bias only, whatever the number of rows (batch-invariant
+                                     mode): the 256x256 tile where N % 64 == 0 and K % 64 == 0, the X-stationary kernel elsewhere */
 int ir_linear_fwd_ex(int32_t dtype, int32_t x_is_f32, int64_t m, int32_t n, int32_t k, const void* x, int64_t x_ld, const void* w,
                      int64_t w_ld, const void* bias, void* y, int64_t y_ld, int32_t scale_cols, float col_scale,
                      int32_t kernel, void* stream);
 /* kernel id (IR_LIN_*) the automatic choice makes for a shape, or -1 when no kernel covers it */
 int ir_linear_kernel_for(int64_t m, int32_t n, int32_t k, int32_t has_bias);
+/* ABI v10: the kernel a selector (IR_LIN_AUTO or IR_LIN_BATCH_INVARIANT) resolves to for a shape, or -1 */
+int ir_linear_kernel_for_ex(int64_t m, int32_t n, int32_t k, int32_t has_bias, int32_t selector);
 
 /*
  * ir_linear_fwd_stats - ir_linear_fwd_scaled that ALSO leaves the token statistics of output columns
@@ -392,6 +430,11 @@ int ir_linear_stats_rows(int64_t m, int32_t n, int32_t k, int32_t has_bias);
 int ir_linear_fwd_stats(int32_t dtype, int32_t x_is_f32, int64_t m, int32_t n, int32_t k, const void* x, int64_t x_ld, const void* w,
                         int64_t w_ld, const void* bias, void* y, int64_t y_ld, int32_t scale_cols, float col_scale,
                         int32_t stats_col0, int32_t stats_cols, float* stats_ws, size_t stats_ws_bytes, void* stream);
+/* ABI v10: the same with a kernel selector - IR_LIN_AUTO (= ir_linear_fwd_stats) or IR_LIN_BATCH_INVARIANT; every kernel's
+ * statistics blocks are 64 rows of one wave, so a block's partials depend on its own rows only */
+int ir_linear_fwd_stats_ex(int32_t dtype, int32_t x_is_f32, int64_t m, int32_t n, int32_t k, const void* x, int64_t x_ld, const void* w,
+                           int64_t w_ld, const void* bias, void* y, int64_t y_ld, int32_t scale_cols, float col_scale,
+                           int32_t stats_col0, int32_t stats_cols, float* stats_ws, size_t stats_ws_bytes, int32_t kernel, void* stream);
 /*
  * ir_adain_affine_from_partials - the (a, b) of ir_adain_stats from those partials: one small launch per shared layer.
  *   style_ws: partials of V_self from the shared layer's own q/k/v projection (B sets of len_self rows, style_rows per block);
@@ -404,7 +447,10 @@ int ir_adain_affine_from_partials(int32_t batch, int32_t heads, int32_t n_refs, 
                                   const float* style_ws, int32_t style_rows, const float* content_ws, int32_t content_rows,
                                   const float* content_mean, const float* content_std, const int32_t* valid, float eps,
                                   float* a, float* b, void* stream);
-/* mean and unbiased std (no eps) of n_sets matrices of `len` rows from their partials: fp32 (n_sets, H, 64) each */
+/* mean and unbiased std (no eps) of n_sets matrices of `len` rows from their partials: fp32 (n_sets, H, 64) each.
+ * Batch invariance (ABI v10): this merge, ir_adain_affine_from_partials, ir_token_stats and ir_adain_stats[_cached] pick their
+ * kernels from per-set sizes (token counts, rows per block, N, H) and merge every set's partials in a fixed order inside one
+ * workgroup: the statistics of a set never depend on how many other sets share the call. */
 int ir_token_stats_from_partials(int32_t n_sets, int32_t heads, int32_t len, const float* ws, int32_t rows, float* mean, float* std,
                                  void* stream);
 

@@ -13,10 +13,12 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # IR_LIB_PATH: load an alternative build of the same ABI (compiler-flag A/B experiments)
 LIB_PATH = os.environ.get("IR_LIB_PATH") or os.path.join(_HERE, "libinstantrestore_hip.so")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 IR_DTYPE_F16, IR_DTYPE_BF16 = 0, 1
 IR_FLAG_INCLUDE_SELF, IR_FLAG_Q_PRESCALED, IR_FLAG_OUT_F32 = 1, 2, 4
+IR_FLAG_BATCH_INVARIANT = 8   # ABI v10
+IR_LIN_BATCH_INVARIANT = 16   # ABI v10: the kernel selector of ir_linear_fwd_ex / ir_linear_fwd_stats_ex / ir_linear_kernel_for_ex
 
 i32, i64, f32, u32, vp = C.c_int32, C.c_int64, C.c_float, C.c_uint32, C.c_void_p
 
@@ -33,6 +35,13 @@ class SharedAttnArgs(C.Structure):
                               "o_sb", "o_sl", "o_sh")]
         + [("workspace", vp), ("workspace_bytes", C.c_uint64), ("tuning", i32), ("reserved", i32), ("valid_refs", vp), ("seg_mass", vp)]
     )
+
+
+class SharedAttnPlan(C.Structure):
+    """mirror of ``ir_shared_attn_plan_info`` (ABI v10: the batch-invariant plan of a call)"""
+
+    _fields_ = [("struct_size", u32), ("kernel", i32), ("rows_per_item", i32), ("items_per_batch", i32), ("pieces_per_item", i32),
+                ("batch_per_launch", i32), ("workspace_bytes", C.c_uint64)]
 
 
 class ImageDesc(C.Structure):
@@ -52,6 +61,8 @@ SYMBOLS = {
     "ir_shared_attn_workspace_bytes": (C.c_size_t, []),
     "ir_shared_attn_fwd": (C.c_int, [C.POINTER(SharedAttnArgs), vp]),
     "ir_shared_attn_kernel_name": (C.c_char_p, [C.POINTER(SharedAttnArgs)]),
+    "ir_shared_attn_plan": (C.c_int, [C.POINTER(SharedAttnArgs), C.POINTER(SharedAttnPlan)]),
+    "ir_shared_attn_workspace_bytes_for": (C.c_size_t, [C.POINTER(SharedAttnArgs)]),
     "ir_time_shared_attn_fwd": (C.c_int, [C.POINTER(SharedAttnArgs), i32, vp, C.POINTER(f32)]),
     "ir_bench_mfma_stream_scratch_bytes": (C.c_size_t, []),
     "ir_bench_mfma_stream": (C.c_int, [i32, i32, i32, i32, vp, C.c_size_t, vp, C.POINTER(f32)]),
@@ -74,8 +85,10 @@ SYMBOLS = {
     "ir_linear_fwd_scaled": (C.c_int, [i32, i32, i64, i32, i32, vp, i64, vp, i64, vp, vp, i64, i32, f32, vp]),
     "ir_linear_fwd_ex": (C.c_int, [i32, i32, i64, i32, i32, vp, i64, vp, i64, vp, vp, i64, i32, f32, i32, vp]),
     "ir_linear_kernel_for": (C.c_int, [i64, i32, i32, i32]),
+    "ir_linear_kernel_for_ex": (C.c_int, [i64, i32, i32, i32, i32]),
     "ir_linear_stats_rows": (C.c_int, [i64, i32, i32, i32]),
     "ir_linear_fwd_stats": (C.c_int, [i32, i32, i64, i32, i32, vp, i64, vp, i64, vp, vp, i64, i32, f32, i32, i32, vp, C.c_size_t, vp]),
+    "ir_linear_fwd_stats_ex": (C.c_int, [i32, i32, i64, i32, i32, vp, i64, vp, i64, vp, vp, i64, i32, f32, i32, i32, vp, C.c_size_t, i32, vp]),
     "ir_adain_affine_from_partials": (C.c_int, [i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, f32, vp, vp, vp]),
     "ir_token_stats_from_partials": (C.c_int, [i32, i32, i32, vp, i32, vp, vp, vp]),
     "ir_zero_invalid_refs": (C.c_int, [i32, i32, i32, i32, vp, vp, i64, i64, i64, i64,

@@ -20,6 +20,12 @@ reference's own path rounds the scores to 16 bit before its softmax, which this 
 The processors own no parameters and no buffers (the reference's checkpoints are loaded with
 ``strict=True``, test.py:47-50).  They never fall back to torch math: CPU tensors, fp32
 activations outside autocast, attention masks and missing libraries raise.
+
+Batch-invariant mode (ABI v10; :func:`set_batch_invariant`, or the plain attribute ``batch_invariant`` of
+:class:`SharedAttnProcessor` / :class:`AttnProcessor`): every GEMM, statistics pass and attention of a processor then runs
+the library's batch-invariant plans, so an identity's outputs (``attention_mass`` / ``attention_probs`` included) do not
+depend on how many identities share its batch or where it sits.  A projection that would run on the vendor GEMM - a shape this
+library's GEMMs do not cover, or one left to the module call (biased / unfoldable projections, autograd enabled) - raises instead.  The UNet body around the processors (convolutions, norms) is not covered.
 """
 from __future__ import annotations
 
@@ -89,8 +95,8 @@ def _kv_source(attn, st: _Prepared) -> torch.Tensor:
     return st.encoder
 
 
-def _epilogue(attn, st: _Prepared, tokens: torch.Tensor) -> torch.Tensor:
-    out = _project_out(attn, tokens)   # linear proj (LoRA-wrapped on the main UNet)
+def _epilogue(attn, st: _Prepared, tokens: torch.Tensor, bi: bool = False) -> torch.Tensor:
+    out = _project_out(attn, tokens, bi)   # linear proj (LoRA-wrapped on the main UNet)
     out = attn.to_out[1](out)      # dropout (p = 0)
     if st.ndim == 4:
         bsz, ch, hh, ww = st.shape4
@@ -115,10 +121,26 @@ def _own_gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]) ->
     return bool(_ops.linear_supported(x, w, bias))
 
 
-def _linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+def _linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], bi: bool = False) -> torch.Tensor:
     if _ops.linear_supported(x, w, bias):
-        return _ops.linear(x, w, bias)
+        return _ops.linear(x, w, bias, batch_invariant=True) if bi else _ops.linear(x, w, bias)
+    if bi:   # the vendor GEMM picks its kernel (and its summation order) from the row count
+        raise NotImplementedError(f"batch-invariant mode: projection x {tuple(x.shape)} {x.dtype} @ w {tuple(w.shape)} is not covered by "
+                                  "this library's GEMMs (K % 64 == 0 and N % 64 == 0, or K <= 320 / 640 with N % 32 == 0)")
     return torch.nn.functional.linear(x, w, bias)
+
+
+def _module_call(bi: bool, what: str) -> None:
+    """the mode's guard in front of every projection that would run as the module call itself (``nn.Linear`` -> ``F.linear``, the
+    vendor GEMM, whose kernel and summation order follow the row count): it raises instead"""
+    if bi:
+        raise NotImplementedError(f"batch-invariant mode: {what} would run as a module call (F.linear: the vendor GEMM picks its "
+                                  "kernel from the row count); only projections this library's GEMMs run are covered")
+
+
+def _bi_kw(bi: bool) -> dict:
+    """the keyword of the batch-invariant mode, handed to ``_ops`` only when it is on (a stand-in ``_ops`` without it keeps working)"""
+    return {"batch_invariant": True} if bi else {}
 
 
 LOG2E = 1.4426950408889634
@@ -130,7 +152,7 @@ FOLD_MIN_REF_TOKENS = 8   # reference token axes shorter than this get their Ada
 FUSED_STATS = True  # own fused q/k/v GEMM: the token statistics of its V third (AdaIN) are its workgroups' tail, no pass over V
 
 
-def _project_qkv(attn, st: _Prepared, want_stats: bool = False):
+def _project_qkv(attn, st: _Prepared, want_stats: bool = False, bi: bool = False):
     """``to_q`` / ``to_k`` / ``to_v`` of the reference (attn_processors.py:222-230).  Returns
     ``(q, k, v, q_prescaled, v_stats)``; ``v_stats`` is ``None`` unless ``want_stats`` and the fused GEMM could leave
     the partial token statistics of V behind (``ops.ColumnStats``: what ``adain`` needs of V, attn_processors.py:9-10,
@@ -153,12 +175,13 @@ def _project_qkv(attn, st: _Prepared, want_stats: bool = False):
     src = _kv_source(attn, st)
     tq, tk, tv = attn.to_q, attn.to_k, attn.to_v
     if torch.is_grad_enabled():
+        _module_call(bi, "q/k/v with autograd enabled")
         return tq(st.hidden), tk(src), tv(src), False, None
     if st.encoder is not None:
         # cross attention (the f-1 layers, attn_processors.py:224-230 with encoder_hidden_states): q from the image tokens,
         # k / v from the text states - different inputs, so no q/k/v fusion, but still this library's GEMMs (round 4: the
         # tiny-M shapes lead the vendor GEMM + its cast pass, profiles/r4_gemm_probe_small.txt) and ONE GEMM for k and v
-        q = _project_single(attn, "_ir_q_cache", "_ir_q_bias_cache", tq, st.hidden)
+        q = _project_single(attn, "_ir_q_cache", "_ir_q_bias_cache", tq, st.hidden, bi)
         ek, ev = _lora.effective_linear(tk), _lora.effective_linear(tv)
         if ek is not None and ev is not None and ek[0].bias is None and ev[0].bias is None and ek[0].weight.shape == ev[0].weight.shape:
             dtype = _autocast_or(ek[0].weight, src)
@@ -166,13 +189,15 @@ def _project_qkv(attn, st: _Prepared, want_stats: bool = False):
             xs = src
             if xs.dtype != dtype and not (FUSED_CAST and _own_gemm(xs, w, None)):
                 xs = xs.to(dtype)
-            kv = _linear(xs, w, None)
+            kv = _linear(xs, w, None, bi)
             c = w.shape[0] // 2
             return q, kv[..., :c], kv[..., c:], False, None
+        _module_call(bi, "cross-attention k/v that cannot be fused")
         return q, tk(src), tv(src), False, None
     effs = [_lora.effective_linear(m) for m in (tq, tk, tv)]
     if any(e is None or e[0].bias is not None for e in effs) or \
             not (effs[0][0].weight.shape == effs[1][0].weight.shape == effs[2][0].weight.shape):
+        _module_call(bi, "biased or unfoldable q/k/v projections")
         return tq(st.hidden), tk(src), tv(src), False, None
     dtype = _autocast_or(effs[0][0].weight, st.hidden)
     w = _lora.cached_weight(attn, "_ir_qkv_cache", (tq, tk, tv), dtype)
@@ -181,8 +206,10 @@ def _project_qkv(attn, st: _Prepared, want_stats: bool = False):
     own = _own_gemm(x, w, None)      # fp32 activations go straight in: the own GEMM casts them while loading
     if x.dtype != dtype and not (own and FUSED_CAST):
         x = x.to(dtype)
-    presc = bool(PRESCALE_Q and c % 32 == 0 and own and _ops.tuning_supports_prescaled_q())
+    # (batch-invariant mode: the A/B tuning hook does not reach the attention, so it does not decide the q form either)
+    presc = bool(PRESCALE_Q and c % 32 == 0 and own and (bi or _ops.tuning_supports_prescaled_q()))
     kw = dict(scale_cols=c, col_scale=float(attn.scale) * LOG2E) if presc else {}
+    kw.update(_bi_kw(bi))
     vstats = None
     if want_stats and FUSED_STATS and own and x.dim() == 3 and c % _ops.HEAD_DIM == 0:
         # token statistics of the V third as the GEMM's tail: whole row blocks per token set (rows | L), whole heads
@@ -190,15 +217,16 @@ def _project_qkv(attn, st: _Prepared, want_stats: bool = False):
         if rows > 0 and x.shape[1] % rows == 0 and x.shape[1] // rows <= _ops.STATS_MAX_CHUNKS:
             qkv, vstats = _ops.linear(x, w, None, stats=(2 * c, c), **kw)
     if vstats is None:
-        qkv = _ops.linear(x, w, None, **kw) if presc else _linear(x, w, None)
+        qkv = _ops.linear(x, w, None, **kw) if presc else _linear(x, w, None, bi)
     return qkv[..., :c], qkv[..., c:2 * c], qkv[..., 2 * c:], presc, vstats
 
 
-def _project_single(attn, slot: str, bias_slot: str, module, x: torch.Tensor) -> torch.Tensor:
+def _project_single(attn, slot: str, bias_slot: str, module, x: torch.Tensor, bi: bool = False) -> torch.Tensor:
     """one projection module (plain ``nn.Linear`` or a foldable LoRA wrapper in inference state) as one GEMM of this library
     against its cached folded weight; the module call itself when it cannot be folded"""
     eff = _lora.effective_linear(module)
     if eff is None:
+        _module_call(bi, "an unfoldable projection")
         return module(x)
     dtype = _autocast_or(eff[0].weight, x)
     w = _lora.cached_weight(attn, slot, (module,), dtype)
@@ -207,10 +235,10 @@ def _project_single(attn, slot: str, bias_slot: str, module, x: torch.Tensor) ->
         bias = _lora.cached_cast(attn, bias_slot, bias, dtype)
     if x.dtype != dtype and not (FUSED_CAST and _own_gemm(x, w, bias)):
         x = x.to(dtype)
-    return _linear(x, w, bias)
+    return _linear(x, w, bias, bi)
 
 
-def _project_kv_only(attn, st: _Prepared):
+def _project_kv_only(attn, st: _Prepared, bi: bool = False):
     """``to_k`` / ``to_v`` alone (the last K/V-capture layer under early exit): the lower two thirds of
     the cached fused weight when there is one, the two module calls otherwise."""
     src = _kv_source(attn, st)
@@ -225,19 +253,22 @@ def _project_kv_only(attn, st: _Prepared):
             x = st.hidden
             if x.dtype != dtype and not (FUSED_CAST and _own_gemm(x, w[c:], None)):
                 x = x.to(dtype)
-            kv = _linear(x, w[c:], None)
+            kv = _linear(x, w[c:], None, bi)
             return kv[..., :c], kv[..., c:]
+    _module_call(bi, "k/v projections that cannot be fused")
     return tk(src), tv(src)
 
 
-def _project_out(attn, tokens: torch.Tensor) -> torch.Tensor:
+def _project_out(attn, tokens: torch.Tensor, bi: bool = False) -> torch.Tensor:
     """``to_out[0]`` (attn_processors.py:267): one GEMM also when the module is a LoRA wrapper in
     inference state; the module call itself in training or when it cannot be folded."""
     proj = attn.to_out[0]
     if torch.is_grad_enabled():
+        _module_call(bi, "the out projection with autograd enabled")
         return proj(tokens)
     eff = _lora.effective_linear(proj)
     if eff is None:
+        _module_call(bi, "an unfoldable out projection")
         return proj(tokens)
     dtype = _autocast_or(eff[0].weight, tokens)
     w = _lora.cached_weight(attn, "_ir_out_cache", (proj,), dtype)
@@ -245,7 +276,7 @@ def _project_out(attn, tokens: torch.Tensor) -> torch.Tensor:
     if bias is not None and bias.dtype != dtype:
         bias = _lora.cached_cast(attn, "_ir_out_bias_cache", bias, dtype)
     x = tokens if tokens.dtype == dtype else tokens.to(dtype)
-    return _linear(x, w, bias)
+    return _linear(x, w, bias, bi)
 
 
 def _stats_cached(value: torch.Tensor, cstats, heads: int):
@@ -307,6 +338,7 @@ class AttnProcessor(nn.Module):
         self.v_mean, self.v_std = None, None   # every reference V, fp32 (B*N, H, 64) - constant per identity
         self.v_part = None                # ... or (round 4) the partials the q/k/v GEMM left behind (ops.ColumnStats): merged
                                           # by the shared layer's affine kernel, or into (mean, std) on demand
+        self.batch_invariant = False      # ABI v10 (plain attribute; set_batch_invariant): batch-invariant GEMMs and attention
 
     def reset(self):
         self.keys, self.values = None, None
@@ -343,18 +375,20 @@ class AttnProcessor(nn.Module):
         if group and all(p.keys is not None for p in group if p is not self):
             # every other capturing layer has run: this is the last one, and only its to_k / to_v are still
             # needed - no query, no attention, no out projection
-            self.keys, self.values = _project_kv_only(attn, st)
+            self.keys, self.values = _project_kv_only(attn, st, self.batch_invariant)
             self._stash_stats(attn)
             self._mark_ready()
             raise ReferenceCaptureComplete()
-        query, key, value, presc, vstats = _project_qkv(attn, st, want_stats=bool(self.capture_stats))
+        bi = bool(self.batch_invariant)
+        query, key, value, presc, vstats = _project_qkv(attn, st, want_stats=bool(self.capture_stats), bi=bi)
         self.keys, self.values = key, value  # consumed in place by the shared layers: no copies
         self._stash_stats(attn, vstats)
         self._mark_ready()
         _same_16bit(query, key, value)
         kw = {"q_prescaled": True} if presc else {}
+        kw.update(_bi_kw(bi))
         tokens = _ops.shared_attention(query, key, value, heads=attn.heads, scale=attn.scale, include_self=True, **kw)
-        return _epilogue(attn, st, tokens)
+        return _epilogue(attn, st, tokens, bi)
 
 
 # ------------------------------------------------------------------------------------------
@@ -423,6 +457,9 @@ class SharedAttnProcessor(nn.Module):
         # model guarantees); ``attention_mass[..., int(train_input):]`` is the per-REFERENCE form (what the demo presumably meant).
         self.save_attention_mass = False
         self.attention_mass = None
+        # ABI v10 (plain attribute; set_batch_invariant): every GEMM and attention of this processor runs the library's batch-invariant
+        # plans - an identity's output, attention_mass and attention_probs do not depend on the rest of its batch
+        self.batch_invariant = False
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                 ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None):
@@ -434,7 +471,8 @@ class SharedAttnProcessor(nn.Module):
         # the GEMM's statistics tail (style partials of this layer's own V) only pays when the content statistics arrive
         # precomputed (``ref_stats``): without them ir_adain_stats reads every V anyway and would throw the partials away
         have_cstats = bool(shared and ref_stats is not None and ref_stats[self.self_attn_idx] is not None)
-        query, key, value, presc, vstats = _project_qkv(attn, st, want_stats=bool(self.use_adain and have_cstats))
+        bi = bool(getattr(self, "batch_invariant", False))
+        query, key, value, presc, vstats = _project_qkv(attn, st, want_stats=bool(self.use_adain and have_cstats), bi=bi)
 
         ref_k = ref_v = None
         include_self = True
@@ -490,6 +528,7 @@ class SharedAttnProcessor(nn.Module):
         want_probs = bool(self.save_self_attentions)
         want_mass = bool(getattr(self, "save_attention_mass", False))
         kw = {"q_prescaled": True} if presc else {}
+        kw.update(_bi_kw(bi))
         if shared and ref_valid is not None:
             kw["valid_refs"] = ref_valid
         # the masses are a by-product of the attention launch itself (ABI v9 ``seg_mass``: the kernels hold the row sums at every
@@ -505,10 +544,10 @@ class SharedAttnProcessor(nn.Module):
             # already carries scale * log2(e): its scores are exponents, ln 2 turns them into the logits of the LSE
             self.attention_probs = _ops.attn_probs(query, key, ref_k, lse, heads=attn.heads,
                                                    scale=0.6931471805599453 if presc else attn.scale,
-                                                   include_self=include_self)
+                                                   include_self=include_self, **_bi_kw(bi))
         else:
             tokens = res
-        return _epilogue(attn, st, tokens)
+        return _epilogue(attn, st, tokens, bi)
 
 
 # ------------------------------------------------------------------------------------------
@@ -559,6 +598,18 @@ def register_attention_processor(unet, cfg, save_self_attentions: bool = False):
     _lora.install_invalidation_hook(unet)
 
 
+def set_batch_invariant(unet, enabled: bool = True) -> int:
+    """Set ``batch_invariant`` on every :class:`SharedAttnProcessor` and :class:`AttnProcessor` of ``unet`` (the main UNet or the
+    reference UNet; call it on both) - the plain attribute, so the processors' constructors stay the reference's.  Returns how
+    many processors it reached."""
+    n = 0
+    for proc in unet.attn_processors.values():
+        if isinstance(proc, (SharedAttnProcessor, AttnProcessor)):
+            proc.batch_invariant = bool(enabled)
+            n += 1
+    return n
+
+
 def register_attention_processor_kv_unet(unet):
     """Put the K/V-capturing :class:`AttnProcessor` on the decoder self-attentions of the frozen
     reference UNet and leave every other processor as it is (attn_processors.py:324-331)."""
@@ -575,4 +626,4 @@ def register_attention_processor_kv_unet(unet):
 
 
 __all__ = ["adain", "AttnProcessor", "FaceIDAttnProcessor", "SharedAttnProcessor",
-           "register_attention_processor", "register_attention_processor_kv_unet"]
+           "register_attention_processor", "register_attention_processor_kv_unet", "set_batch_invariant"]

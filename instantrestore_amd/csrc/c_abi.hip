@@ -32,7 +32,9 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
   if (a->batch <= 0 || a->heads <= 0 || a->len_q <= 0) return fail(IR_ERR_INVALID_ARG, "batch/heads/len_q must be > 0");
   if (a->n_refs < 0 || a->len_self < 0 || a->len_ref < 0) return fail(IR_ERR_INVALID_ARG, "negative length");
   const bool inc = (a->flags & IR_FLAG_INCLUDE_SELF) != 0;
-  if ((a->flags & ~(IR_FLAG_INCLUDE_SELF | IR_FLAG_Q_PRESCALED | IR_FLAG_OUT_F32)) != 0) return fail(IR_ERR_INVALID_ARG, "unknown flag bits 0x%x", a->flags);
+  if ((a->flags & ~(IR_FLAG_INCLUDE_SELF | IR_FLAG_Q_PRESCALED | IR_FLAG_OUT_F32 | IR_FLAG_BATCH_INVARIANT)) != 0) return fail(IR_ERR_INVALID_ARG, "unknown flag bits 0x%x", a->flags);
+  if ((a->flags & IR_FLAG_BATCH_INVARIANT) && a->tuning != IR_TUNE_DEFAULT)
+    return fail(IR_ERR_INVALID_ARG, "IR_FLAG_BATCH_INVARIANT chooses its own kernel: tuning must be 0 (got %d)", a->tuning);
   if (a->reserved != 0) return fail(IR_ERR_INVALID_ARG, "reserved must be 0");
   if (!ir_attn_variant_available(a->tuning)) return fail(IR_ERR_UNSUPPORTED, "tuning value %d is not available in this build", a->tuning);
   if (inc && a->len_self <= 0) return fail(IR_ERR_INVALID_ARG, "INCLUDE_SELF with len_self == 0");
@@ -93,6 +95,63 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
   return IR_OK;
 }
 
+bool batch_invariant(const ir_shared_attn_args* a) { return (a->flags & IR_FLAG_BATCH_INVARIANT) != 0; }
+
+// ABI v10: the batch-invariant plan of a call whose AttnKParams are built; seg_mass counts wherever it is asked for (it sizes the pieces'
+// partials, never the kernel or the cut)
+IrAttnBiPlan bi_plan_of(const ir_shared_attn_args* a, const AttnKParams& p0) {
+  AttnKParams p = p0;
+  p.seg_cum = (float*)a->seg_mass;
+  IrAttnBiPlan pl;
+  ir_attn_bi_plan(p, &pl);
+  return pl;
+}
+
+// batch entries per launch that the caller's workspace holds (0: not even one)
+int bi_batch_per_launch(const IrAttnBiPlan& pl, int batch, size_t ws_bytes) {
+  if (pl.pieces <= 1 || ir_attn_bi_workspace_bytes(pl, batch) <= ws_bytes) return batch;
+  const size_t chunk_items = 8 * (ws_bytes / (8 * (size_t)pl.pieces * pl.piece_bytes));   // whole XCD chunks of items
+  const size_t nb = chunk_items / (size_t)pl.items;
+  return nb < (size_t)batch ? (int)nb : batch;
+}
+
+// the part of a call that covers batch entries [b0, b0 + nb): every pointer moved by b0 entries
+AttnKParams batch_slice(const AttnKParams& p, int b0, int nb) {
+  AttnKParams q = p;
+  q.B = nb;
+  q.q = (const char*)p.q + (int64_t)b0 * p.q_sb * 2;
+  if (p.k_self != nullptr) { q.k_self = (const char*)p.k_self + (int64_t)b0 * p.ks_sb * 2; q.v_self = (const char*)p.v_self + (int64_t)b0 * p.vs_sb * 2; }
+  if (p.k_ref != nullptr) { q.k_ref = (const char*)p.k_ref + (int64_t)b0 * p.kr_sb * 2; q.v_ref = (const char*)p.v_ref + (int64_t)b0 * p.vr_sb * 2; }
+  if (p.aa != nullptr) { q.aa = p.aa + (int64_t)b0 * p.N * p.H * 64; q.ab = p.ab + (int64_t)b0 * p.N * p.H * 64; }
+  q.out = (char*)p.out + (int64_t)b0 * p.o_sb * (p.out_f32 ? 4 : 2);
+  if (p.lse != nullptr) q.lse = p.lse + (int64_t)b0 * p.H * p.Lq;
+  if (p.seg_cum != nullptr) q.seg_cum = p.seg_cum + (int64_t)b0 * p.H * p.Lq * p.nseg_out;
+  if (p.valid != nullptr) q.valid = p.valid + b0;
+  return q;
+}
+
+// the forward launch of a validated call: the default dispatch (tuning), or the batch-invariant plan over as many launches as the
+// workspace needs (each entry's plan is the same in every one of them)
+int launch_fwd(const ir_shared_attn_args* a, const AttnKParams& p, hipStream_t s) {
+  if (!batch_invariant(a)) {
+    const hipError_t e = ir_launch_shared_attn_fwd(p, a->dtype, a->tuning, s);
+    if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "shared_attn_fwd launch: %s", hipGetErrorString(e));
+    return IR_OK;
+  }
+  IrAttnBiPlan pl;
+  ir_attn_bi_plan(p, &pl);
+  const int per = bi_batch_per_launch(pl, p.B, p.ws_bytes);
+  if (per <= 0)
+    return fail(IR_ERR_WORKSPACE, "batch-invariant plan (%d pieces per item): workspace %zu < %zu bytes for one batch entry, %zu for the whole batch "
+                "(ir_shared_attn_workspace_bytes_for)", pl.pieces, p.ws_bytes, ir_attn_bi_workspace_bytes(pl, 1), ir_attn_bi_workspace_bytes(pl, p.B));
+  for (int b0 = 0; b0 < p.B; b0 += per) {
+    const AttnKParams q = batch_slice(p, b0, p.B - b0 < per ? p.B - b0 : per);
+    const hipError_t e = ir_launch_shared_attn_fwd_bi(q, a->dtype, pl, s);
+    if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "shared_attn_fwd (batch-invariant) launch: %s", hipGetErrorString(e));
+  }
+  return IR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -112,6 +171,17 @@ const char* ir_shared_attn_kernel_name(const ir_shared_attn_args* args) {
   p.seg_cum = (float*)args->seg_mass;
   const int v = args->tuning & 31;
   const bool fold = p.aa != nullptr;
+  if (batch_invariant(args)) {   // the plan's kernel family and cut; the name does not change with seg_mass (the output does not either)
+    static thread_local char name[256];
+    const IrAttnBiPlan pl = bi_plan_of(args, p);
+    const char* base = pl.kernel == 16 ? (fold ? "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, AdaIN ratio-frame fold, forms>"
+                                               : "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, forms>")
+                     : pl.kernel == 13 ? (fold ? "shared_attn_fwd_w64_kernel<64 rows/wave, 8 waves, AdaIN ratio-frame fold>" : "shared_attn_fwd_w64_kernel<64 rows/wave, 8 waves>")
+                     : pl.kernel == 11 ? (fold ? "shared_attn_fwd_pipe_kernel<4 waves, lazy max, pre-scaled Q, AdaIN fold>" : "shared_attn_fwd_pipe_kernel<4 waves, lazy max, pre-scaled Q>")
+                                       : (fold ? "shared_attn_fwd_pipe_kernel<4 waves, lazy max, early QK, AdaIN fold>" : "shared_attn_fwd_pipe_kernel<4 waves, lazy max, early QK>");
+    snprintf(name, sizeof(name), "%s [batch-invariant: %d piece%s per %d-row item]", base, pl.pieces, pl.pieces > 1 ? "s" : "", pl.rows);
+    return name;
+  }
   const bool w64 = (v == 0 && ir_attn_default_is_w64(p)) || v == 13;
   if ((v == 16 || (v == 0 && ir_attn_default_is_w128(p))) && ir_attn_w128_supports(p)) {
     static const char* const names[8] = {
@@ -148,13 +218,36 @@ const char* ir_shared_attn_kernel_name(const ir_shared_attn_args* args) {
 // 8 XCDs x 64 pieces x 512 rows x (64 + 2) floats: the largest remainder split of any kernel (512-row items)
 size_t ir_shared_attn_workspace_bytes(void) { return (size_t)8 * 64 * 512 * 66 * sizeof(float); }
 
+size_t ir_shared_attn_workspace_bytes_for(const ir_shared_attn_args* args) {
+  AttnKParams p;
+  if (build_attn_params(args, &p, false) != IR_OK) return 0;
+  if (!batch_invariant(args)) return ir_shared_attn_workspace_bytes();
+  return ir_attn_bi_workspace_bytes(bi_plan_of(args, p), p.B);
+}
+
+int ir_shared_attn_plan(const ir_shared_attn_args* args, ir_shared_attn_plan_info* plan) {
+  if (plan == nullptr) return fail(IR_ERR_INVALID_ARG, "plan is NULL");
+  if (plan->struct_size != sizeof(ir_shared_attn_plan_info))
+    return fail(IR_ERR_INVALID_ARG, "plan struct_size %u != %zu (ABI mismatch)", plan->struct_size, sizeof(ir_shared_attn_plan_info));
+  AttnKParams p;
+  const int rc = build_attn_params(args, &p, false);
+  if (rc != IR_OK) return rc;
+  if (!batch_invariant(args)) return fail(IR_ERR_INVALID_ARG, "ir_shared_attn_plan reports the IR_FLAG_BATCH_INVARIANT plan (the default dispatch plans per launch)");
+  const IrAttnBiPlan pl = bi_plan_of(args, p);
+  plan->kernel = pl.kernel;
+  plan->rows_per_item = pl.rows;
+  plan->items_per_batch = pl.items;
+  plan->pieces_per_item = pl.pieces;
+  plan->batch_per_launch = bi_batch_per_launch(pl, p.B, p.ws_bytes);
+  plan->workspace_bytes = ir_attn_bi_workspace_bytes(pl, p.B);
+  return IR_OK;
+}
+
 int ir_shared_attn_fwd(const ir_shared_attn_args* args, void* stream) {
   AttnKParams p;
   const int rc = build_attn_params(args, &p, true);
   if (rc != IR_OK) return rc;
-  const hipError_t e = ir_launch_shared_attn_fwd(p, args->dtype, args->tuning, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "shared_attn_fwd launch: %s", hipGetErrorString(e));
-  return IR_OK;
+  return launch_fwd(args, p, (hipStream_t)stream);
 }
 
 int ir_time_shared_attn_fwd(const ir_shared_attn_args* args, int32_t iters, void* stream, float* ms_per_launch) {
@@ -166,7 +259,9 @@ int ir_time_shared_attn_fwd(const ir_shared_attn_args* args, int32_t iters, void
   hipEvent_t e0, e1;
   if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return fail(IR_ERR_LAUNCH, "hipEventCreate failed");
   hipError_t e = hipEventRecord(e0, s);
-  for (int i = 0; i < iters && e == hipSuccess; ++i) e = ir_launch_shared_attn_fwd(p, args->dtype, args->tuning, s);
+  for (int i = 0; i < iters && e == hipSuccess; ++i)
+    e = batch_invariant(args) ? (launch_fwd(args, p, s) == IR_OK ? hipSuccess : hipErrorLaunchFailure)
+                              : ir_launch_shared_attn_fwd(p, args->dtype, args->tuning, s);
   if (e == hipSuccess) e = hipEventRecord(e1, s);
   if (e == hipSuccess) e = hipEventSynchronize(e1);
   float ms = 0.f;
@@ -471,6 +566,20 @@ static bool x_stationary_covers(int32_t n, int32_t k, const void* bias) {
   return ((k % 64 == 0 && k <= 320) || k == 640) && n % 32 == 0 && (bias == nullptr || n <= kLinearMaxBiasN);
 }
 
+// ABI v10 (IR_LIN_BATCH_INVARIANT): one kernel per (N, K, bias) whatever M is, and never a split contraction - every element of y
+// is the same fp32 sum in the same order at any number of rows
+static int linear_kernel_batch_invariant(int32_t n, int32_t k, int32_t has_bias) {
+  static const int dummy = 0;
+  if (k % 64 == 0 && n % 64 == 0) return IR_LIN_TILED_FIRST + IR_LIN_TILE_256x256;
+  return x_stationary_covers(n, k, has_bias ? (const void*)&dummy : nullptr) ? IR_LIN_X_STATIONARY : -1;
+}
+
+int ir_linear_kernel_for_ex(int64_t m, int32_t n, int32_t k, int32_t has_bias, int32_t selector) {
+  if (selector == IR_LIN_AUTO) return ir_linear_kernel_for(m, n, k, has_bias);
+  if (selector == IR_LIN_BATCH_INVARIANT) return m > 0 ? linear_kernel_batch_invariant(n, k, has_bias) : -1;
+  return -1;
+}
+
 int ir_linear_kernel_for(int64_t m, int32_t n, int32_t k, int32_t has_bias) {
   static const int dummy = 0;
   const bool xs = x_stationary_covers(n, k, has_bias ? (const void*)&dummy : nullptr);
@@ -511,6 +620,16 @@ int ir_linear_fwd_stats(int32_t dtype, int32_t x_is_f32, int64_t m, int32_t n, i
                         int32_t stats_col0, int32_t stats_cols, float* stats_ws, size_t stats_ws_bytes, void* stream) {
   if (stats_ws == nullptr) return fail(IR_ERR_INVALID_ARG, "stats_ws is NULL (use ir_linear_fwd_scaled for a call without statistics)");
   return linear_fwd_impl(dtype, x_is_f32, m, n, k, x, x_ld, w, w_ld, bias, y, y_ld, scale_cols, col_scale, IR_LIN_AUTO, stats_col0, stats_cols,
+                         stats_ws, stats_ws_bytes, stream);
+}
+
+int ir_linear_fwd_stats_ex(int32_t dtype, int32_t x_is_f32, int64_t m, int32_t n, int32_t k, const void* x, int64_t x_ld, const void* w,
+                           int64_t w_ld, const void* bias, void* y, int64_t y_ld, int32_t scale_cols, float col_scale,
+                           int32_t stats_col0, int32_t stats_cols, float* stats_ws, size_t stats_ws_bytes, int32_t kernel, void* stream) {
+  if (stats_ws == nullptr) return fail(IR_ERR_INVALID_ARG, "stats_ws is NULL (use ir_linear_fwd_ex for a call without statistics)");
+  if (kernel != IR_LIN_AUTO && kernel != IR_LIN_BATCH_INVARIANT)
+    return fail(IR_ERR_INVALID_ARG, "ir_linear_fwd_stats_ex: kernel %d (IR_LIN_AUTO or IR_LIN_BATCH_INVARIANT)", kernel);
+  return linear_fwd_impl(dtype, x_is_f32, m, n, k, x, x_ld, w, w_ld, bias, y, y_ld, scale_cols, col_scale, kernel, stats_col0, stats_cols,
                          stats_ws, stats_ws_bytes, stream);
 }
 
@@ -557,6 +676,7 @@ static int linear_fwd_impl(int32_t dtype, int32_t x_is_f32, int64_t m, int32_t n
   if (!x || !w || !y) return fail(IR_ERR_INVALID_ARG, "NULL pointer");
   if (m <= 0 || n <= 0 || k <= 0) return fail(IR_ERR_INVALID_ARG, "sizes must be > 0");
   if (kernel == IR_LIN_AUTO) kernel = ir_linear_kernel_for(m, n, k, bias != nullptr);
+  else if (kernel == IR_LIN_BATCH_INVARIANT) kernel = linear_kernel_batch_invariant(n, k, bias != nullptr);
   if (kernel < 0) return fail(IR_ERR_UNSUPPORTED, "K = %d, N = %d: K must be a multiple of 64 and N of 64 (of 32 for K <= 320 or K = 640)", k, n);
   if (kernel == IR_LIN_X_STATIONARY) {
     if (!x_stationary_covers(n, k, bias))

@@ -58,7 +58,21 @@ struct AttnKParams {
   float* seg_cum;     // (B, H, Lq, nseg_out) fp32 or nullptr
   float* ws_cum;      // [piece][QB rows][nseg_out]
   int nseg_out;       // include_self + N
+  // sk_k on ENTRY to a kernel launcher: 0 = the launcher plans the remainder split itself (default dispatch); > 0 = a fixed plan
+  // (ABI v10 batch-invariant mode, ir_attn_bi_plan): every item in sk_k pieces (1: whole items), workspace sized by the caller
 };
+
+// ABI v10 (IR_FLAG_BATCH_INVARIANT): the kernel and the cut of every work item into K/V-range pieces, from per-item parameters only
+struct IrAttnBiPlan {
+  int kernel;          // IR_TUNE_W128 (16), IR_TUNE_W64X8 (13), IR_TUNE_PIPE32_PRESCALE_Q (11) or IR_TUNE_PIPE32_EARLYQK (14)
+  int rows;            // query rows per work item
+  int items;           // work items per batch entry
+  int pieces;          // K/V-range pieces per item (1: whole items)
+  size_t piece_bytes;  // fp32 partials of one piece (O, max, sum, and the cumulative segment values with seg_mass)
+};
+void ir_attn_bi_plan(const AttnKParams& p, IrAttnBiPlan* pl);
+size_t ir_attn_bi_workspace_bytes(const IrAttnBiPlan& pl, int batch);   // scratch of one launch over `batch` entries
+hipError_t ir_launch_shared_attn_fwd_bi(const AttnKParams& p, int dtype, const IrAttnBiPlan& pl, hipStream_t s);
 
 struct AdainKParams {
   const void* v_self;

@@ -490,6 +490,49 @@ hipError_t ir_launch_seg_mass_finish(const AttnKParams& p, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ABI v10 batch-invariant plan (IR_FLAG_BATCH_INVARIANT).  The default rules above read the batch size (items512, the remainder
+// split of the last round of workgroup slots) and process state (IR_ATTN_W128); this one reads per-item parameters only:
+//   kernel: the 128-row kernel (its FORMS instantiation, which carries valid_refs and seg_mass at run time) for pre-scaled Q, whole
+//           tiles and Lq >= 4096; the 8-wave 64-row kernel for other Lq >= 4096 calls; the pipelined 32-row kernel below that;
+//   pieces: every item of a call WITH references (n_refs > 0: the shared layers, whose batch is the identities) is cut into k
+//           K/V-range pieces (tile boundaries from the item's own tile count) merged by the combine kernel in piece order;
+//           k = ceil(256 / items of ONE batch entry) - one entry fills the 256 CUs of an MI355X (a constant, not the device's count) -
+//           within pieces of at least 8 tiles.  Plain attention (n_refs == 0: the K/V-capture layers, whose batch is identities x
+//           references, and the cross attention over 77 text tokens) runs whole items: a capture layer's batch already fills the chip,
+//           and cutting it would cost fp32 partials of its whole K/V walk (7 pieces of 1280 items at cfg 2's 64x64 class: 1.2 GB per
+//           launch) for no fill.  k = 1: whole items, no merge pass, no workspace.
+void ir_attn_bi_plan(const AttnKParams& p, IrAttnBiPlan* pl) {
+  const bool w128 = p.q_prescaled && p.Lq >= 4096 && ir_attn_w128_supports(p);
+  const bool w64 = !w128 && p.Lq >= 4096;
+  pl->kernel = w128 ? 16 : w64 ? 13 : (p.q_prescaled ? 11 : 14);
+  pl->rows = (w128 || w64) ? 512 : 128;
+  pl->items = p.H * ((p.Lq + pl->rows - 1) / pl->rows);
+  int k = (256 + pl->items - 1) / pl->items;
+  const int kmax = p.N > 0 ? p.ntiles / 8 : 1;
+  if (k > kmax) k = kmax;
+  pl->pieces = k > 1 ? k : 1;
+  pl->piece_bytes = (size_t)pl->rows * (66 + (p.seg_cum != nullptr ? p.nseg_out : 0)) * sizeof(float);
+}
+
+size_t ir_attn_bi_workspace_bytes(const IrAttnBiPlan& pl, int batch) {   // the launchers' layout: 8 XCD chunks of ceil(items / 8) items
+  if (pl.pieces <= 1) return 0;
+  const size_t ix = ((size_t)batch * pl.items + 7) / 8;
+  return 8 * ix * (size_t)pl.pieces * pl.piece_bytes;
+}
+
+// (the 128-row kernel: always its FORMS instantiation; the 64- and 32-row kernels: their MASS instantiations store the cumulative
+// values unconditionally, so they run only when seg_mass is given - the plain ones otherwise, same bytes: tests/test_gpu_seg_mass.py)
+hipError_t ir_launch_shared_attn_fwd_bi(const AttnKParams& p, int dtype, const IrAttnBiPlan& pl, hipStream_t s) {
+  AttnKParams q = p;
+  q.sk_k = pl.pieces;   // the launchers take the fixed plan (no remainder split of their own, no IR_ATTN_FORCE_SPLIT)
+  hipError_t e;
+  if (pl.kernel == 16) e = ir_launch_shared_attn_fwd_w128_forms(q, dtype, s);
+  else if (pl.kernel == 13) e = ir_launch_shared_attn_fwd_w64x8(q, dtype, s);
+  else e = ir_launch_shared_attn_fwd_pipe(q, dtype, pl.kernel, s);
+  if (e != hipSuccess || p.seg_cum == nullptr) return e;
+  return ir_launch_seg_mass_finish(p, s);
+}
+
 static hipError_t launch_attn_kernel(const AttnKParams& p, int dtype, int variant, hipStream_t s);
 
 hipError_t ir_launch_shared_attn_fwd(const AttnKParams& p, int dtype, int variant, hipStream_t s) {

@@ -793,7 +793,12 @@ hipError_t launch(const AttnKParams& p0, hipStream_t s) {
   int full = (p.sk_ix / slots_x) * slots_x;
   int rem = p.sk_ix - full;
   int k = 1;
-  if (p.ws != nullptr && rem > 0) {
+  const bool fixed = p0.sk_k > 0;   // a fixed plan (batch-invariant mode): every item in sk_k pieces
+  if (fixed) {
+    k = p0.sk_k;
+    full = k > 1 ? 0 : p.sk_ix;
+    rem = p.sk_ix - full;
+  } else if (p.ws != nullptr && rem > 0) {
     const size_t piece_bytes = (size_t)QB * (66 + (p.seg_cum != nullptr ? p.nseg_out : 0)) * sizeof(float);
     // pieces of at least 8 tiles.  (Round 3 tried 5-tile pieces for the 16x16-token class - 320 items of 20 tiles on 512
     // slots, cut in three - to put two workgroups on every CU: 47 us against 37 us unsplit, profiles/r3_layer_classes_cfg2_presc.txt:
@@ -806,7 +811,7 @@ hipError_t launch(const AttnKParams& p0, hipStream_t s) {
     // 32-row kernel's grid into k K/V-range pieces (more resident waves per CU to hide the per-tile latency chain), within the
     // workspace; read once, off by default.  profiles/r6_small_classes.txt has what it measures.
     static const int force_k = [] { const char* e = getenv("IR_ATTN_FORCE_SPLIT"); return e != nullptr ? atoi(e) : 0; }();
-    if (force_k > 1 && p.ws != nullptr && p.ntiles >= 2 * force_k) {
+    if (!fixed && force_k > 1 && p.ws != nullptr && p.ntiles >= 2 * force_k) {
       const size_t piece_bytes = (size_t)QB * (66 + (p.seg_cum != nullptr ? p.nseg_out : 0)) * sizeof(float);
       const long cap = (long)(p.ws_bytes / piece_bytes / 8);
       if ((long)p.sk_ix * force_k <= cap) { full = 0; rem = p.sk_ix; k = force_k; }

@@ -713,7 +713,11 @@ hipError_t launch(const AttnKParams& p0, hipStream_t s) {
   int full = (p.sk_ix / slots_x) * slots_x;
   int rem = p.sk_ix - full;
   int k = 1;
-  if (p.ws != nullptr && rem > 0) {
+  if (p0.sk_k > 0) {   // a fixed plan (batch-invariant mode): every item in sk_k pieces
+    k = p0.sk_k;
+    full = k > 1 ? 0 : p.sk_ix;
+    rem = p.sk_ix - full;
+  } else if (p.ws != nullptr && rem > 0) {
     const size_t piece_bytes = (size_t)QB * (66 + (p.seg_cum != nullptr ? p.nseg_out : 0)) * sizeof(float);
     k = ir_pick_split(rem, slots_x, p.ntiles / 8 /* pieces of at least 8 tiles */, (long)(p.ws_bytes / piece_bytes / 8));
   }

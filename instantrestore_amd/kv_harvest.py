@@ -37,7 +37,11 @@ def harvest_reference_kv(original_unet, n_refs: int, valid_indices: Sequence[int
 
     ``with_valid`` (round 5) appends ``valid``: the int32 ``(B,)`` device tensor of valid counts when some reference was
     zero-filled here, else ``None`` - hand it on as ``'ref_valid'`` and the shared layers close the zeroed segments in closed
-    form instead of walking them (ABI v8 ``valid_refs``; same output)."""
+    form instead of walking them (ABI v8 ``valid_refs``; same output).
+
+    Batch-invariant mode (ABI v10): the harvest follows its processors - what they stashed was computed under their own
+    ``batch_invariant`` attribute, and what runs here (the zero fill, ``token_stats``, the partials' merge) works per identity
+    and per reference in a fixed order whatever the batch, so it keeps the stashes' invariance without a switch of its own."""
     procs = [p for p in original_unet.attn_processors.values() if type(p) in [_ap.AttnProcessor]]
     if not procs:
         raise RuntimeError("no AttnProcessor on this UNet: call register_attention_processor_kv_unet first")

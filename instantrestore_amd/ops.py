@@ -108,14 +108,16 @@ def _ref(t: torch.Tensor, heads: int, name: str) -> torch.Tensor:
 
 
 def _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, lse, split=True,
-               q_prescaled=False, valid_refs=None):
+               q_prescaled=False, valid_refs=None, batch_invariant=False):
     a = _lib.SharedAttnArgs()
     a.struct_size = C.sizeof(_lib.SharedAttnArgs)
     a.dtype = _dtype_code(q)
     a.flags = (_lib.IR_FLAG_INCLUDE_SELF if include_self else 0) | (_lib.IR_FLAG_Q_PRESCALED if q_prescaled else 0)
     if out is not None and out.dtype == torch.float32:
         a.flags |= _lib.IR_FLAG_OUT_F32
-    a.tuning = _TUNING
+    if batch_invariant:   # ABI v10: the library's batch-invariant plan; the A/B tuning hook does not apply to it
+        a.flags |= _lib.IR_FLAG_BATCH_INVARIANT
+    a.tuning = 0 if batch_invariant else _TUNING
     a.batch, a.len_q, _ = q.shape
     a.heads = heads
     a.scale = float(scale)
@@ -142,11 +144,23 @@ def _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adai
         a.o_sb, a.o_sl, a.o_sh = out.stride(0), out.stride(1), HEAD_DIM
     if lse is not None:
         a.lse = lse.data_ptr()
-    if out is not None and split:  # scratch for the remainder split (ir_shared_attn_workspace_bytes)
+    if out is not None and split and not batch_invariant:  # scratch for the remainder split (ir_shared_attn_workspace_bytes)
         ws = _workspace(q.device)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
         a._keepalive = ws
     return a
+
+
+def _bi_workspace(a, device) -> None:
+    """batch-invariant mode: a per-call scratch of exactly what the plan's pieces need (``ir_shared_attn_workspace_bytes_for``;
+    none when every item runs whole), from torch's caching allocator on the current stream - so it follows that stream's
+    ordering and, under graph capture, lives in the graph's pool like any other intermediate; the shared per-thread buffer of
+    :func:`_workspace` (and its capture pinning) is not involved.  Set after ``seg_mass``: the masses size the pieces' partials."""
+    nbytes = int(_lib.lib().ir_shared_attn_workspace_bytes_for(C.byref(a)))
+    if nbytes > 0:
+        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+        a._keepalive = ws
 
 
 _WS = threading.local()
@@ -234,7 +248,7 @@ def shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, s
                      include_self: bool = True, adain: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                      return_lse: bool = False, split: bool = True, q_prescaled: bool = False,
                      out_dtype: Optional[torch.dtype] = None, valid_refs: Optional[torch.Tensor] = None,
-                     return_mass: bool = False):
+                     return_mass: bool = False, batch_invariant: bool = False):
     """Fused extended self-attention (``ir_shared_attn_fwd``).
 
     Returns ``out`` (B, Lq, H*64) in q's dtype [, ``lse`` (B, H, Lq) fp32] [, ``mass`` (B, H, Lq, include_self + N) fp32:
@@ -248,18 +262,25 @@ def shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, s
     ``ref_k`` and ``ref_v`` (``zero_invalid_refs``; pix2pix_turbo.py:269-273).  The kernels then close that suffix of the reference
     list analytically (every score exactly 0, every value row 0 or the AdaIN shift) instead of walking its tiles: same result,
     time proportional to the valid segments.  Zeroed, not masked: the tokens keep their exp(0) weight.
+    ``batch_invariant`` (ABI v10, ``IR_FLAG_BATCH_INVARIANT``): the bytes of entry ``b`` of every output depend on entry ``b``'s
+    inputs and the per-entry parameters only - not on the batch size or position, the other entries, the stream, capture,
+    ``return_lse`` / ``return_mass`` or the tuning hook (:func:`shared_attention_plan` shows the plan).  ``split`` is ignored
+    in this mode: the plan's K/V-range pieces are part of the result, and their scratch is allocated per call.
     """
     q, k_self, v_self, ref_k, ref_v = _prep(q, k_self, v_self, ref_k, ref_v, heads, include_self, adain)
     if out_dtype not in (None, q.dtype, torch.float32):
         raise TypeError("out_dtype must be the compute dtype or torch.float32")
     out = torch.empty((q.shape[0], q.shape[1], heads * HEAD_DIM), dtype=out_dtype or q.dtype, device=q.device)
     lse = torch.empty((q.shape[0], heads, q.shape[1]), dtype=torch.float32, device=q.device) if return_lse else None
-    args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, lse, split, q_prescaled, valid_refs)
+    args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, lse, split, q_prescaled, valid_refs,
+                      batch_invariant)
     mass = None
     if return_mass:
         nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
         mass = torch.empty((q.shape[0], heads, q.shape[1], nseg), dtype=torch.float32, device=q.device)
         args.seg_mass = mass.data_ptr()
+    if batch_invariant:
+        _bi_workspace(args, q.device)
     sink = EVENT_SINK
     if sink is not None and sink[0](q, ref_k, adain):   # bench.py: HIP events around chosen launches, in situ
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -276,16 +297,20 @@ def shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, s
 @_on_tensor_device
 def time_shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, scale: float,
                           include_self: bool = True, adain=None, iters: int = 10, split: bool = True,
-                          q_prescaled: bool = False, valid_refs: Optional[torch.Tensor] = None, return_mass: bool = False) -> float:
-    """Average ms per launch measured with HIP events on the launch stream (``bench.py``); ``valid_refs`` / ``return_mass`` as
-    in :func:`shared_attention` (the masses' finishing kernel is part of the timed launch)."""
+                          q_prescaled: bool = False, valid_refs: Optional[torch.Tensor] = None, return_mass: bool = False,
+                          batch_invariant: bool = False) -> float:
+    """Average ms per launch measured with HIP events on the launch stream (``bench.py``); ``valid_refs`` / ``return_mass`` /
+    ``batch_invariant`` as in :func:`shared_attention` (the masses' finishing kernel is part of the timed launch)."""
     q, k_self, v_self, ref_k, ref_v = _prep(q, k_self, v_self, ref_k, ref_v, heads, include_self, adain)
     out = torch.empty((q.shape[0], q.shape[1], heads * HEAD_DIM), dtype=q.dtype, device=q.device)
-    args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, None, split, q_prescaled, valid_refs)
+    args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, None, split, q_prescaled, valid_refs,
+                      batch_invariant)
     if return_mass:
         nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
         mass = torch.empty((q.shape[0], heads, q.shape[1], nseg), dtype=torch.float32, device=q.device)
         args.seg_mass = mass.data_ptr()
+    if batch_invariant:
+        _bi_workspace(args, q.device)
     ms = C.c_float(0.0)
     _lib.check(_lib.lib().ir_time_shared_attn_fwd(C.byref(args), int(iters), _stream(), C.byref(ms)),
                "ir_time_shared_attn_fwd")
@@ -310,12 +335,15 @@ def bench_mfma_stream(dtype: torch.dtype = torch.bfloat16, zero_operands: bool =
 
 def shared_attention_kernel_name(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, scale: float,
                                  include_self: bool = True, adain=None, q_prescaled: bool = False,
-                                 valid_refs: Optional[torch.Tensor] = None, return_mass: bool = False) -> str:
+                                 valid_refs: Optional[torch.Tensor] = None, return_mass: bool = False,
+                                 batch_invariant: bool = False) -> str:
     """which kernel the dispatcher launches for these tensors (reporting only; ``valid_refs`` / ``return_mass`` as in
-    :func:`shared_attention` - they decide the 128-row kernel's form and whether the default rule takes it)"""
+    :func:`shared_attention` - they decide the 128-row kernel's form and whether the default rule takes it;
+    ``batch_invariant``: the kernel and pieces of the batch-invariant plan)"""
     q, k_self, v_self, ref_k, ref_v = _prep(q, k_self, v_self, ref_k, ref_v, heads, include_self, adain)
     out = torch.empty((q.shape[0], q.shape[1], heads * HEAD_DIM), dtype=q.dtype, device=q.device)
-    args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, None, True, q_prescaled, valid_refs)
+    args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, None, True, q_prescaled, valid_refs,
+                      batch_invariant)
     if return_mass:   # never written: the name is all this call computes
         nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
         mass = torch.empty((q.shape[0], heads, q.shape[1], nseg), dtype=torch.float32, device=q.device)
@@ -323,27 +351,80 @@ def shared_attention_kernel_name(q, k_self, v_self, ref_k=None, ref_v=None, *, h
     return _lib.lib().ir_shared_attn_kernel_name(C.byref(args)).decode()
 
 
+def shared_attention_plan(batch: int, len_q: int, heads: int, *, len_self: int = 0, n_refs: int = 0, len_ref: int = 0,
+                          dtype: torch.dtype = torch.bfloat16, include_self: bool = True, adain: bool = False,
+                          q_prescaled: bool = False, valid_refs: bool = False, return_mass: bool = False,
+                          out_dtype: Optional[torch.dtype] = None, workspace_bytes: Optional[int] = None) -> dict:
+    """the batch-invariant plan of a :func:`shared_attention` call of these sizes (``ir_shared_attn_plan``; host only - no tensor,
+    no device): ``kernel`` (``IR_TUNE_*``), ``rows_per_item``, ``items_per_batch``, ``pieces_per_item``, ``workspace_bytes`` (the
+    scratch of one launch over the batch, what :func:`shared_attention` allocates per call) and ``batch_per_launch`` - the entries
+    one launch covers with a workspace of ``workspace_bytes`` bytes (default: the plan's own size)"""
+    a = _lib.SharedAttnArgs()
+    a.struct_size = C.sizeof(_lib.SharedAttnArgs)
+    a.dtype = _DT[dtype]
+    a.flags = _lib.IR_FLAG_BATCH_INVARIANT | (_lib.IR_FLAG_INCLUDE_SELF if include_self else 0) | \
+        (_lib.IR_FLAG_Q_PRESCALED if q_prescaled else 0) | (_lib.IR_FLAG_OUT_F32 if out_dtype == torch.float32 else 0)
+    a.batch, a.len_q, a.heads, a.scale = int(batch), int(len_q), int(heads), 0.125
+    a.len_self = int(len_self) if include_self else 0
+    a.n_refs, a.len_ref = int(n_refs), int(len_ref)
+    # the checks of a launch look at the pointer fields (set or NULL, alignment) and never read through them: one aligned dummy
+    c = HEAD_DIM * int(heads)
+    dummy = 256
+    a.q = a.out = dummy
+    a.q_sb, a.q_sl, a.q_sh = int(len_q) * c, c, HEAD_DIM
+    a.o_sb, a.o_sl, a.o_sh = int(len_q) * c, c, HEAD_DIM
+    if include_self:
+        a.k_self = a.v_self = dummy
+        a.ks_sb = a.vs_sb = int(len_self) * c
+        a.ks_sl = a.vs_sl = c
+        a.ks_sh = a.vs_sh = HEAD_DIM
+    if n_refs:
+        a.k_ref = a.v_ref = dummy
+        a.kr_sb = a.vr_sb = int(n_refs) * int(len_ref) * c
+        a.kr_sn = a.vr_sn = int(len_ref) * c
+        a.kr_sl = a.vr_sl = c
+        a.kr_sh = a.vr_sh = HEAD_DIM
+    if adain:
+        a.adain_a = a.adain_b = dummy
+    if valid_refs:
+        a.valid_refs = dummy
+    if return_mass:
+        a.seg_mass = dummy
+    L = _lib.lib()
+    if workspace_bytes is None:
+        workspace_bytes = int(L.ir_shared_attn_workspace_bytes_for(C.byref(a)))
+    if workspace_bytes > 0:
+        a.workspace, a.workspace_bytes = dummy, int(workspace_bytes)
+    plan = _lib.SharedAttnPlan()
+    plan.struct_size = C.sizeof(_lib.SharedAttnPlan)
+    _lib.check(L.ir_shared_attn_plan(C.byref(a), C.byref(plan)), "ir_shared_attn_plan")
+    return {n: int(getattr(plan, n)) for n, _ in _lib.SharedAttnPlan._fields_ if n != "struct_size"}
+
+
 PROBS_KERNELS = {"auto": 0, "generic": 1, "lines64": 2, "lines32": 3, "lines32k128": 4, "lines64k128": 5, "lines32k256": 6}   # IR_PROBS_*
 
 
-def _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled=False):
+def _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled=False, batch_invariant=False):
     q, k_self, _, ref_k, _ = _prep(q, k_self, k_self, ref_k, ref_k, heads, include_self, None)
     B, Lq, _ = q.shape
     lkv = (k_self.shape[1] if include_self else 0) + (ref_k.shape[1] * ref_k.shape[2] if ref_k is not None else 0)
     if lse.dtype != torch.float32 or not lse.is_contiguous() or tuple(lse.shape) != (B, heads, Lq):
         raise ValueError("lse must be contiguous fp32 (B, H, Lq)")
-    args = _fill_args(q, k_self, k_self, ref_k, ref_k, heads, scale, include_self, None, None, lse, True, q_prescaled)
+    args = _fill_args(q, k_self, k_self, ref_k, ref_k, heads, scale, include_self, None, None, lse, True, q_prescaled, None,
+                      batch_invariant)
     return args, q, B, Lq, lkv, (q, k_self, ref_k, lse)
 
 
 @_on_tensor_device
 def attn_probs(q, k_self, ref_k, lse, *, heads: int, scale: float, include_self: bool = True, kernel: str = "auto",
-               q_prescaled: bool = False) -> torch.Tensor:
+               q_prescaled: bool = False, batch_invariant: bool = False) -> torch.Tensor:
     """Materialise ``attention_probs`` (B, H, Lq, Lkv) from the LSE of the fused forward
     (``ir_attn_probs``; the ``save_self_attentions`` dump path, attn_processors.py:258-261).
     ``kernel``: ``PROBS_KERNELS`` (benchmarks / A-B tests; "auto" is what the processors use).  ``q_prescaled``: ``q`` holds
-    ``Q * scale * log2(e)`` (``IR_FLAG_Q_PRESCALED``; ``scale`` stays the reference's ``attn.scale``, the unit of ``lse``)."""
-    args, q, B, Lq, lkv, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled)
+    ``Q * scale * log2(e)`` (``IR_FLAG_Q_PRESCALED``; ``scale`` stays the reference's ``attn.scale``, the unit of ``lse``).
+    ``batch_invariant`` (ABI v10): the kernel follows the per-entry parameters only (with an invariant ``lse``, so is every
+    probability)."""
+    args, q, B, Lq, lkv, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant)
     probs = torch.empty((B, heads, Lq, lkv), dtype=q.dtype, device=q.device)
     _lib.check(_lib.lib().ir_attn_probs_ex(C.byref(args), probs.data_ptr(), PROBS_KERNELS[kernel], _stream()), "ir_attn_probs")
     return probs
@@ -351,10 +432,11 @@ def attn_probs(q, k_self, ref_k, lse, *, heads: int, scale: float, include_self:
 
 @_on_tensor_device
 def attn_segment_mass(q, k_self, ref_k, lse, *, heads: int, scale: float, include_self: bool = True,
-                      q_prescaled: bool = False) -> torch.Tensor:
+                      q_prescaled: bool = False, batch_invariant: bool = False) -> torch.Tensor:
     """Attention mass per K/V segment, fp32 (B, H, Lq, include_self + N), without the probability matrix
-    (``ir_attn_segment_mass``): what gradio_demo.py:119-127 reduces ``attention_probs`` to."""
-    args, q, B, Lq, _, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled)
+    (``ir_attn_segment_mass``): what gradio_demo.py:119-127 reduces ``attention_probs`` to.  ``batch_invariant`` as in
+    :func:`attn_probs`."""
+    args, q, B, Lq, _, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant)
     nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
     mass = torch.empty((B, heads, Lq, nseg), dtype=torch.float32, device=q.device)
     _lib.check(_lib.lib().ir_attn_segment_mass(C.byref(args), mass.data_ptr(), _stream()), "ir_attn_segment_mass")
@@ -514,8 +596,11 @@ def linear_supported(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
 _KERNEL_FOR = {}
 
 
-def linear_kernel_for(rows: int, n: int, k: int, bias: bool) -> int:
-    """IR_LIN_* id of the kernel the automatic choice launches for a shape (-1: unsupported)"""
+def linear_kernel_for(rows: int, n: int, k: int, bias: bool, batch_invariant: bool = False) -> int:
+    """IR_LIN_* id of the kernel the automatic choice launches for a shape (-1: unsupported); ``batch_invariant``: the one
+    kernel ``linear(..., batch_invariant=True)`` launches for (N, K, bias) at any number of rows"""
+    if batch_invariant:
+        return int(_lib.lib().ir_linear_kernel_for_ex(int(rows), int(n), int(k), 1 if bias else 0, _lib.IR_LIN_BATCH_INVARIANT))
     return int(_lib.lib().ir_linear_kernel_for(int(rows), int(n), int(k), 1 if bias else 0))
 
 
@@ -594,7 +679,7 @@ class RefStatsPartials:
 
 @_on_tensor_device
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, scale_cols: int = 0,
-           col_scale: float = 1.0, kernel: int = 0, stats: Optional[Tuple[int, int]] = None):
+           col_scale: float = 1.0, kernel: int = 0, stats: Optional[Tuple[int, int]] = None, batch_invariant: bool = False):
     """``F.linear(x, weight, bias)`` for ``x (..., K)``, 16-bit ``weight (N, K)`` (``ir_linear_fwd_ex``): fp32 accumulation,
     one rounding.  Raises for unsupported shapes.  ``scale_cols`` / ``col_scale``: the first ``scale_cols`` output columns
     are multiplied by ``col_scale`` in fp32 before that rounding.  ``x`` may be fp32: it is rounded to the weight's dtype
@@ -602,22 +687,37 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
 
     ``stats=(col0, cols)``: also return the partial token statistics of output columns ``[col0, col0 + cols)`` - whole
     heads - computed by the GEMM's own workgroups from the block they have just stored (``ir_linear_fwd_stats``; the AdaIN
-    statistics without a pass over V): the result is ``(y, ColumnStats)``.  Check :func:`linear_stats_rows` first."""
+    statistics without a pass over V): the result is ``(y, ColumnStats)``.  Check :func:`linear_stats_rows` first.
+
+    ``batch_invariant`` (ABI v10, ``IR_LIN_BATCH_INVARIANT``): one kernel per (N, K, bias) at every number of rows and no split
+    contraction - row ``r`` of ``y`` (and a 64-row statistics block) depends on row ``r`` of ``x``, ``weight`` and ``bias`` only.
+    Not combinable with ``kernel``."""
     _need_gpu(x, weight, bias)
     _forward_only(x, weight, bias)
+    if batch_invariant:
+        if kernel:
+            raise ValueError("batch_invariant: the kernel choice is the library's (kernel=0)")
+        kernel = _lib.IR_LIN_BATCH_INVARIANT
     n, k = weight.shape
     x2 = x.reshape(-1, k)
     if x2.stride(1) != 1 or x2.stride(0) % 8 != 0:
         x2 = x2.contiguous()
     y = torch.empty((x2.shape[0], n), dtype=weight.dtype, device=x.device)
     if stats is not None:
-        if kernel:
+        if kernel and not batch_invariant:
             raise ValueError("stats: the kernel choice is the library's (kernel=0)")
         col0, cols = int(stats[0]), int(stats[1])
         rows = linear_stats_rows(x2.shape[0], n, k, bias is not None)
         if rows <= 0 or cols <= 0 or cols % HEAD_DIM or col0 % HEAD_DIM:
             raise ValueError(f"linear(stats=...): shape ({x2.shape[0]}, {n}, {k}) / columns ({col0}, {cols}) cannot carry the statistics tail")
         ws = torch.empty((x2.shape[0] // rows, cols // HEAD_DIM, 128), dtype=torch.float32, device=x.device)
+        if batch_invariant:
+            rc = _lib.lib().ir_linear_fwd_stats_ex(_dtype_code(weight), 1 if x.dtype == torch.float32 else 0, x2.shape[0], n, k,
+                                                   x2.data_ptr(), x2.stride(0), weight.data_ptr(), weight.stride(0),
+                                                   None if bias is None else bias.data_ptr(), y.data_ptr(), n, int(scale_cols),
+                                                   float(col_scale), col0, cols, ws.data_ptr(), ws.numel() * 4, int(kernel), _stream())
+            _lib.check(rc, "ir_linear_fwd_stats_ex")
+            return y.view(*x.shape[:-1], n), ColumnStats(ws, rows, cols // HEAD_DIM)
         rc = _lib.lib().ir_linear_fwd_stats(_dtype_code(weight), 1 if x.dtype == torch.float32 else 0, x2.shape[0], n, k, x2.data_ptr(),
                                             x2.stride(0), weight.data_ptr(), weight.stride(0),
                                             None if bias is None else bias.data_ptr(), y.data_ptr(), n, int(scale_cols),
