@@ -49,6 +49,8 @@ def main(argv=None):
     ap.add_argument("--px", type=int, default=512)
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
     ap.add_argument("--small", action="store_true", help="narrow UNet topology (tests)")
+    ap.add_argument("--landmark-maps", action="store_true",
+                    help="one more frame that leaves the landmark attention map of every shared layer behind (attention_rows)")
     args = ap.parse_args(argv)
 
     import __graft_entry__ as ge
@@ -138,6 +140,33 @@ def main(argv=None):
             top.save_attention_mass = False
             assert float((z3.float() - z4.float()).abs().max()) <= 2e-2 * max(1.0, float(z4.float().abs().max()))
             assert mass.shape[-1] == N + int(top.train_input) and float((mass.sum(-1) - 1).abs().max()) < 2e-3
+        # Where do the facial landmarks look (vis_utils.py:88-110)?  Each shared layer is told which query tokens they fall on
+        # and leaves the sum of those tokens' head-mean probability rows behind - (B, Lkv) fp32, reshaped to one side x 5*side
+        # picture over the degraded image and its references - instead of the (B, H, L, Lkv) tensor of save_self_attentions.
+        if args.landmark_maps:
+            import numpy as np
+            from instantrestore_amd.attn_maps import landmark_picture, landmark_rows
+            landmarks = np.random.default_rng(0).uniform(0.2 * 512, 0.8 * 512, size=(68, 2))       # 68 seeded pseudo-landmarks, (x, y) at 512 px
+            shared = sorted((p for p in unet.attn_processors.values() if getattr(p, "self_attn_idx", None) is not None),
+                            key=lambda p: p.self_attn_idx)
+            side_of = {}
+            for p in shared:
+                tokens = keys[p.self_attn_idx].shape[2]
+                if tokens < len(landmarks):        # a toy resolution: ir_attn_rows takes at most len_q rows (the model's smallest shared layer has 256 tokens)
+                    continue
+                side_of[p.self_attn_idx] = int(round(tokens ** 0.5))
+                p.attention_rows_index = torch.from_numpy(landmark_rows(landmarks, side_of[p.self_attn_idx]))
+                p.attention_rows_reduce = "map"
+            unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1),
+                 cross_attention_kwargs={"ref_keys": ck, "ref_values": cv, "ref_stats": cs})
+            for p in shared:
+                if p.self_attn_idx not in side_of:
+                    continue
+                m, p.attention_rows_index = p.attention_rows, None
+                pic = landmark_picture(m[0], side_of[p.self_attn_idx])
+                print(f"shared layer {p.self_attn_idx}: landmark map {tuple(m.shape)} fp32, sum per identity {[round(float(t), 3) for t in m.sum(-1)]} "
+                      f"(68 rows of probabilities), picture {pic.shape}")
+                assert float((m.sum(-1) - 68).abs().max()) < 68 * 8e-3
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     assert out_u8.shape == (B, S, S, 3) and out_u8.dtype == torch.uint8

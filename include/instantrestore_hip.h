@@ -231,6 +231,35 @@ int ir_attn_probs_ex(const ir_shared_attn_args* args, void* probs, int32_t kerne
 int ir_attn_segment_mass(const ir_shared_attn_args* args, float* mass, void* stream);
 
 /*
+ * ir_attn_rows (opt-in) - the probability rows of a caller-chosen set of query tokens, without the probability matrix.
+ *
+ * Replaces `attention_probs[:, :, idx, :]` and what face_replace/training/utils/vis_utils.py:88-110
+ * (get_visualization_image; coach.py:308-317, 367-377) reduces it to: the head mean of attention_probs, the rows of the
+ * facial landmarks picked out of it (`img[landmark_indices]`) and their sum, reshaped to one heat map over the degraded
+ * image and its references.  calc_landmark_loss (coach.py:531-560) and calc_attn_probs (inference/test.py:93-110) read rows
+ * of the same tensor.  Same args as ir_attn_probs (q, the K pointers, lse; v_*, adain_*, out, valid_refs, seg_mass and workspace
+ * are ignored, `tuning` must be 0) plus
+ *   row_index  int32 (B, n_rows) contiguous on the device: token indices into the query axis, one list per batch entry.
+ *              Duplicates are legal and produce repeated rows (IR_ROWS_MAP counts them as often as they occur, like NumPy
+ *              fancy indexing); an index outside [0, len_q) yields an all-zero row and is never used as an address.  Read by
+ *              the kernel when it runs: a replayed hipGraph follows in-place updates of it.
+ *   n_rows     1 ... len_q
+ *   reduce     IR_ROWS_NONE       out = `dtype` (B, H, n_rows, Lkv): p[b,h,r,j] = exp(scale*<q[idx[b,r]], k_j> - lse[b,h,idx[b,r]]),
+ *                                 bit-identical to rows idx[b,:] of ir_attn_probs' output (IR_FLAG_Q_PRESCALED: same rule)
+ *              IR_ROWS_HEAD_MEAN  out = fp32 (B, n_rows, Lkv): (sum over heads, ascending, of the fp32 p) * (1/H)
+ *              IR_ROWS_MAP        out = fp32 (B, Lkv): the sum of the head-mean rows over r in a fixed order
+ *   out        contiguous, 16-byte aligned, column order [self (iff INCLUDE_SELF)] ++ ref 0 ++ ... ++ ref N-1
+ * Bound: K read once (B * H * Lkv * 128 bytes) + the output written; no workspace, no atomics, one launch; asynchronous and
+ * capturable.  The cut of the work follows len_self, len_ref, n_refs, n_rows and reduce only: the call is batch invariant with
+ * or without IR_FLAG_BATCH_INVARIANT.  Any segment length; rows are written 16 bytes at a time when every segment length is
+ * a multiple of 8 keys (IR_ROWS_NONE) or 4 keys (fp32 forms).
+ */
+#define IR_ROWS_NONE 0
+#define IR_ROWS_HEAD_MEAN 1
+#define IR_ROWS_MAP 2
+int ir_attn_rows(const ir_shared_attn_args* args, const int32_t* row_index, int32_t n_rows, int32_t reduce, void* out, void* stream);
+
+/*
  * ir_adain_stats - per-(b, n, channel) AdaIN affine from token statistics.
  *
  * Replaces the statistics half of adain() (attn_processors.py:9-10) and of its call site

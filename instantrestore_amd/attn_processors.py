@@ -460,6 +460,15 @@ class SharedAttnProcessor(nn.Module):
         # ABI v10 (plain attribute; set_batch_invariant): every GEMM and attention of this processor runs the library's batch-invariant
         # plans - an identity's output, attention_mass and attention_probs do not depend on the rest of its batch
         self.batch_invariant = False
+        # opt-in (plain attributes like ``save_attention_mass``): ``attention_rows_index`` - an integer tensor ``(R,)`` or ``(B, R)`` of
+        # query tokens, e.g. ``attn_maps.landmark_rows(...)`` - makes every call of a shared layer leave ``attention_rows``: the
+        # probability rows of those tokens (``ir_attn_rows``), reduced as ``attention_rows_reduce`` says - "none": ``attention_probs[:, :, idx]``
+        # (B, H, R, Lkv); "head_mean": fp32 (B, R, Lkv), ``attn.mean(dim=1)[b][idx]``; "map": fp32 (B, Lkv), their sum - what
+        # vis_utils.py:88-110 reads out of ``attention_probs``, without the (B, H, L, Lkv) tensor.  Independent of
+        # ``save_self_attentions`` (with both set, the one LSE of the attention call serves both).  ``None``: off, nothing changes.
+        self.attention_rows_index = None
+        self.attention_rows_reduce = "head_mean"
+        self.attention_rows = None
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                 ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None):
@@ -527,6 +536,8 @@ class SharedAttnProcessor(nn.Module):
 
         want_probs = bool(self.save_self_attentions)
         want_mass = bool(getattr(self, "save_attention_mass", False))
+        rows_index = getattr(self, "attention_rows_index", None) if shared else None
+        want_lse = want_probs or rows_index is not None
         kw = {"q_prescaled": True} if presc else {}
         kw.update(_bi_kw(bi))
         if shared and ref_valid is not None:
@@ -534,19 +545,25 @@ class SharedAttnProcessor(nn.Module):
         # the masses are a by-product of the attention launch itself (ABI v9 ``seg_mass``: the kernels hold the row sums at every
         # segment boundary): no second pass over Q and K
         res = _ops.shared_attention(query, key, value, ref_k, ref_v, heads=attn.heads, scale=attn.scale,
-                                    include_self=include_self, adain=affine, return_lse=want_probs, return_mass=want_mass, **kw)
+                                    include_self=include_self, adain=affine, return_lse=want_lse, return_mass=want_mass, **kw)
         if want_mass:
             self.attention_mass = res[-1]
-            res = res[:-1] if want_probs else res[0]
-        if want_probs:
+            res = res[:-1] if want_lse else res[0]
+        if want_lse:
             tokens, lse = res
+        else:
+            tokens = res
+        if rows_index is not None:
+            # the rows of the chosen tokens from the same LSE (pre-scaled query: as for the dump below)
+            self.attention_rows = _ops.attn_rows(query, key, ref_k, lse, rows_index, heads=attn.heads,
+                                                 scale=0.6931471805599453 if presc else attn.scale, include_self=include_self,
+                                                 reduce=getattr(self, "attention_rows_reduce", "head_mean"), **_bi_kw(bi))
+        if want_probs:
             # (B, H, L, Lkv), columns [self?] ++ ref0 ++ ... ++ refN-1, in the compute dtype.  A pre-scaled query
             # already carries scale * log2(e): its scores are exponents, ln 2 turns them into the logits of the LSE
             self.attention_probs = _ops.attn_probs(query, key, ref_k, lse, heads=attn.heads,
                                                    scale=0.6931471805599453 if presc else attn.scale,
                                                    include_self=include_self, **_bi_kw(bi))
-        else:
-            tokens = res
         return _epilogue(attn, st, tokens, bi)
 
 

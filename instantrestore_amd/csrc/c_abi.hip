@@ -334,6 +334,27 @@ int ir_attn_segment_mass(const ir_shared_attn_args* args, float* mass, void* str
   return IR_OK;
 }
 
+int ir_attn_rows(const ir_shared_attn_args* args, const int32_t* row_index, int32_t n_rows, int32_t reduce, void* out, void* stream) {
+  if (args == nullptr) return fail(IR_ERR_INVALID_ARG, "args is NULL");
+  if (args->struct_size == sizeof(ir_shared_attn_args) && args->tuning != IR_TUNE_DEFAULT)
+    return fail(IR_ERR_UNSUPPORTED, "ir_attn_rows has one kernel: tuning must be 0 (got %d)", args->tuning);
+  AttnKParams p;
+  const int rc = build_attn_params(args, &p, false);
+  if (rc != IR_OK) return rc;
+  if (row_index == nullptr) return fail(IR_ERR_INVALID_ARG, "row_index is NULL");
+  if (out == nullptr) return fail(IR_ERR_INVALID_ARG, "out is NULL");
+  if (args->lse == nullptr) return fail(IR_ERR_INVALID_ARG, "lse is NULL");
+  if (n_rows < 1 || n_rows > args->len_q) return fail(IR_ERR_INVALID_ARG, "n_rows %d outside [1, len_q = %d]", n_rows, args->len_q);
+  if (reduce != IR_ROWS_NONE && reduce != IR_ROWS_HEAD_MEAN && reduce != IR_ROWS_MAP)
+    return fail(IR_ERR_UNSUPPORTED, "reduce %d: IR_ROWS_NONE (0), IR_ROWS_HEAD_MEAN (1) or IR_ROWS_MAP (2)", reduce);
+  if ((reinterpret_cast<uintptr_t>(row_index) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "row_index must be 4-byte aligned");
+  if (!aligned16(out)) return fail(IR_ERR_UNSUPPORTED, "out must be 16-byte aligned");
+  if (p.q_prescaled) p.scale_log2 = 1.0f;   // as in ir_attn_probs: the products of a pre-scaled q and k ARE the exponents
+  const hipError_t e = ir_launch_attn_rows(p, args->dtype, row_index, n_rows, reduce, out, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "attn_rows launch: %s", hipGetErrorString(e));
+  return IR_OK;
+}
+
 static int adain_nchunk(int32_t len_self, int32_t len_ref) {
   const int a = (len_self + IR_ADAIN_ROWS - 1) / IR_ADAIN_ROWS;
   const int b = (len_ref + IR_ADAIN_ROWS - 1) / IR_ADAIN_ROWS;

@@ -150,6 +150,10 @@ static inline int ir_pick_split(int rem, int slots, int kmax, long cap_pieces) {
 hipError_t ir_launch_attn_probs(const AttnKParams& p, int dtype, int variant, hipStream_t s);
 bool ir_attn_probs_uses_lines(const AttnKParams& p);
 hipError_t ir_launch_attn_segment_mass(const AttnKParams& p, int dtype, float* mass, hipStream_t s);
+// attn_rows.hip: the probability rows of `n_rows` chosen query tokens per batch entry (row_index: int32 (B, n_rows) on the device),
+// as they are or reduced over heads / over heads and rows; `reduce` is IR_ROWS_* of the public header
+constexpr int kRowsNone = 0, kRowsHeadMean = 1, kRowsMap = 2;
+hipError_t ir_launch_attn_rows(const AttnKParams& p, int dtype, const int32_t* row_index, int n_rows, int reduce, void* out, hipStream_t s);
 hipError_t ir_launch_adain_stats(const AdainKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_token_stats(const AdainKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_adain_stats_cached(const AdainKParams& p, int dtype, hipStream_t s);

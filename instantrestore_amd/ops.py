@@ -443,6 +443,54 @@ def attn_segment_mass(q, k_self, ref_k, lse, *, heads: int, scale: float, includ
     return mass
 
 
+ROWS_REDUCE = {"none": _lib.IR_ROWS_NONE, "head_mean": _lib.IR_ROWS_HEAD_MEAN, "map": _lib.IR_ROWS_MAP}
+
+
+def _row_index(rows, batch: int, len_q: int, device: torch.device) -> torch.Tensor:
+    """``rows`` as the contiguous int32 ``(B, R)`` device tensor ``ir_attn_rows`` reads.  A CPU tensor is range-checked here; a
+    device tensor is converted without a sync (the kernel turns an index outside ``[0, len_q)`` into an all-zero row)."""
+    rows = torch.as_tensor(rows)
+    if rows.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) or rows.dim() not in (1, 2):
+        raise ValueError(f"rows must be an integer tensor (R,) or (B, R), got {rows.dtype} {tuple(rows.shape)}")
+    if rows.dim() == 2 and rows.shape[0] != batch:
+        raise ValueError(f"rows: {rows.shape[0]} index lists for a batch of {batch}")
+    if rows.shape[-1] < 1 or rows.shape[-1] > len_q:
+        raise ValueError(f"rows: {rows.shape[-1]} indices per entry, expected 1 ... len_q = {len_q}")
+    if not rows.is_cuda and (int(rows.min()) < 0 or int(rows.max()) >= len_q):
+        raise ValueError(f"rows: indices must lie in [0, {len_q})")
+    rows = rows.to(device=device, dtype=torch.int32, non_blocking=True)
+    if rows.dim() == 1:
+        rows = rows.unsqueeze(0).expand(batch, -1)
+    return rows.contiguous()
+
+
+@_on_tensor_device
+def attn_rows(q, k_self, ref_k, lse, rows, *, heads: int, scale: float, include_self: bool = True, reduce: str = "none",
+              q_prescaled: bool = False, batch_invariant: bool = False) -> torch.Tensor:
+    """The probability rows of the query tokens ``rows`` from the LSE of the fused forward, without the ``(B, H, Lq, Lkv)``
+    tensor (``ir_attn_rows``): what vis_utils.py:88-110 (``get_visualization_image``) reads out of ``attention_probs``.
+
+    ``rows``: integer tensor ``(R,)`` (one list for the whole batch) or ``(B, R)``, on the CPU or the device; duplicates give
+    repeated rows.  ``reduce``: ``"none"`` - ``attention_probs[:, :, rows]``, ``(B, H, R, Lkv)`` in q's dtype, bit for bit the rows
+    of :func:`attn_probs`; ``"head_mean"`` - fp32 ``(B, R, Lkv)``, ``attn.mean(dim=1)[b][rows]``; ``"map"`` - fp32 ``(B, Lkv)``,
+    the sum of those rows (the landmark heat map before its reshape, :func:`instantrestore_amd.attn_maps.landmark_picture`).
+    ``q_prescaled`` as in :func:`attn_probs`.  Batch invariant by construction; ``batch_invariant`` is accepted and changes nothing."""
+    if reduce not in ROWS_REDUCE:
+        raise ValueError(f"reduce must be one of {sorted(ROWS_REDUCE)}, got {reduce!r}")
+    args, q, B, Lq, lkv, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant)
+    args.tuning = 0   # one kernel: the A/B hook of the forward does not apply
+    idx = _row_index(rows, B, Lq, q.device)
+    R = idx.shape[1]
+    if reduce == "none":
+        out = torch.empty((B, heads, R, lkv), dtype=q.dtype, device=q.device)
+    elif reduce == "head_mean":
+        out = torch.empty((B, R, lkv), dtype=torch.float32, device=q.device)
+    else:
+        out = torch.empty((B, lkv), dtype=torch.float32, device=q.device)
+    _lib.check(_lib.lib().ir_attn_rows(C.byref(args), idx.data_ptr(), R, ROWS_REDUCE[reduce], out.data_ptr(), _stream()), "ir_attn_rows")
+    return out
+
+
 @_on_tensor_device
 def adain_stats(v_self: torch.Tensor, ref_v: torch.Tensor, *, heads: int, eps: float = ADAIN_EPS):
     """AdaIN as a per-(b, n, head, channel) affine ``x*a + b`` (``ir_adain_stats``).
