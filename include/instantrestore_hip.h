@@ -137,7 +137,8 @@ typedef struct ir_shared_attn_args {
                                masses are mass[..., INCLUDE_SELF:].  NULL = off. */
 } ir_shared_attn_args;
 
-/* values of ir_shared_attn_args.tuning (csrc/shared_attn_fwd.hip lists what each one is) */
+/* values of ir_shared_attn_args.tuning (csrc/shared_attn_fwd.hip: kAttnVariants has one row per value - kernel family, form, what
+ * it takes; ir_attn_choose is the dispatch) */
 #define IR_TUNE_DEFAULT 0
 #define IR_TUNE_PIPE32_EXACTMAX 7
 #define IR_TUNE_PIPE32 10
@@ -165,7 +166,8 @@ typedef struct ir_shared_attn_args {
 size_t ir_shared_attn_workspace_bytes(void);
 
 /* Name of the kernel ir_shared_attn_fwd would launch for these arguments (incl. their `tuning` field)
- * (reporting only: bench.py's roofline block); "" if the arguments are invalid. Static storage. */
+ * (reporting only: bench.py's roofline block); "" if the arguments are invalid. Storage: one buffer per thread, overwritten by
+ * the thread's next call. */
 const char* ir_shared_attn_kernel_name(const ir_shared_attn_args* args);
 
 int ir_shared_attn_fwd(const ir_shared_attn_args* args, void* stream);

@@ -72,8 +72,7 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
   p->include_self = inc ? 1 : 0;
   p->q_prescaled = (a->flags & IR_FLAG_Q_PRESCALED) ? 1 : 0;
   p->out_f32 = (a->flags & IR_FLAG_OUT_F32) ? 1 : 0;
-  if (p->q_prescaled && a->tuning != IR_TUNE_DEFAULT && a->tuning != IR_TUNE_W64X8 && a->tuning != IR_TUNE_W128 && a->tuning != IR_TUNE_PIPE32_PRESCALE_Q &&
-      a->tuning != IR_TUNE_PIPE32_POSTCHECK && !(a->tuning >= IR_TUNE_W64_ABL_FIRST && a->tuning < IR_TUNE_W64_ABL_FIRST + 16))
+  if (p->q_prescaled && ((a->tuning >> 5) != 0 || !ir_attn_variant(a->tuning)->presc_q))   // (the availability test above found the row)
     return fail(IR_ERR_UNSUPPORTED, "IR_FLAG_Q_PRESCALED is implemented by the W128, W64X8, PIPE32_PRESCALE_Q and PIPE32_POSTCHECK kernels only");
   if (a->tuning == IR_TUNE_W128 && !p->q_prescaled)
     return fail(IR_ERR_UNSUPPORTED, "IR_TUNE_W128 needs IR_FLAG_Q_PRESCALED");
@@ -110,7 +109,7 @@ IrAttnBiPlan bi_plan_of(const ir_shared_attn_args* a, const AttnKParams& p0) {
 // batch entries per launch that the caller's workspace holds (0: not even one)
 int bi_batch_per_launch(const IrAttnBiPlan& pl, int batch, size_t ws_bytes) {
   if (pl.pieces <= 1 || ir_attn_bi_workspace_bytes(pl, batch) <= ws_bytes) return batch;
-  const size_t chunk_items = 8 * (ws_bytes / (8 * (size_t)pl.pieces * pl.piece_bytes));   // whole XCD chunks of items
+  const size_t chunk_items = kIrXcds * (ws_bytes / ir_attn_partials_bytes(kIrXcds, pl.pieces, pl.piece_bytes));   // whole XCD chunks of items
   const size_t nb = chunk_items / (size_t)pl.items;
   return nb < (size_t)batch ? (int)nb : batch;
 }
@@ -162,61 +161,64 @@ const char* ir_build_info(void) { return "instantrestore_hip gfx950 (CDNA4) hipc
 
 const char* ir_last_error_string(void) { return g_err; }
 
-// 8 XCDs x 64 slots pieces of up to 256 rows, 64 fp32 of O + (max, sum) per row
+// The kernel a call launches, in words: ir_attn_choose's (or the batch-invariant plan's) choice, formatted with the call's fold /
+// valid_refs / seg_mass / pre-scaled flags.  No dispatch rule lives here.
 const char* ir_shared_attn_kernel_name(const ir_shared_attn_args* args) {
   AttnKParams p;
   if (build_attn_params(args, &p, false) != IR_OK) return "";
   // the launch takes seg_mass only with an output (need_out); for reporting the by-product counts wherever it is asked for - it
   // decides the 128-row kernel's form and whether the default rule takes that kernel.  Never dereferenced here
   p.seg_cum = (float*)args->seg_mass;
-  const int v = args->tuning & 31;
-  const bool fold = p.aa != nullptr;
-  if (batch_invariant(args)) {   // the plan's kernel family and cut; the name does not change with seg_mass (the output does not either)
-    static thread_local char name[256];
+  const bool bi = batch_invariant(args), fold = p.aa != nullptr;
+  const IrAttnChoice c = bi ? ir_attn_choose_bi(p) : ir_attn_choose(p, args->tuning);
+  const char* head = nullptr;        // the name up to the fold
+  const char* fold_text = ", AdaIN fold";
+  bool forms = false;                // the 128-row kernel's default-mode names say which of its forms run
+  switch (c.family) {
+    case IR_FAM_REFUSED: return "";
+    case IR_FAM_W128: case IR_FAM_W128_FORMS:
+      head = "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q";
+      fold_text = ", AdaIN ratio-frame fold";
+      forms = !bi;
+      break;
+    case IR_FAM_W64X8:   // (the batch-invariant name does not say how Q arrives)
+      head = p.q_prescaled && !bi ? "shared_attn_fwd_w64_kernel<64 rows/wave, 8 waves, pre-scaled Q (reference through the MFMA C operand, checked after the exponentials)"
+                                  : "shared_attn_fwd_w64_kernel<64 rows/wave, 8 waves";
+      fold_text = ", AdaIN ratio-frame fold";
+      break;
+    case IR_FAM_W64X4:
+      head = "shared_attn_fwd_w64_kernel<64 rows/wave, 4 waves";
+      fold_text = ", AdaIN ratio-frame fold";
+      break;
+    case IR_FAM_PIPE32:
+      switch (c.form) {
+        case IR_PIPE_EXACT: head = "shared_attn_fwd_pipe_kernel<4 waves, exact rescale"; fold_text = ""; break;
+        case IR_PIPE_LAZY: head = "shared_attn_fwd_pipe_kernel<4 waves, lazy max"; fold_text = ""; break;
+        case IR_PIPE_PRESC:
+          if (p.q_prescaled) head = "shared_attn_fwd_pipe_kernel<4 waves, lazy max, pre-scaled Q";
+          else { head = "shared_attn_fwd_pipe_kernel<4 waves, lazy max, pre-scaled Q (Q rounded in the kernel)"; fold_text = ""; }
+          break;
+        case IR_PIPE_EARLYQK: head = "shared_attn_fwd_pipe_kernel<4 waves, lazy max, early QK"; break;
+        case IR_PIPE_POSTCHECK: head = "shared_attn_fwd_pipe_kernel<4 waves, pre-scaled Q, reference checked after the exponentials"; break;
+        default: break;
+      }
+      break;
+    default: break;
+  }
+  if (head == nullptr) return "shared_attn_fwd (tuning variant)";
+  static thread_local char name[256];
+  int n = snprintf(name, sizeof(name), "%s%s%s%s%s>", head, fold ? fold_text : "", forms && p.valid != nullptr ? ", zero suffix in closed form" : "",
+                   forms && p.seg_cum != nullptr ? ", segment masses" : "", bi && c.family == IR_FAM_W128_FORMS ? ", forms" : "");
+  if (bi) {   // the plan's cut; the name does not change with seg_mass (the output does not either)
     const IrAttnBiPlan pl = bi_plan_of(args, p);
-    const char* base = pl.kernel == 16 ? (fold ? "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, AdaIN ratio-frame fold, forms>"
-                                               : "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, forms>")
-                     : pl.kernel == 13 ? (fold ? "shared_attn_fwd_w64_kernel<64 rows/wave, 8 waves, AdaIN ratio-frame fold>" : "shared_attn_fwd_w64_kernel<64 rows/wave, 8 waves>")
-                     : pl.kernel == 11 ? (fold ? "shared_attn_fwd_pipe_kernel<4 waves, lazy max, pre-scaled Q, AdaIN fold>" : "shared_attn_fwd_pipe_kernel<4 waves, lazy max, pre-scaled Q>")
-                                       : (fold ? "shared_attn_fwd_pipe_kernel<4 waves, lazy max, early QK, AdaIN fold>" : "shared_attn_fwd_pipe_kernel<4 waves, lazy max, early QK>");
-    snprintf(name, sizeof(name), "%s [batch-invariant: %d piece%s per %d-row item]", base, pl.pieces, pl.pieces > 1 ? "s" : "", pl.rows);
-    return name;
+    snprintf(name + n, sizeof(name) - n, " [batch-invariant: %d piece%s per %d-row item]", pl.pieces, pl.pieces > 1 ? "s" : "", pl.rows);
   }
-  const bool w64 = (v == 0 && ir_attn_default_is_w64(p)) || v == 13;
-  if ((v == 16 || (v == 0 && ir_attn_default_is_w128(p))) && ir_attn_w128_supports(p)) {
-    static const char* const names[8] = {
-        "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q>",
-        "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, AdaIN ratio-frame fold>",
-        "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, zero suffix in closed form>",
-        "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, AdaIN ratio-frame fold, zero suffix in closed form>",
-        "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, segment masses>",
-        "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, AdaIN ratio-frame fold, segment masses>",
-        "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, zero suffix in closed form, segment masses>",
-        "shared_attn_fwd_w128_kernel<128 rows/wave, one wave per SIMD, hand-placed stream, pre-scaled Q, AdaIN ratio-frame fold, zero suffix in closed form, segment masses>"};
-    return names[(fold ? 1 : 0) | (p.valid != nullptr ? 2 : 0) | (p.seg_cum != nullptr ? 4 : 0)];
-  }
-  if (p.q_prescaled) {   // the dispatch of ir_launch_shared_attn_fwd, restated for reporting
-    if (w64) return fold ? "shared_attn_fwd_w64_kernel<64 rows/wave, 8 waves, pre-scaled Q (reference through the MFMA C operand, checked after the exponentials), AdaIN ratio-frame fold>"
-                         : "shared_attn_fwd_w64_kernel<64 rows/wave, 8 waves, pre-scaled Q (reference through the MFMA C operand, checked after the exponentials)>";
-    if (v == 11 || v == 0) return fold ? "shared_attn_fwd_pipe_kernel<4 waves, lazy max, pre-scaled Q, AdaIN fold>" : "shared_attn_fwd_pipe_kernel<4 waves, lazy max, pre-scaled Q>";
-    if (v == 18) return fold ? "shared_attn_fwd_pipe_kernel<4 waves, pre-scaled Q, reference checked after the exponentials, AdaIN fold>"
-                                       : "shared_attn_fwd_pipe_kernel<4 waves, pre-scaled Q, reference checked after the exponentials>";
-  }
-  switch (v) {
-    case 0: return ir_attn_default_is_w64(p) ? (fold ? "shared_attn_fwd_w64_kernel<64 rows/wave, 8 waves, AdaIN ratio-frame fold>" : "shared_attn_fwd_w64_kernel<64 rows/wave, 8 waves>")
-                                             : (fold ? "shared_attn_fwd_pipe_kernel<4 waves, lazy max, early QK, AdaIN fold>" : "shared_attn_fwd_pipe_kernel<4 waves, lazy max, early QK>");
-    case 12: return fold ? "shared_attn_fwd_w64_kernel<64 rows/wave, 4 waves, AdaIN ratio-frame fold>" : "shared_attn_fwd_w64_kernel<64 rows/wave, 4 waves>";
-    case 13: return fold ? "shared_attn_fwd_w64_kernel<64 rows/wave, 8 waves, AdaIN ratio-frame fold>" : "shared_attn_fwd_w64_kernel<64 rows/wave, 8 waves>";
-    case 11: return "shared_attn_fwd_pipe_kernel<4 waves, lazy max, pre-scaled Q (Q rounded in the kernel)>";
-    case 14: return fold ? "shared_attn_fwd_pipe_kernel<4 waves, lazy max, early QK, AdaIN fold>" : "shared_attn_fwd_pipe_kernel<4 waves, lazy max, early QK>";
-    case 10: return "shared_attn_fwd_pipe_kernel<4 waves, lazy max>";
-    case 7: return "shared_attn_fwd_pipe_kernel<4 waves, exact rescale>";
-    default: return "shared_attn_fwd (tuning variant)";
-  }
+  return name;
 }
 
-// 8 XCDs x 64 pieces x 512 rows x (64 + 2) floats: the largest remainder split of any kernel (512-row items)
-size_t ir_shared_attn_workspace_bytes(void) { return (size_t)8 * 64 * 512 * 66 * sizeof(float); }
+size_t ir_shared_attn_workspace_bytes(void) {   // the largest remainder split of any kernel
+  return (size_t)kIrXcds * kIrWsPiecesPerXcd * ir_attn_piece_bytes(kIrMaxItemRows, 0);
+}
 
 size_t ir_shared_attn_workspace_bytes_for(const ir_shared_attn_args* args) {
   AttnKParams p;

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ir_attn_plan.h"
+
 #define IR_KV_TILE 64          // keys per K/V tile
 #define IR_ADAIN_ROWS 256      // token rows per AdaIN partial-statistics workgroup
 
@@ -62,6 +64,46 @@ struct AttnKParams {
   // (ABI v10 batch-invariant mode, ir_attn_bi_plan): every item in sk_k pieces (1: whole items), workspace sized by the caller
 };
 
+// what a kernel launcher gives ir_attn_plan (ir_attn_plan.h): the call, its own rows per item and slots rule
+static inline IrAttnPlanIn ir_attn_plan_in(const AttnKParams& p, int rows, int slots, int force_k = 0) {
+  return {p.B, p.H, p.Lq, p.ntiles, rows, slots, p.ws != nullptr, p.ws_bytes, p.seg_cum != nullptr ? p.nseg_out : 0, p.sk_k, force_k};
+}
+
+// ---- the dispatch of the attention forward (shared_attn_fwd.hip: kAttnVariants, ir_attn_choose) ----
+enum IrAttnFamily {
+  IR_FAM_REFUSED = 0,   // the launch returns hipErrorInvalidValue
+  IR_FAM_W128,          // 128 rows per wave, one wave per SIMD (shared_attn_fwd_w128.hip) ...
+  IR_FAM_W128_FORMS,    // ... its valid_refs / seg_mass instantiation
+  IR_FAM_W64X8,         // 64 rows per wave, 8-wave (512-row) workgroups (shared_attn_fwd_w64.hip) ...
+  IR_FAM_W64X4,         // ... 4 waves
+  IR_FAM_PIPE32,        // software-pipelined 32-row kernel (shared_attn_fwd_pipe.hip), in one of its forms
+  IR_FAM_DEV            // -DIR_ABLATIONS builds: the straight-line kernel, the 64-row kernel's ablations, the `>> 5` ablation bits
+};
+enum IrPipeForm {   // template forms of the 32-row kernel (shared_attn_fwd_pipe.hip's launch_t has the template arguments)
+  IR_PIPE_NONE = 0,
+  IR_PIPE_EXACT,        // asm-issued LDS-DMA staging, exact (every-change) rescale
+  IR_PIPE_LAZY,         // + lazy max
+  IR_PIPE_PRESC,        // + pre-scaled Q, reference through the MFMA C operand
+  IR_PIPE_EARLYQK,      // LAZY with the next tile's QK^T issued before the row max
+  IR_PIPE_POSTCHECK,    // PRESC with the reference checked after the exponentials (no row max on ordinary tiles; K ring of 3)
+  IR_PIPE_DEV_REG4, IR_PIPE_DEV_REG8, IR_PIPE_DEV_DMA, IR_PIPE_DEV_STRAIGHT3   // development builds: register staging with 4 / 8 waves,
+};                                                                             // builtin LDS-DMA, straight schedule at 3 waves/SIMD
+struct IrAttnVariant {   // one tuning value (IR_TUNE_*)
+  int id;
+  IrAttnFamily family;   // (IR_TUNE_DEFAULT: what the default rules fall back to)
+  IrPipeForm form;
+  bool presc_q;          // takes IR_FLAG_Q_PRESCALED
+  bool seg_mass;         // carries the seg_mass by-product
+  bool product;          // false: -DIR_ABLATIONS builds only
+};
+struct IrAttnChoice {
+  IrAttnFamily family;
+  IrPipeForm form;       // IR_FAM_PIPE32 only
+};
+const IrAttnVariant* ir_attn_variant(int tuning);                      // nullptr: not available in this build
+IrAttnChoice ir_attn_choose(const AttnKParams& p, int tuning);         // what ir_launch_shared_attn_fwd runs
+IrAttnChoice ir_attn_choose_bi(const AttnKParams& p);                  // what the batch-invariant plan runs
+
 // ABI v10 (IR_FLAG_BATCH_INVARIANT): the kernel and the cut of every work item into K/V-range pieces, from per-item parameters only
 struct IrAttnBiPlan {
   int kernel;          // IR_TUNE_W128 (16), IR_TUNE_W64X8 (13), IR_TUNE_PIPE32_PRESCALE_Q (11) or IR_TUNE_PIPE32_EARLYQK (14)
@@ -112,7 +154,7 @@ struct ZeroRefsKParams {
 
 // launchers (defined next to their kernels); dtype: 0 = f16, 1 = bf16. Return hipError_t.
 hipError_t ir_launch_shared_attn_fwd(const AttnKParams& p, int dtype, int variant, hipStream_t s);
-hipError_t ir_launch_shared_attn_fwd_pipe(const AttnKParams& p, int dtype, int nw, hipStream_t s);
+hipError_t ir_launch_shared_attn_fwd_pipe(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s);
 hipError_t ir_launch_shared_attn_fwd_pipe_abl(const AttnKParams& p, int abl, hipStream_t s);
 hipError_t ir_launch_shared_attn_combine(const AttnKParams& p, int dtype, int qb, int rem, hipStream_t s);
 hipError_t ir_launch_shared_attn_fwd_w64(const AttnKParams& p, int dtype, hipStream_t s);
@@ -131,20 +173,6 @@ hipError_t ir_launch_seg_mass_finish(const AttnKParams& p, hipStream_t s);   // 
 bool ir_attn_default_is_w64(const AttnKParams& p);
 bool ir_attn_variant_available(int variant);
 
-// Remainder split: `rem` items of the last, partially filled round (per XCD) on `slots` concurrently
-// resident workgroups.  Cutting each into k K/V-range pieces makes the round last ceil(rem*k/slots)/k of an
-// item; pick the k that minimises it (plus a small per-piece charge for the fp32 partials and the combine),
-// within the piece-length floor `kmax` and the workspace capacity `cap_pieces` (pieces per XCD).
-static inline int ir_pick_split(int rem, int slots, int kmax, long cap_pieces) {
-  int best_k = 1;
-  double best = 1.0;   // k = 1: one round of whole items
-  for (int k = 2; k <= kmax && (long)rem * k <= cap_pieces; ++k) {
-    const int rounds = (rem * k + slots - 1) / slots;
-    const double t = (double)rounds / k + 0.012 * k;
-    if (t < best - 1e-9) { best = t; best_k = k; }
-  }
-  return best_k;
-}   // the default dispatch rule (variant 0)
 // variant: 0 = automatic (line kernel when every segment length is a multiple of 8), 1 = round 1's 2-byte-store kernel,
 // 2 / 3 = the line kernel with 64 / 32 query rows per wave
 hipError_t ir_launch_attn_probs(const AttnKParams& p, int dtype, int variant, hipStream_t s);

@@ -34,6 +34,7 @@
 //   * softmax in fp32 in the exp2 domain; accumulators are rescaled only when a running max
 //     actually moved (exact), otherwise the multiply pass is skipped;
 //   * blockIdx is remapped so the query blocks that share one (b,h)'s K/V sit on one XCD's L2.
+#include "../../include/instantrestore_hip.h"
 #include "ir_common.h"
 #include "ir_kernels.h"
 
@@ -413,14 +414,7 @@ hipError_t launch_t(const AttnKParams& p, int nw, hipStream_t s) {
 #endif  // IR_ABLATIONS
 
 // variant & 31 selects the kernel (per-call tuning field of ir_shared_attn_args; 0 = default dispatch, see
-// ir_attn_default_is_w64).  Product library:
-//   16 128 query rows per wave, ONE wave per SIMD, hand-placed instruction stream (shared_attn_fwd_w128.hip; pre-scaled Q only)
-//   13 64 query rows per wave, 8-wave (512-row) workgroups (shared_attn_fwd_w64.hip)     12 the same, 4 waves
-//   10 software-pipelined 32-row kernel, 4 waves, asm-issued LDS-DMA staging, lazy max (shared_attn_fwd_pipe.hip)
-//    7 the same with an exact (every-change) rescale
-//   11 10 + pre-scaled Q, reference through the MFMA C operand (opt-in fast mode: one more rounding of Q)
-//   14 10 with the next tile's QK^T issued before the row max
-//   18 11 with the reference checked after the exponentials (no row max on ordinary tiles; K ring of 3)
+// ir_attn_default_is_w64).  One row per tuning value: everything that asks "which values ..." reads this table.
 // Development builds only (tools/experiments/build.sh, -DIR_ABLATIONS; documented experiments, NOTES.md): 1/2 this file's
 // straight-line kernel with 8 / 4 waves, 3/4 pipelined with register staging, 6 pipelined + builtin LDS-DMA, 9 straight
 // schedule at 3 waves/SIMD; 20-28 the energy / timing ablations of the 64-row QS kernel (shared_attn_fwd_w64.hip, WRONG
@@ -429,15 +423,43 @@ hipError_t launch_t(const AttnKParams& p, int nw, hipStream_t s) {
 // 15 the 64-row kernel with rotated phases, 16 one wave per SIMD, 17 a three-stage 32-row pipeline: measured negative
 // results - NOTES.md 4.1b, 4.1b', profiles/r1_pp_phase_trace.txt, r2_sp_ablation.txt - whose sources were second copies of
 // product kernel bodies and left the tree in round 5.)
-bool ir_attn_variant_available(int variant) {
-  const int base = variant & 31;
+static const IrAttnVariant kAttnVariants[] = {
+    // id                         family          32-row form           presc. Q  seg_mass  product
+    {IR_TUNE_DEFAULT,             IR_FAM_PIPE32,  IR_PIPE_EARLYQK,      true,     true,     true},   // the rules of ir_attn_choose; this row where none takes a larger kernel
+    {IR_TUNE_PIPE32_EXACTMAX,     IR_FAM_PIPE32,  IR_PIPE_EXACT,        false,    false,    true},
+    {IR_TUNE_PIPE32,              IR_FAM_PIPE32,  IR_PIPE_LAZY,         false,    false,    true},
+    {IR_TUNE_PIPE32_PRESCALE_Q,   IR_FAM_PIPE32,  IR_PIPE_PRESC,        true,     true,     true},   // opt-in fast mode without the flag: one more rounding of Q
+    {IR_TUNE_W64X4,               IR_FAM_W64X4,   IR_PIPE_NONE,         false,    false,    true},
+    {IR_TUNE_W64X8,               IR_FAM_W64X8,   IR_PIPE_NONE,         true,     true,     true},
+    {IR_TUNE_PIPE32_EARLYQK,      IR_FAM_PIPE32,  IR_PIPE_EARLYQK,      false,    true,     true},
+    {IR_TUNE_W128,                IR_FAM_W128,    IR_PIPE_NONE,         true,     true,     true},   // pre-scaled Q only
+    {IR_TUNE_PIPE32_POSTCHECK,    IR_FAM_PIPE32,  IR_PIPE_POSTCHECK,    true,     false,    true},
 #ifdef IR_ABLATIONS
-  return (base <= 18 && base != 8 && base != 15 && base != 17) || (base >= 20 && base < 20 + ir_w64_abl_count());
-#else
-  if ((variant >> 5) != 0) return false;
-  return base == 0 || base == 7 || (base >= 10 && base <= 14) || base == 16 || base == 18;   // (17, TP32: retired, like 1-6, 8, 9, 15 development builds)
+    {1,                           IR_FAM_DEV,     IR_PIPE_NONE,         false,    false,    false},
+    {2,                           IR_FAM_DEV,     IR_PIPE_NONE,         false,    false,    false},
+    {3,                           IR_FAM_PIPE32,  IR_PIPE_DEV_REG4,     false,    false,    false},
+    {4,                           IR_FAM_PIPE32,  IR_PIPE_DEV_REG8,     false,    false,    false},
+    {6,                           IR_FAM_PIPE32,  IR_PIPE_DEV_DMA,      false,    false,    false},
+    {9,                           IR_FAM_PIPE32,  IR_PIPE_DEV_STRAIGHT3, false,   false,    false},
 #endif
+};
+#ifdef IR_ABLATIONS
+static const IrAttnVariant kW64AblVariant = {IR_TUNE_W64_ABL_FIRST, IR_FAM_DEV, IR_PIPE_NONE, true, false, false};   // IR_TUNE_W64_ABL_FIRST + index
+#endif
+
+const IrAttnVariant* ir_attn_variant(int tuning) {
+  const int base = tuning & 31;
+#ifdef IR_ABLATIONS
+  if (base >= IR_TUNE_W64_ABL_FIRST) return base < IR_TUNE_W64_ABL_FIRST + ir_w64_abl_count() ? &kW64AblVariant : nullptr;
+#else
+  if ((tuning >> 5) != 0) return nullptr;   // the ablation bits: development builds
+#endif
+  for (const IrAttnVariant& v : kAttnVariants)
+    if (v.id == base) return &v;
+  return nullptr;
 }
+
+bool ir_attn_variant_available(int variant) { return ir_attn_variant(variant) != nullptr; }
 
 // Default dispatch: the 64-rows-per-wave kernel in 512-row workgroups for query axes of >= 4096 rows whose (b, h, 512-row)
 // items fill the chip or whose K/V walk is long; the 32-row pipelined kernel below that
@@ -501,62 +523,84 @@ hipError_t ir_launch_seg_mass_finish(const AttnKParams& p, hipStream_t s) {
 //           references, and the cross attention over 77 text tokens) runs whole items: a capture layer's batch already fills the chip,
 //           and cutting it would cost fp32 partials of its whole K/V walk (7 pieces of 1280 items at cfg 2's 64x64 class: 1.2 GB per
 //           launch) for no fill.  k = 1: whole items, no merge pass, no workspace.
+IrAttnChoice ir_attn_choose_bi(const AttnKParams& p) {
+  if (p.Lq >= 4096) return {p.q_prescaled && ir_attn_w128_supports(p) ? IR_FAM_W128_FORMS : IR_FAM_W64X8, IR_PIPE_NONE};
+  return {IR_FAM_PIPE32, p.q_prescaled ? IR_PIPE_PRESC : IR_PIPE_EARLYQK};
+}
+
 void ir_attn_bi_plan(const AttnKParams& p, IrAttnBiPlan* pl) {
-  const bool w128 = p.q_prescaled && p.Lq >= 4096 && ir_attn_w128_supports(p);
-  const bool w64 = !w128 && p.Lq >= 4096;
-  pl->kernel = w128 ? 16 : w64 ? 13 : (p.q_prescaled ? 11 : 14);
-  pl->rows = (w128 || w64) ? 512 : 128;
+  const IrAttnChoice c = ir_attn_choose_bi(p);
+  pl->kernel = c.family == IR_FAM_W128_FORMS ? IR_TUNE_W128 : c.family == IR_FAM_W64X8 ? IR_TUNE_W64X8
+               : c.form == IR_PIPE_PRESC ? IR_TUNE_PIPE32_PRESCALE_Q : IR_TUNE_PIPE32_EARLYQK;
+  pl->rows = c.family == IR_FAM_PIPE32 ? 128 : 512;
   pl->items = p.H * ((p.Lq + pl->rows - 1) / pl->rows);
-  int k = (256 + pl->items - 1) / pl->items;
-  const int kmax = p.N > 0 ? p.ntiles / 8 : 1;
+  int k = (kIrBiCus + pl->items - 1) / pl->items;
+  const int kmax = p.N > 0 ? p.ntiles / kIrPieceMinTiles : 1;
   if (k > kmax) k = kmax;
   pl->pieces = k > 1 ? k : 1;
-  pl->piece_bytes = (size_t)pl->rows * (66 + (p.seg_cum != nullptr ? p.nseg_out : 0)) * sizeof(float);
+  pl->piece_bytes = ir_attn_piece_bytes(pl->rows, p.seg_cum != nullptr ? p.nseg_out : 0);
 }
 
-size_t ir_attn_bi_workspace_bytes(const IrAttnBiPlan& pl, int batch) {   // the launchers' layout: 8 XCD chunks of ceil(items / 8) items
-  if (pl.pieces <= 1) return 0;
-  const size_t ix = ((size_t)batch * pl.items + 7) / 8;
-  return 8 * ix * (size_t)pl.pieces * pl.piece_bytes;
+size_t ir_attn_bi_workspace_bytes(const IrAttnBiPlan& pl, int batch) {
+  return pl.pieces <= 1 ? 0 : ir_attn_partials_bytes((size_t)batch * pl.items, pl.pieces, pl.piece_bytes);
 }
 
-// (the 128-row kernel: always its FORMS instantiation; the 64- and 32-row kernels: their MASS instantiations store the cumulative
-// values unconditionally, so they run only when seg_mass is given - the plain ones otherwise, same bytes: tests/test_gpu_seg_mass.py)
+// The one dispatch decision of a default-mode call: the table row of the tuning value, the default rules for IR_TUNE_DEFAULT, and
+// where a family does not take the call.  ir_launch_shared_attn_fwd runs it; ir_shared_attn_kernel_name (c_abi.hip) prints it.
+IrAttnChoice ir_attn_choose(const AttnKParams& p, int tuning) {
+  const IrAttnVariant* v = ir_attn_variant(tuning);
+  if (v == nullptr) return {IR_FAM_REFUSED, IR_PIPE_NONE};
+#ifdef IR_ABLATIONS
+  const bool abl = (tuning >> 5) != 0;
+  // the experiments that never learned IR_FLAG_OUT_F32 would write 16-bit data into an fp32 buffer
+  if (p.out_f32 && (abl || v->family == IR_FAM_DEV)) return {IR_FAM_REFUSED, IR_PIPE_NONE};
+  if (abl || v->id == IR_TUNE_W64_ABL_FIRST) return {IR_FAM_DEV, IR_PIPE_NONE};
+#endif
+  IrAttnChoice c = {v->family, v->form};
+  if (v->id == IR_TUNE_DEFAULT) {
+    if (p.q_prescaled && ir_attn_default_is_w128(p)) c = {IR_FAM_W128, IR_PIPE_NONE};
+    else if (ir_attn_default_is_w64(p)) c = {IR_FAM_W64X8, IR_PIPE_NONE};
+  }
+  if (c.family == IR_FAM_W128) {   // what it does not cover it refuses; valid_refs / seg_mass: its FORMS instantiation
+    if (!ir_attn_w128_supports(p)) return {IR_FAM_REFUSED, IR_PIPE_NONE};
+    if (p.valid != nullptr || p.seg_cum != nullptr) c.family = IR_FAM_W128_FORMS;
+    return c;
+  }
+  // pre-scaled Q: the 64-row kernel's QS instantiation where the default rule (or IR_TUNE_W64X8) takes that kernel, the
+  // 32-row kernel's reference-through-C form (no Q rounding of its own, the row max of every tile) for every other shape.  Its
+  // check-after-the-exponentials form (IR_TUNE_PIPE32_POSTCHECK, round 3) is parity-green and measures the SAME time
+  // on both short layer classes (profiles/r3_layer_classes_cfg2_presc.txt: this kernel is bound by its LDS fragment
+  // reads, not by vector instructions), at 8 KiB more LDS - so it stays opt-in
+  if (p.q_prescaled && c.family != IR_FAM_W64X8) return {IR_FAM_PIPE32, c.form == IR_PIPE_POSTCHECK ? IR_PIPE_POSTCHECK : IR_PIPE_PRESC};
+  return c;
+}
+
+// (the 64- and 32-row kernels' MASS instantiations store the cumulative values unconditionally, so their launchers take them only
+// when seg_mass is given - the plain ones otherwise, same bytes: tests/test_gpu_seg_mass.py.)  fp32 output (IR_FLAG_OUT_F32): every
+// product kernel stores its result before the rounding when asked - what the parity tests look at is the kernel that ships
+static hipError_t launch_choice(const AttnKParams& p, int dtype, IrAttnChoice c, hipStream_t s) {
+  switch (c.family) {
+    case IR_FAM_W128: return ir_launch_shared_attn_fwd_w128(p, dtype, s);
+    case IR_FAM_W128_FORMS: return ir_launch_shared_attn_fwd_w128_forms(p, dtype, s);
+    case IR_FAM_W64X8: return ir_launch_shared_attn_fwd_w64x8(p, dtype, s);
+    case IR_FAM_W64X4: return ir_launch_shared_attn_fwd_w64(p, dtype, s);
+    case IR_FAM_PIPE32: return ir_launch_shared_attn_fwd_pipe(p, dtype, c.form, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
 hipError_t ir_launch_shared_attn_fwd_bi(const AttnKParams& p, int dtype, const IrAttnBiPlan& pl, hipStream_t s) {
   AttnKParams q = p;
   q.sk_k = pl.pieces;   // the launchers take the fixed plan (no remainder split of their own, no IR_ATTN_FORCE_SPLIT)
-  hipError_t e;
-  if (pl.kernel == 16) e = ir_launch_shared_attn_fwd_w128_forms(q, dtype, s);
-  else if (pl.kernel == 13) e = ir_launch_shared_attn_fwd_w64x8(q, dtype, s);
-  else e = ir_launch_shared_attn_fwd_pipe(q, dtype, pl.kernel, s);
+  const hipError_t e = launch_choice(q, dtype, ir_attn_choose_bi(p), s);
   if (e != hipSuccess || p.seg_cum == nullptr) return e;
   return ir_launch_seg_mass_finish(p, s);
 }
 
-static hipError_t launch_attn_kernel(const AttnKParams& p, int dtype, int variant, hipStream_t s);
-
-hipError_t ir_launch_shared_attn_fwd(const AttnKParams& p, int dtype, int variant, hipStream_t s) {
-  if (!ir_attn_variant_available(variant)) return hipErrorInvalidValue;
-  if (p.seg_cum != nullptr) {
-    // by-product of the 64-row and the pipelined 32-row kernels (every product kernel); the development-only experiments never learned it
-    // (the 8-wave 64-row kernel and the 32-row kernel's two default forms carry the MASS instantiation, the 128-row kernel its
-    // FORMS instantiation: tuning 0, 11, 13, 14, 16)
-    const int b0 = variant & 31;
-    if ((variant >> 5) != 0 || !(b0 == 0 || b0 == 11 || b0 == 13 || b0 == 14 || b0 == 16)) return hipErrorInvalidValue;
-  }
-  const hipError_t e = launch_attn_kernel(p, dtype, variant, s);
-  if (e != hipSuccess || p.seg_cum == nullptr) return e;
-  return ir_launch_seg_mass_finish(p, s);
-}
-
-static hipError_t launch_attn_kernel(const AttnKParams& p, int dtype, int variant, hipStream_t s) {
 #ifdef IR_ABLATIONS
-  {   // the experiments that never learned IR_FLAG_OUT_F32 would write 16-bit data into an fp32 buffer
-    const int b0 = variant & 31;
-    if (p.out_f32 && (b0 == 1 || b0 == 2 || b0 >= 20 || (variant >> 5) != 0)) return hipErrorInvalidValue;
-  }
-  const int abl = variant >> 5;
-  if (abl != 0 && (variant & 31) == 3) return ir_launch_shared_attn_fwd_pipe_abl(p, abl, s);
+static hipError_t launch_dev(const AttnKParams& p, int dtype, int variant, hipStream_t s) {
+  const int abl = variant >> 5, base = variant & 31;
+  if (abl != 0 && base == 3) return ir_launch_shared_attn_fwd_pipe_abl(p, abl, s);
   if (abl != 0) {
     switch (abl & 7) {
       case 1: return launch<__bf16, 4, false, 1>(p, s);
@@ -568,40 +612,23 @@ static hipError_t launch_attn_kernel(const AttnKParams& p, int dtype, int varian
       default: return launch<__bf16, 4, false, 7>(p, s);
     }
   }
+  if (base >= IR_TUNE_W64_ABL_FIRST) return ir_launch_shared_attn_fwd_w64_abl(p, dtype, base - IR_TUNE_W64_ABL_FIRST, s);
+  const int nw = (base == 1) ? 8 : 4;
+  return dtype == 1 ? launch_t<__bf16>(p, nw, s) : launch_t<_Float16>(p, nw, s);
+}
 #endif
-  const int base = variant & 31;
-  // pre-scaled Q: the 64-row kernel's QS instantiation where the default rule (or IR_TUNE_W64X8) takes that kernel, the
-  // 32-row kernel's reference-through-C form for every other shape.  fp32 output (IR_FLAG_OUT_F32): every product kernel
-  // stores its result before the rounding when asked - what the parity tests look at is the kernel that ships
+
+hipError_t ir_launch_shared_attn_fwd(const AttnKParams& p, int dtype, int variant, hipStream_t s) {
+  const IrAttnVariant* v = ir_attn_variant(variant);
+  if (v == nullptr) return hipErrorInvalidValue;
+  // seg_mass: a by-product of every product kernel's default forms; the other forms and the development experiments never learned it
+  if (p.seg_cum != nullptr && ((variant >> 5) != 0 || !v->seg_mass)) return hipErrorInvalidValue;
+  const IrAttnChoice c = ir_attn_choose(p, variant);
 #ifdef IR_ABLATIONS
-  if (base >= 20) return ir_launch_shared_attn_fwd_w64_abl(p, dtype, base - 20, s);
+  const hipError_t e = c.family == IR_FAM_DEV ? launch_dev(p, dtype, variant, s) : launch_choice(p, dtype, c, s);
+#else
+  const hipError_t e = launch_choice(p, dtype, c, s);
 #endif
-  if (base == 16) return ir_launch_shared_attn_fwd_w128(p, dtype, s);   // (refuses what it does not cover)
-  if (p.q_prescaled) {
-    if (base == 0 && ir_attn_default_is_w128(p)) return ir_launch_shared_attn_fwd_w128(p, dtype, s);
-    if ((base == 0 && ir_attn_default_is_w64(p)) || base == 13) return ir_launch_shared_attn_fwd_w64x8(p, dtype, s);
-    // the 32-row kernel's pre-scaled-Q form (no Q rounding of its own), with the row max of every tile.  Its
-    // check-after-the-exponentials form (IR_TUNE_PIPE32_POSTCHECK, round 3) is parity-green and measures the SAME time
-    // on both short layer classes (profiles/r3_layer_classes_cfg2_presc.txt: this kernel is bound by its LDS fragment
-    // reads, not by vector instructions), at 8 KiB more LDS - so it stays opt-in
-    return ir_launch_shared_attn_fwd_pipe(p, dtype, base == 18 ? 18 : 11, s);
-  }
-  switch (base) {
-    case 0:
-      if (ir_attn_default_is_w64(p)) return ir_launch_shared_attn_fwd_w64x8(p, dtype, s);
-      return ir_launch_shared_attn_fwd_pipe(p, dtype, 14, s);
-    case 7: case 10: case 11: case 14: case 18: return ir_launch_shared_attn_fwd_pipe(p, dtype, base, s);
-    case 12: return ir_launch_shared_attn_fwd_w64(p, dtype, s);
-    case 13: return ir_launch_shared_attn_fwd_w64x8(p, dtype, s);
-#ifdef IR_ABLATIONS
-    case 3: return ir_launch_shared_attn_fwd_pipe(p, dtype, 4, s);   // register staging, 4 waves
-    case 4: return ir_launch_shared_attn_fwd_pipe(p, dtype, 8, s);   // register staging, 8 waves
-    case 6: case 9: return ir_launch_shared_attn_fwd_pipe(p, dtype, base, s);
-    case 1: case 2: {
-      const int nw = (base == 1) ? 8 : 4;
-      return dtype == 1 ? launch_t<__bf16>(p, nw, s) : launch_t<_Float16>(p, nw, s);
-    }
-#endif
-    default: return hipErrorInvalidValue;
-  }
+  if (e != hipSuccess || p.seg_cum == nullptr) return e;
+  return ir_launch_seg_mass_finish(p, s);
 }

@@ -778,78 +778,66 @@ __global__ void __launch_bounds__(256) shared_attn_combine_kernel(const AttnKPar
   }
 }
 
-// Work plan: items = B*H*ceil(Lq/QB); every XCD owns ix = ceil(items/8) consecutive items and
-// has `slots_x` concurrently resident workgroups (CUs/8 * workgroups per CU).  Whole rounds run
-// full K/V ranges; the remainder items are cut into k pieces so the last round ends early.
+// measurement knob (round 6, VERDICT r5 item 5: "the split-K/V form on purpose"): IR_ATTN_FORCE_SPLIT=k cuts EVERY item of the
+// 32-row kernel's grid into k K/V-range pieces (more resident waves per CU to hide the per-tile latency chain), within the
+// workspace; read once, off by default.  profiles/r6_small_classes.txt has what it measures.
+int force_split() {
+  static const int force_k = [] { const char* e = getenv("IR_ATTN_FORCE_SPLIT"); return e != nullptr ? atoi(e) : 0; }();
+  return force_k;
+}
+
+// (the work plan: ir_attn_plan.h)
 template <typename T, int NW, bool FOLD, int ABL = 0, bool MASS = false>
 hipError_t launch(const AttnKParams& p0, hipStream_t s) {
   if (!MASS && p0.seg_cum != nullptr) return hipErrorInvalidValue;   // seg_mass: the two default forms carry the MASS instantiation
-  AttnKParams p = p0;
   constexpr int QB = NW * 32;
-  p.nqb = (p.Lq + QB - 1) / QB;
-  p.sk_items = p.B * p.H * p.nqb;
-  p.sk_ix = (p.sk_items + 7) / 8;
-  const int slots_x = 32 * (NW == 8 ? 1 : (((ABL & 256) && !FOLD) ? 3 : 2));
-  int full = (p.sk_ix / slots_x) * slots_x;
-  int rem = p.sk_ix - full;
-  int k = 1;
-  const bool fixed = p0.sk_k > 0;   // a fixed plan (batch-invariant mode): every item in sk_k pieces
-  if (fixed) {
-    k = p0.sk_k;
-    full = k > 1 ? 0 : p.sk_ix;
-    rem = p.sk_ix - full;
-  } else if (p.ws != nullptr && rem > 0) {
-    const size_t piece_bytes = (size_t)QB * (66 + (p.seg_cum != nullptr ? p.nseg_out : 0)) * sizeof(float);
-    // pieces of at least 8 tiles.  (Round 3 tried 5-tile pieces for the 16x16-token class - 320 items of 20 tiles on 512
-    // slots, cut in three - to put two workgroups on every CU: 47 us against 37 us unsplit, profiles/r3_layer_classes_cfg2_presc.txt:
-    // the prologue, the fp32 partials and the combine launch cost more than the idle slots.)
-    k = ir_pick_split(rem, slots_x, p.ntiles / 8, (long)(p.ws_bytes / piece_bytes / 8));
-  }
-  if (k <= 1) { full = p.sk_ix; rem = 0; k = 1; }
-  {
-    // measurement knob (round 6, VERDICT r5 item 5: "the split-K/V form on purpose"): IR_ATTN_FORCE_SPLIT=k cuts EVERY item of the
-    // 32-row kernel's grid into k K/V-range pieces (more resident waves per CU to hide the per-tile latency chain), within the
-    // workspace; read once, off by default.  profiles/r6_small_classes.txt has what it measures.
-    static const int force_k = [] { const char* e = getenv("IR_ATTN_FORCE_SPLIT"); return e != nullptr ? atoi(e) : 0; }();
-    if (!fixed && force_k > 1 && p.ws != nullptr && p.ntiles >= 2 * force_k) {
-      const size_t piece_bytes = (size_t)QB * (66 + (p.seg_cum != nullptr ? p.nseg_out : 0)) * sizeof(float);
-      const long cap = (long)(p.ws_bytes / piece_bytes / 8);
-      if ((long)p.sk_ix * force_k <= cap) { full = 0; rem = p.sk_ix; k = force_k; }
-    }
-  }
-  p.sk_full = full;
-  p.sk_k = k;
-  p.ws_o = p.ws;
-  p.ws_ml = p.ws + (size_t)8 * rem * k * QB * 64;
-  p.ws_cum = p.ws_ml + (size_t)8 * rem * k * QB * 2;
-  const int grid = 8 * (full + rem * k);
-  hipLaunchKernelGGL((shared_attn_fwd_pipe_kernel<T, NW, FOLD, ABL, MASS>), dim3(grid), dim3(NW * 64), 0, s, p);
+  const int slots_x = 32 * (NW == 8 ? 1 : (((ABL & 256) && !FOLD) ? 3 : 2));   // CUs per XCD x workgroups per CU
+  const IrAttnPlan pl = ir_attn_plan(ir_attn_plan_in(p0, QB, slots_x, force_split()));
+  AttnKParams p = p0;
+  ir_attn_plan_apply(pl, p);
+  hipLaunchKernelGGL((shared_attn_fwd_pipe_kernel<T, NW, FOLD, ABL, MASS>), dim3(pl.grid), dim3(NW * 64), 0, s, p);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess || k <= 1) return e;
-  hipLaunchKernelGGL((shared_attn_combine_kernel<T, QB>), dim3(8 * rem, QB / 16), dim3(256), 0, s, p);
-  return hipGetLastError();
+  if (e != hipSuccess || pl.k <= 1) return e;
+  return ir_launch_shared_attn_combine(p, std::is_same<T, __bf16>::value ? 1 : 0, QB, pl.rem, s);
+}
+
+// template arguments (ABL bits) of the forms, IrPipeForm of ir_kernels.h
+constexpr int kAsmDma = 128, kLazyMax = 1024, kPrescQ = 2048, kEarlyQK = 4096, kPostCheck = 8192;
+#ifdef IR_ABLATIONS
+constexpr int kDma = 64, kStraight3 = 256;   // builtin LDS-DMA staging; straight schedule at 3 waves/SIMD (0: register staging)
+#endif
+constexpr int kFormExact = kAsmDma;                                   // LDS-DMA from asm
+constexpr int kFormLazy = kAsmDma | kLazyMax;                         // asm DMA + lazy max
+constexpr int kFormPresc = kFormLazy | kPrescQ;                       // + pre-scaled Q, reference through the C operand
+constexpr int kFormEarlyQK = kFormLazy | kEarlyQK;                    // + QK^T of the next tile first
+constexpr int kFormPostCheck = kFormPresc | kPostCheck;               // PRESC + reference checked after the exponentials
+
+template <typename T, int ABL, bool MASS = false, int NW = 4>
+hipError_t launch_f(const AttnKParams& p, hipStream_t s) {
+  return p.aa != nullptr ? launch<T, NW, true, ABL, MASS>(p, s) : launch<T, NW, false, ABL, MASS>(p, s);
 }
 
 template <typename T>
-hipError_t launch_t(const AttnKParams& p, int nw, hipStream_t s) {
-  const bool fold = (p.aa != nullptr);
+hipError_t launch_t(const AttnKParams& p, IrPipeForm form, hipStream_t s) {
   if (p.seg_cum != nullptr) {   // ABI v9 seg_mass: the two forms the default dispatch takes
-    if (nw == 11) return fold ? launch<T, 4, true, 128 | 1024 | 2048, true>(p, s) : launch<T, 4, false, 128 | 1024 | 2048, true>(p, s);
-    if (nw == 14) return fold ? launch<T, 4, true, 128 | 1024 | 4096, true>(p, s) : launch<T, 4, false, 128 | 1024 | 4096, true>(p, s);
+    if (form == IR_PIPE_PRESC) return launch_f<T, kFormPresc, true>(p, s);
+    if (form == IR_PIPE_EARLYQK) return launch_f<T, kFormEarlyQK, true>(p, s);
     return hipErrorInvalidValue;
   }
+  switch (form) {
 #ifdef IR_ABLATIONS
-  if (nw == 8) return fold ? launch<T, 8, true>(p, s) : launch<T, 8, false>(p, s);
-  if (nw == 6) return fold ? launch<T, 4, true, 64>(p, s) : launch<T, 4, false, 64>(p, s);  // LDS-DMA staging
-  if (nw == 9) return fold ? launch<T, 4, true, 256>(p, s) : launch<T, 4, false, 256>(p, s);  // straight schedule, 3 waves/SIMD
-  if (nw == 4) return fold ? launch<T, 4, true>(p, s) : launch<T, 4, false>(p, s);             // register staging
+    case IR_PIPE_DEV_REG8: return launch_f<T, 0, false, 8>(p, s);
+    case IR_PIPE_DEV_DMA: return launch_f<T, kDma>(p, s);
+    case IR_PIPE_DEV_STRAIGHT3: return launch_f<T, kStraight3>(p, s);
+    case IR_PIPE_DEV_REG4: return launch_f<T, 0>(p, s);
 #endif
-  if (nw == 7) return fold ? launch<T, 4, true, 128>(p, s) : launch<T, 4, false, 128>(p, s);  // LDS-DMA from asm
-  if (nw == 10) return fold ? launch<T, 4, true, 128 | 1024>(p, s) : launch<T, 4, false, 128 | 1024>(p, s);  // asm DMA + lazy max
-  if (nw == 11) return fold ? launch<T, 4, true, 128 | 1024 | 2048>(p, s) : launch<T, 4, false, 128 | 1024 | 2048>(p, s);  // + pre-scaled Q, reference through the C operand
-  if (nw == 14) return fold ? launch<T, 4, true, 128 | 1024 | 4096>(p, s) : launch<T, 4, false, 128 | 1024 | 4096>(p, s);  // + QK^T of the next tile first
-  if (nw == 18) return fold ? launch<T, 4, true, 128 | 1024 | 2048 | 8192>(p, s) : launch<T, 4, false, 128 | 1024 | 2048 | 8192>(p, s);  // 11 + reference checked after the exponentials
-  return hipErrorInvalidValue;
+    case IR_PIPE_EXACT: return launch_f<T, kFormExact>(p, s);
+    case IR_PIPE_LAZY: return launch_f<T, kFormLazy>(p, s);
+    case IR_PIPE_PRESC: return launch_f<T, kFormPresc>(p, s);
+    case IR_PIPE_EARLYQK: return launch_f<T, kFormEarlyQK>(p, s);
+    case IR_PIPE_POSTCHECK: return launch_f<T, kFormPostCheck>(p, s);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace
@@ -878,21 +866,22 @@ hipError_t ir_launch_shared_attn_fwd_pipe_abl(const AttnKParams& p, int abl, hip
 #endif
 }
 
-// combine launcher shared with the ping-pong kernel (p must carry the final sk_* / ws_* fields)
-hipError_t ir_launch_shared_attn_combine(const AttnKParams& p, int dtype, int qb, int rem, hipStream_t s) {
-  if (qb == 512) {
-    if (dtype == 1) hipLaunchKernelGGL((shared_attn_combine_kernel<__bf16, 512>), dim3(8 * rem, 32), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((shared_attn_combine_kernel<_Float16, 512>), dim3(8 * rem, 32), dim3(256), 0, s, p);
-  } else if (qb == 256) {
-    if (dtype == 1) hipLaunchKernelGGL((shared_attn_combine_kernel<__bf16, 256>), dim3(8 * rem, 16), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((shared_attn_combine_kernel<_Float16, 256>), dim3(8 * rem, 16), dim3(256), 0, s, p);
-  } else {
-    if (dtype == 1) hipLaunchKernelGGL((shared_attn_combine_kernel<__bf16, 128>), dim3(8 * rem, 8), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((shared_attn_combine_kernel<_Float16, 128>), dim3(8 * rem, 8), dim3(256), 0, s, p);
-  }
+// the combine of every kernel family (p must carry the final sk_* / ws_* fields)
+template <typename T, int QB>
+static hipError_t combine(const AttnKParams& p, int rem, hipStream_t s) {
+  hipLaunchKernelGGL((shared_attn_combine_kernel<T, QB>), dim3(kIrXcds * rem, QB / 16), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 
-hipError_t ir_launch_shared_attn_fwd_pipe(const AttnKParams& p, int dtype, int nw, hipStream_t s) {
-  return dtype == 1 ? launch_t<__bf16>(p, nw, s) : launch_t<_Float16>(p, nw, s);
+hipError_t ir_launch_shared_attn_combine(const AttnKParams& p, int dtype, int qb, int rem, hipStream_t s) {
+  switch (qb) {
+    case 512: return dtype == 1 ? combine<__bf16, 512>(p, rem, s) : combine<_Float16, 512>(p, rem, s);
+    case 256: return dtype == 1 ? combine<__bf16, 256>(p, rem, s) : combine<_Float16, 256>(p, rem, s);
+    case 128: return dtype == 1 ? combine<__bf16, 128>(p, rem, s) : combine<_Float16, 128>(p, rem, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t ir_launch_shared_attn_fwd_pipe(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s) {
+  return dtype == 1 ? launch_t<__bf16>(p, form, s) : launch_t<_Float16>(p, form, s);
 }

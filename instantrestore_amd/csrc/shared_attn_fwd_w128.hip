@@ -462,33 +462,13 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(1,
 
 template <typename T, bool FOLD, bool FORMS = false>
 hipError_t launch(const AttnKParams& p0, hipStream_t s) {
+  const IrAttnPlan pl = ir_attn_plan(ir_attn_plan_in(p0, QB, 32));   // one workgroup (four waves, one per SIMD) per CU, 32 CUs per XCD
   AttnKParams p = p0;
-  p.nqb = (p.Lq + QB - 1) / QB;
-  p.sk_items = p.B * p.H * p.nqb;
-  p.sk_ix = (p.sk_items + 7) / 8;
-  const int slots_x = 32;   // one workgroup (four waves, one per SIMD) per CU, 32 CUs per XCD
-  int full = (p.sk_ix / slots_x) * slots_x;
-  int rem = p.sk_ix - full;
-  int k = 1;
-  if (p0.sk_k > 0) {   // a fixed plan (batch-invariant mode): every item in sk_k pieces
-    k = p0.sk_k;
-    full = k > 1 ? 0 : p.sk_ix;
-    rem = p.sk_ix - full;
-  } else if (p.ws != nullptr && rem > 0) {
-    const size_t piece_bytes = (size_t)QB * (66 + (p.seg_cum != nullptr ? p.nseg_out : 0)) * sizeof(float);
-    k = ir_pick_split(rem, slots_x, p.ntiles / 8 /* pieces of at least 8 tiles */, (long)(p.ws_bytes / piece_bytes / 8));
-  }
-  if (k <= 1) { full = p.sk_ix; rem = 0; k = 1; }
-  p.sk_full = full;
-  p.sk_k = k;
-  p.ws_o = p.ws;
-  p.ws_ml = p.ws + (size_t)8 * rem * k * QB * 64;
-  p.ws_cum = p.seg_cum != nullptr ? p.ws_ml + (size_t)8 * rem * k * QB * 2 : nullptr;
-  const int grid = 8 * (full + rem * k);
-  hipLaunchKernelGGL((shared_attn_fwd_w128_kernel<T, FOLD, FORMS>), dim3(grid), dim3(NW * 64), 0, s, p);
+  ir_attn_plan_apply(pl, p);
+  hipLaunchKernelGGL((shared_attn_fwd_w128_kernel<T, FOLD, FORMS>), dim3(pl.grid), dim3(NW * 64), 0, s, p);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess || k <= 1) return e;
-  return ir_launch_shared_attn_combine(p, std::is_same<T, __bf16>::value ? 1 : 0, QB, rem, s);
+  if (e != hipSuccess || pl.k <= 1) return e;
+  return ir_launch_shared_attn_combine(p, std::is_same<T, __bf16>::value ? 1 : 0, QB, pl.rem, s);
 }
 
 }  // namespace

@@ -701,33 +701,13 @@ __global__ void __launch_bounds__(NW * 64, 2) shared_attn_fwd_w64_kernel(const A
 template <typename T, bool FOLD, int NW = 4, bool QS = false, int ABL = 0, bool MASS = false>
 hipError_t launch(const AttnKParams& p0, hipStream_t s) {
   if (!MASS && p0.seg_cum != nullptr) return hipErrorInvalidValue;   // seg_mass: the 8-wave forms carry the MASS instantiation
-  AttnKParams p = p0;
   constexpr int QB = NW * 64;
-  p.nqb = (p.Lq + QB - 1) / QB;
-  p.sk_items = p.B * p.H * p.nqb;
-  p.sk_ix = (p.sk_items + 7) / 8;
   // resident workgroups per CU: 8 waves (two per SIMD at ~256 registers), and the QS form's LDS (K/V ring + NW x 8 KiB of Q)
   constexpr int lds_wg = QS ? (2 * W64_RING * TILE_BYTES + NW * 8192) : (2 * W64_RING * TILE_BYTES);
   constexpr int by_lds = (160 * 1024) / lds_wg, by_waves = 8 / NW;
-  const int slots_x = 32 * (by_lds < by_waves ? by_lds : by_waves);
-  int full = (p.sk_ix / slots_x) * slots_x;
-  int rem = p.sk_ix - full;
-  int k = 1;
-  if (p0.sk_k > 0) {   // a fixed plan (batch-invariant mode): every item in sk_k pieces
-    k = p0.sk_k;
-    full = k > 1 ? 0 : p.sk_ix;
-    rem = p.sk_ix - full;
-  } else if (p.ws != nullptr && rem > 0) {
-    const size_t piece_bytes = (size_t)QB * (66 + (p.seg_cum != nullptr ? p.nseg_out : 0)) * sizeof(float);
-    k = ir_pick_split(rem, slots_x, p.ntiles / 8 /* pieces of at least 8 tiles */, (long)(p.ws_bytes / piece_bytes / 8));
-  }
-  if (k <= 1) { full = p.sk_ix; rem = 0; k = 1; }
-  p.sk_full = full;
-  p.sk_k = k;
-  p.ws_o = p.ws;
-  p.ws_ml = p.ws + (size_t)8 * rem * k * QB * 64;
-  p.ws_cum = p.ws_ml + (size_t)8 * rem * k * QB * 2;
-  const int grid = 8 * (full + rem * k);
+  const IrAttnPlan pl = ir_attn_plan(ir_attn_plan_in(p0, QB, 32 * (by_lds < by_waves ? by_lds : by_waves)));
+  AttnKParams p = p0;
+  ir_attn_plan_apply(pl, p);
   size_t dyn_lds = 0;
   if (QS) {
     dyn_lds = (size_t)2 * W64_RING * TILE_BYTES + (size_t)NW * 8192;   // K/V ring + the waves' Q fragments
@@ -735,10 +715,10 @@ hipError_t launch(const AttnKParams& p0, hipStream_t s) {
     const hipError_t ea = ir_opt_in_dynamic_lds(once, (const void*)shared_attn_fwd_w64_kernel<T, FOLD, NW, QS, ABL, MASS>, dyn_lds);
     if (ea != hipSuccess) return ea;
   }
-  hipLaunchKernelGGL((shared_attn_fwd_w64_kernel<T, FOLD, NW, QS, ABL, MASS>), dim3(grid), dim3(NW * 64), dyn_lds, s, p);
+  hipLaunchKernelGGL((shared_attn_fwd_w64_kernel<T, FOLD, NW, QS, ABL, MASS>), dim3(pl.grid), dim3(NW * 64), dyn_lds, s, p);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess || k <= 1) return e;
-  return ir_launch_shared_attn_combine(p, std::is_same<T, __bf16>::value ? 1 : 0, QB, rem, s);
+  if (e != hipSuccess || pl.k <= 1) return e;
+  return ir_launch_shared_attn_combine(p, std::is_same<T, __bf16>::value ? 1 : 0, QB, pl.rem, s);
 }
 
 }  // namespace
