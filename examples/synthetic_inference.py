@@ -51,6 +51,8 @@ def main(argv=None):
     ap.add_argument("--small", action="store_true", help="narrow UNet topology (tests)")
     ap.add_argument("--landmark-maps", action="store_true",
                     help="one more frame that leaves the landmark attention map of every shared layer behind (attention_rows)")
+    ap.add_argument("--kv-tables", action="store_true",
+                    help="one more cached frame whose reference K/V are pointer tables into the cache entries (assemble_tables: no copy)")
     args = ap.parse_args(argv)
 
     import __graft_entry__ as ge
@@ -121,6 +123,13 @@ def main(argv=None):
         z2 = unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1),
                   cross_attention_kwargs={"ref_keys": ck, "ref_values": cv, "ref_stats": cs}).sample
         assert torch.equal(ops.tensor2im_u8(vae.decode(z2)), out_u8), "cached K/V + statistics must reproduce the frame"
+        if args.kv_tables:
+            # the same cached frame without the (B, N, L, C) copies of assemble(): every layer gets a table of pointers into the
+            # per-identity entries (one small host-to-device copy for all 18 tables), and the kernels read the entries in place
+            tk, tv, ts, tvalid = cache.assemble_tables(["id%d" % b for b in range(B)])
+            z3 = unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1),
+                      cross_attention_kwargs={"ref_keys": tk, "ref_values": tv, "ref_stats": ts, "ref_valid": tvalid}).sample
+            assert torch.equal(ops.tensor2im_u8(vae.decode(z3)), out_u8), "pointer tables into the cache must reproduce the frame"
         # A checkpoint trained with fewer references than the caller hands in (inference/test.py:81 passes ITS
         # max_conditioning_images as valid count; pix2pix_turbo.py:269-273 zero-fills the rest): told the counts
         # (cross_attention_kwargs['ref_valid'], what harvest_reference_kv(..., with_valid=True) returns) the kernels close the

@@ -36,7 +36,7 @@ extern "C" {
 
 typedef enum ir_status {
   IR_OK = 0,
-  IR_ERR_INVALID_ARG = -1, /* NULL pointer, negative size, bad stride, bad struct_size */
+  IR_ERR_INVALID_ARG = -1, /* NULL pointer, negative size, bad stride, bad struct_size, a broken rule of a pointer-table call */
   IR_ERR_UNSUPPORTED = -2, /* dtype / head_dim / alignment the kernels do not implement */
   IR_ERR_LAUNCH = -3,      /* hipLaunchKernel reported an error (see ir_last_error_string) */
   IR_ERR_WORKSPACE = -4    /* workspace too small */
@@ -88,7 +88,7 @@ typedef enum ir_dtype { IR_DTYPE_F16 = 0, IR_DTYPE_BF16 = 1 } ir_dtype;
  * All base pointers and strides must keep every (row, head) vector 16-byte aligned.
  */
 typedef struct ir_shared_attn_args {
-  uint32_t struct_size; /* = sizeof(ir_shared_attn_args) */
+  uint32_t struct_size; /* = sizeof(ir_shared_attn_args), or sizeof(ir_shared_attn_table_args) when the block is one (below) */
   int32_t dtype;        /* ir_dtype */
   uint32_t flags;       /* IR_FLAG_* */
   int32_t batch;        /* B */
@@ -136,6 +136,35 @@ typedef struct ir_shared_attn_args {
                                at column 0) are mass[..., 0:4] - valid only when len_self == len_ref - and the per-REFERENCE
                                masses are mass[..., INCLUDE_SELF:].  NULL = off. */
 } ir_shared_attn_args;
+
+/*
+ * Reference K/V through pointer tables: ir_shared_attn_args with two optional fields appended.  Every entry point that takes an
+ * `const ir_shared_attn_args*` also takes a pointer to this block (cast to its first member) and tells the two apart by
+ * `args.struct_size`: sizeof(ir_shared_attn_args) - the block ends behind seg_mass and there are no tables - or
+ * sizeof(ir_shared_attn_table_args).  Every other size is IR_ERR_INVALID_ARG.  IR_ABI_VERSION stays 10: callers built against the
+ * shorter block keep working unchanged, and struct_size carries the compatibility.
+ *
+ *   k_ref_table : device array of B*N device pointers, entry [b*N + n] = &K[b, n, 0, 0, 0] (the first element of reference n of batch
+ *                 entry b, a (len_ref, H, 64) matrix with strides kr_sl, kr_sh); v_ref_table the same for V (vr_sl, vr_sh)
+ *
+ * Rules of a table call:
+ *   - both tables are given or both are NULL (NULL: the call is a dense one);
+ *   - with tables k_ref and v_ref must be NULL, n_refs must be > 0, and kr_sb, kr_sn, vr_sb, vr_sn must be 0;
+ *   - every ENTRY is 16-byte aligned: the caller's promise (the library cannot read device memory while it validates);
+ *   - with valid_refs, entries [b*N + n] with n >= valid_refs[b] are never read or dereferenced by ir_shared_attn_fwd
+ *     (ir_attn_probs[_ex], ir_attn_segment_mass and ir_attn_rows walk every reference and read every entry of the K table);
+ *   - the tables are read by the kernels when they RUN: a replayed hipGraph follows in-place updates of them (as row_index of
+ *     ir_attn_rows does).
+ * A table call runs the kernel, form and K/V-range pieces the same dense call would run (ir_shared_attn_kernel_name and
+ * ir_shared_attn_plan give the same answers) and the same arithmetic: identical bytes for identical data.  ir_adain_stats keeps its
+ * dense v_ref; a table caller gets its AdaIN affine from cached content statistics (ir_adain_stats_cached,
+ * ir_adain_affine_from_partials).
+ */
+typedef struct ir_shared_attn_table_args {
+  ir_shared_attn_args args;        /* args.struct_size = sizeof(ir_shared_attn_table_args) */
+  const void* const* k_ref_table;
+  const void* const* v_ref_table;
+} ir_shared_attn_table_args;
 
 /* values of ir_shared_attn_args.tuning (csrc/shared_attn_fwd.hip: kAttnVariants has one row per value - kernel family, form, what
  * it takes; ir_attn_choose is the dispatch) */

@@ -38,6 +38,14 @@ class SharedAttnArgs(C.Structure):
     )
 
 
+class SharedAttnTableArgs(SharedAttnArgs):
+    """mirror of ``ir_shared_attn_table_args``: ``ir_shared_attn_args`` with the two pointer-table fields appended (a ctypes
+    subclass appends its ``_fields_`` to the base's).  Every entry point that takes ``ir_shared_attn_args*`` takes this block too
+    and tells the two apart by ``struct_size``"""
+
+    _fields_ = [("k_ref_table", vp), ("v_ref_table", vp)]
+
+
 class SharedAttnPlan(C.Structure):
     """mirror of ``ir_shared_attn_plan_info`` (ABI v10: the batch-invariant plan of a call)"""
 

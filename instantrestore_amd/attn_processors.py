@@ -35,6 +35,7 @@ import torch
 from torch import nn
 
 from . import lora_fold as _lora
+from .ops import RefKVTable as _RefKVTable
 from . import ops as _ops  # tests swap this module-level name for an oracle-backed stand-in
 
 
@@ -432,7 +433,8 @@ class SharedAttnProcessor(nn.Module):
     r"""Extended self-attention over ``[self K/V (iff train_input)] ++ N x reference K/V``.
 
     ``ref_keys[self_attn_idx]`` / ``ref_values[...]`` are the ``(B, N, L, C)`` tensors produced
-    by ``get_conditioning_keys_values`` (pix2pix_turbo.py:265-266); they are read in place by the
+    by ``get_conditioning_keys_values`` (pix2pix_turbo.py:265-266) - or ``ops.RefKVTable`` pointer tables over per-identity cache
+    entries (``ReferenceKVCache.assemble_tables``: no ``(B, N, L, C)`` copy; with ``use_adain`` they need ``ref_stats``); they are read in place by the
     kernel (segment walk) - N is taken from the tensor, zero-filled references keep their
     ``exp(0)`` weight, and with ``use_adain`` every reference V is renormalised to the
     statistics of this image's own V inside the kernel's V staging.
@@ -522,9 +524,18 @@ class SharedAttnProcessor(nn.Module):
                                                              content_mean=cstats[0], content_std=cstats[1])
                 elif cstats is not None:
                     affine = _stats_cached(value, cstats, attn.heads)
+                elif isinstance(ref_v, _RefKVTable):
+                    # the content statistics would need a pass over every reference V, and ir_adain_stats reads a dense tensor:
+                    # a table is never densified behind the caller's back
+                    raise ValueError("use_adain with RefKVTable references needs ref_stats: cache the identities with their AdaIN content "
+                                     "statistics (get_conditioning_keys_values(..., with_stats=True)) and pass the stats of "
+                                     "ReferenceKVCache.assemble_tables")
                 else:
                     affine = _ops.adain_stats(value, ref_v, heads=attn.heads)
         _same_16bit(query, key, value, ref_k, ref_v)
+        if affine is not None and ref_v.shape[2] < FOLD_MIN_REF_TOKENS and isinstance(ref_v, _RefKVTable):
+            raise ValueError(f"RefKVTable references of fewer than {FOLD_MIN_REF_TOKENS} tokens with use_adain: this branch forms the "
+                             "renormalised V as a dense tensor; pass dense ref_values (the model's own axes never come here)")
         if affine is not None and ref_v.shape[2] < FOLD_MIN_REF_TOKENS:
             # a handful of reference tokens: a channel whose few values lie ulps apart gets a ratio in the thousands, and the
             # fold's a * sum(p~ v) + b * sum(p) would amplify the 16-bit rounding of P by a * |mean|.  Here the

@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(PW * 64) attn_probs_lines_kernel(const AttnKPa
     const int cr = c - pl.nch_self;
     const int n = cr / pl.nch_ref;
     chunk = cr - n * pl.nch_ref;
-    kb = (const T*)p.k_ref + (int64_t)b * p.kr_sb + (int64_t)n * p.kr_sn + (int64_t)h * p.kr_sh; ksl = p.kr_sl; len = p.Lr;
+    kb = ir_ref_entry((const T*)p.k_ref + (int64_t)b * p.kr_sb + (int64_t)n * p.kr_sn, p.ref_tables) + (int64_t)h * p.kr_sh; ksl = p.kr_sl; len = p.Lr;
     col0 = p.include_self * p.Ls + n * p.Lr;
     seg = p.include_self + n;
   }
@@ -264,7 +264,7 @@ __global__ void __launch_bounds__(PW * 64) attn_probs_generic_kernel(const AttnK
       kb = (const T*)p.k_self + (int64_t)b * p.ks_sb + (int64_t)h * p.ks_sh; ksl = p.ks_sl; len = p.Ls;
     } else {
       const int n = s - p.include_self;
-      kb = (const T*)p.k_ref + (int64_t)b * p.kr_sb + (int64_t)n * p.kr_sn + (int64_t)h * p.kr_sh; ksl = p.kr_sl; len = p.Lr;
+      kb = ir_ref_entry((const T*)p.k_ref + (int64_t)b * p.kr_sb + (int64_t)n * p.kr_sn, p.ref_tables) + (int64_t)h * p.kr_sh; ksl = p.kr_sl; len = p.Lr;
     }
     for (int j0 = 0; j0 < len; j0 += 32) {
       const int key = j0 + lq;

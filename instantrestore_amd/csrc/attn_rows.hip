@@ -118,7 +118,7 @@ __global__ void __launch_bounds__(RW * 64) attn_rows_kernel(const AttnKParams p,
     const int cr = c - pl.nch_self;
     const int n = cr / pl.nch_ref;
     chunk = cr - n * pl.nch_ref;
-    kb = (const T*)p.k_ref + (int64_t)b * p.kr_sb + (int64_t)n * p.kr_sn; ksl = p.kr_sl; ksh = p.kr_sh; len = p.Lr;
+    kb = ir_ref_entry((const T*)p.k_ref + (int64_t)b * p.kr_sb + (int64_t)n * p.kr_sn, p.ref_tables); ksl = p.kr_sl; ksh = p.kr_sh; len = p.Lr;
     col0 = p.include_self * p.Ls + n * p.Lr;
   }
   const int j_begin = (chunk * RW + wid) * pl.kpw;

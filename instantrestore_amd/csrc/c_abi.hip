@@ -25,8 +25,14 @@ bool stride_ok(int64_t s) { return s >= 0 && (s % 8) == 0; }  // keeps every hea
 
 int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_out) {
   if (a == nullptr) return fail(IR_ERR_INVALID_ARG, "args is NULL");
-  if (a->struct_size != sizeof(ir_shared_attn_args))
-    return fail(IR_ERR_INVALID_ARG, "struct_size %u != %zu (ABI mismatch)", a->struct_size, sizeof(ir_shared_attn_args));
+  // the block up to and including seg_mass (no pointer tables), or ir_shared_attn_table_args; nothing in between
+  if (a->struct_size != sizeof(ir_shared_attn_args) && a->struct_size != sizeof(ir_shared_attn_table_args))
+    return fail(IR_ERR_INVALID_ARG, "struct_size %u != %zu or %zu (ABI mismatch)", a->struct_size, sizeof(ir_shared_attn_args),
+                sizeof(ir_shared_attn_table_args));
+  const ir_shared_attn_table_args* ta = a->struct_size == sizeof(ir_shared_attn_table_args) ? (const ir_shared_attn_table_args*)a : nullptr;
+  const void* const* ktab = ta != nullptr ? ta->k_ref_table : nullptr;
+  const void* const* vtab = ta != nullptr ? ta->v_ref_table : nullptr;
+  const bool tables = ktab != nullptr;
   if (a->dtype != IR_DTYPE_F16 && a->dtype != IR_DTYPE_BF16)
     return fail(IR_ERR_UNSUPPORTED, "dtype %d: only fp16 (0) and bf16 (1) are implemented", a->dtype);
   if (a->batch <= 0 || a->heads <= 0 || a->len_q <= 0) return fail(IR_ERR_INVALID_ARG, "batch/heads/len_q must be > 0");
@@ -42,7 +48,15 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
   if (!inc && a->n_refs == 0) return fail(IR_ERR_INVALID_ARG, "empty key/value sequence");
   if (a->q == nullptr || (need_out && a->out == nullptr)) return fail(IR_ERR_INVALID_ARG, "q/out is NULL");
   if (inc && (a->k_self == nullptr || a->v_self == nullptr)) return fail(IR_ERR_INVALID_ARG, "k_self/v_self is NULL");
-  if (a->n_refs > 0 && (a->k_ref == nullptr || a->v_ref == nullptr)) return fail(IR_ERR_INVALID_ARG, "k_ref/v_ref is NULL");
+  if ((ktab == nullptr) != (vtab == nullptr)) return fail(IR_ERR_INVALID_ARG, "k_ref_table and v_ref_table must both be set or both be NULL");
+  if (tables) {
+    if (a->k_ref != nullptr || a->v_ref != nullptr) return fail(IR_ERR_INVALID_ARG, "k_ref_table / v_ref_table given: k_ref and v_ref must be NULL");
+    if (a->n_refs == 0) return fail(IR_ERR_INVALID_ARG, "k_ref_table / v_ref_table need n_refs > 0");
+    if (a->kr_sb != 0 || a->kr_sn != 0 || a->vr_sb != 0 || a->vr_sn != 0)
+      return fail(IR_ERR_INVALID_ARG, "k_ref_table / v_ref_table given: the strides kr_sb, kr_sn, vr_sb, vr_sn must be 0 (the tables hold every base address)");
+    if (((reinterpret_cast<uintptr_t>(ktab) | reinterpret_cast<uintptr_t>(vtab)) & 7u) != 0) return fail(IR_ERR_UNSUPPORTED, "k_ref_table / v_ref_table must be 8-byte aligned");
+  }
+  if (a->n_refs > 0 && !tables && (a->k_ref == nullptr || a->v_ref == nullptr)) return fail(IR_ERR_INVALID_ARG, "k_ref/v_ref is NULL");
   if ((a->adain_a == nullptr) != (a->adain_b == nullptr)) return fail(IR_ERR_INVALID_ARG, "adain_a and adain_b must both be set or both be NULL");
   if (a->adain_a != nullptr && a->n_refs == 0) return fail(IR_ERR_INVALID_ARG, "AdaIN affine without references");
   if (a->valid_refs != nullptr && (reinterpret_cast<uintptr_t>(a->valid_refs) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "valid_refs must be 4-byte aligned");
@@ -69,6 +83,10 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
   p->vr_sb = a->vr_sb; p->vr_sn = a->vr_sn; p->vr_sl = a->vr_sl; p->vr_sh = a->vr_sh;
   p->o_sb = a->o_sb; p->o_sl = a->o_sl; p->o_sh = a->o_sh;
   p->B = a->batch; p->H = a->heads; p->Lq = a->len_q; p->Ls = a->len_self; p->N = a->n_refs; p->Lr = a->len_ref;
+  if (tables) {   // the tables in the dense fields, strided by entries (AttnKParams.ref_tables): batch_slice and every kernel index them as they index K / V
+    p->k_ref = ktab; p->v_ref = vtab; p->ref_tables = 1;
+    p->kr_sb = p->vr_sb = (int64_t)a->n_refs * 4; p->kr_sn = p->vr_sn = 4;
+  }
   p->include_self = inc ? 1 : 0;
   p->q_prescaled = (a->flags & IR_FLAG_Q_PRESCALED) ? 1 : 0;
   p->out_f32 = (a->flags & IR_FLAG_OUT_F32) ? 1 : 0;
@@ -114,7 +132,7 @@ int bi_batch_per_launch(const IrAttnBiPlan& pl, int batch, size_t ws_bytes) {
   return nb < (size_t)batch ? (int)nb : batch;
 }
 
-// the part of a call that covers batch entries [b0, b0 + nb): every pointer moved by b0 entries
+// the part of a call that covers batch entries [b0, b0 + nb): every pointer moved by b0 entries (pointer tables: by b0 * N table entries)
 AttnKParams batch_slice(const AttnKParams& p, int b0, int nb) {
   AttnKParams q = p;
   q.B = nb;
@@ -338,7 +356,7 @@ int ir_attn_segment_mass(const ir_shared_attn_args* args, float* mass, void* str
 
 int ir_attn_rows(const ir_shared_attn_args* args, const int32_t* row_index, int32_t n_rows, int32_t reduce, void* out, void* stream) {
   if (args == nullptr) return fail(IR_ERR_INVALID_ARG, "args is NULL");
-  if (args->struct_size == sizeof(ir_shared_attn_args) && args->tuning != IR_TUNE_DEFAULT)
+  if ((args->struct_size == sizeof(ir_shared_attn_args) || args->struct_size == sizeof(ir_shared_attn_table_args)) && args->tuning != IR_TUNE_DEFAULT)
     return fail(IR_ERR_UNSUPPORTED, "ir_attn_rows has one kernel: tuning must be 0 (got %d)", args->tuning);
   AttnKParams p;
   const int rc = build_attn_params(args, &p, false);

@@ -62,7 +62,24 @@ struct AttnKParams {
   int nseg_out;       // include_self + N
   // sk_k on ENTRY to a kernel launcher: 0 = the launcher plans the remainder split itself (default dispatch); > 0 = a fixed plan
   // (ABI v10 batch-invariant mode, ir_attn_bi_plan): every item in sk_k pieces (1: whole items), workspace sized by the caller
+  // pointer tables (ir_shared_attn_table_args.k_ref_table / v_ref_table): k_ref / v_ref then hold the TABLES - device arrays of B*N
+  // device pointers - and kr_sb, kr_sn (vr_sb, vr_sn) their strides in 2-byte elements (4 N and 4: eight bytes per entry), so the dense
+  // expression k_ref + b * kr_sb + n * kr_sn is the address of entry [b*N + n] and the kernels' one extra step is to read the
+  // segment's base address there (ir_ref_entry).  No kernel argument of its own for the tables: the attention kernels have no
+  // SGPRs to spare.  Read by the kernels when they run, never by the dispatch or the plans
+  int ref_tables;     // 0/1
 };
+
+// The base address (head 0, token 0) of a reference segment from `at` = k_ref + b * kr_sb + n * kr_sn: `at` itself in the dense
+// layout, the pointer stored at `at` in a pointer-table call.  Wave-uniform, outside every inner loop; read through the constant
+// address space (one scalar load: the tables do not change while a kernel runs)
+#ifdef __HIPCC__
+template <typename T>
+__device__ __forceinline__ const T* ir_ref_entry(const T* at, int tables) {
+  typedef const __attribute__((address_space(4))) uint64_t* ConstTable;
+  return tables ? (const T*)(uintptr_t)*(ConstTable)(uintptr_t)at : at;
+}
+#endif
 
 // what a kernel launcher gives ir_attn_plan (ir_attn_plan.h): the call, its own rows per item and slots rule
 static inline IrAttnPlanIn ir_attn_plan_in(const AttnKParams& p, int rows, int slots, int force_k = 0) {

@@ -230,8 +230,8 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(1,
       const int rr = t - p.tiles_self;
       const int n = rr / p.tiles_ref;
       r.seg = p.include_self + n; r.t0 = rr - n * p.tiles_ref; seg_tiles = p.tiles_ref;
-      r.sk = (const T*)p.k_ref + (int64_t)b * p.kr_sb + (int64_t)n * p.kr_sn + (int64_t)h * p.kr_sh;
-      r.sv = (const T*)p.v_ref + (int64_t)b * p.vr_sb + (int64_t)n * p.vr_sn + (int64_t)h * p.vr_sh;
+      r.sk = ir_ref_entry((const T*)p.k_ref + (int64_t)b * p.kr_sb + (int64_t)n * p.kr_sn, p.ref_tables) + (int64_t)h * p.kr_sh;
+      r.sv = ir_ref_entry((const T*)p.v_ref + (int64_t)b * p.vr_sb + (int64_t)n * p.vr_sn, p.ref_tables) + (int64_t)h * p.vr_sh;
       r.ksl_b = (int)p.kr_sl * 2; r.vsl_b = (int)p.vr_sl * 2; r.slen = p.Lr;
     }
     const int seg_left = seg_tiles - r.t0, piece_left = tile_end - t;

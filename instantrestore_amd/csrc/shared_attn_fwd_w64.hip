@@ -151,8 +151,8 @@ __global__ void __launch_bounds__(NW * 64, 2) shared_attn_fwd_w64_kernel(const A
       ksl_b = (int)c->ks_sl * 2; vsl_b = (int)c->vs_sl * 2; slen = c->Ls; sntile = c->tiles_self;
     } else {
       const int n = s - c->include_self;
-      sk = (const T*)c->k_ref + (int64_t)b * c->kr_sb + (int64_t)n * c->kr_sn + (int64_t)h * c->kr_sh;
-      sv = (const T*)c->v_ref + (int64_t)b * c->vr_sb + (int64_t)n * c->vr_sn + (int64_t)h * c->vr_sh;
+      sk = ir_ref_entry((const T*)c->k_ref + (int64_t)b * c->kr_sb + (int64_t)n * c->kr_sn, c->ref_tables) + (int64_t)h * c->kr_sh;
+      sv = ir_ref_entry((const T*)c->v_ref + (int64_t)b * c->vr_sb + (int64_t)n * c->vr_sn, c->ref_tables) + (int64_t)h * c->vr_sh;
       ksl_b = (int)c->kr_sl * 2; vsl_b = (int)c->vr_sl * 2; slen = c->Lr; sntile = c->tiles_ref;
     }
     krw = make_rsrc_words(sk, (unsigned)((slen - 1) * ksl_b + 128));

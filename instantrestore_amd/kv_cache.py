@@ -21,6 +21,11 @@ import torch
 KV = Tuple[List[torch.Tensor], ...]   # (keys, values) or (keys, values, stats): stats[l] = (mean, std) fp32 (1, N, H, 64)
 
 
+class _TableList(list):
+    """the key tables of one :meth:`ReferenceKVCache.assemble_tables` set; also holds what ``refill_tables`` rewrites - the set's
+    one pointer block (``buf``), its pinned staging tensor and the valid counts"""
+
+
 class ReferenceKVCache:
     def __init__(self, max_identities: int = 64):
         if max_identities < 1:
@@ -92,6 +97,121 @@ class ReferenceKVCache:
                      for l in range(n_layers)]
             return keys, values, stats
         return keys, values
+
+    def _table_plan(self, identities: Sequence[Hashable], n_max: int = 0):
+        """host side of :meth:`assemble_tables` / :meth:`refill_tables`: the entries (LRU order touched as :meth:`assemble`
+        touches it), every identity's reference count, N and whether the identities carry statistics"""
+        entries = [self._store[i] for i in identities]
+        for i in identities:
+            self._store.move_to_end(i)
+        counts = [int(e[0][0].shape[1]) for e in entries]
+        with_stats = [len(e) > 2 for e in entries]
+        if any(with_stats) and not all(with_stats):
+            raise ValueError("assemble_tables(): some of these identities were cached with AdaIN content statistics and some without; "
+                             "cache them the same way (the statistics would otherwise be dropped silently)")
+        return entries, counts, max(max(counts), n_max), all(with_stats)
+
+    @staticmethod
+    def _table_words(entries, counts, n_refs: int):
+        """the int64 words of one table set: 2 * layers * B * N addresses (keys of every layer, then values; an unused slot points
+        at its identity's reference 0), then the B valid counts packed as int32 pairs"""
+        n_layers = len(entries[0][0])
+        words = []
+        for side in (0, 1):
+            for l in range(n_layers):
+                for e, c in zip(entries, counts):
+                    t = e[side][l]
+                    if t.data_ptr() % 16 or t.stride(-1) != 1 or t.stride(2) % 8 or (t.stride(1) * t.element_size()) % 16:
+                        raise ValueError("assemble_tables(): a cached entry is not 16-byte aligned")
+                    words += [t[0, n if n < c else 0].data_ptr() for n in range(n_refs)]
+        valid = counts + [0] * (len(counts) % 2)
+        words += [valid[i] | (valid[i + 1] << 32) for i in range(0, len(valid), 2)]     # little-endian int32 pairs
+        return words
+
+    @staticmethod
+    def _table_stats(entries, counts, n_refs: int, l: int):
+        """layer l's content statistics (B, N, H, 64): concatenated; an unused slot gets (0, 0), what the harvest writes for a
+        zero-filled reference"""
+        if any(e[2][l] is None for e in entries):
+            return None
+        def pad(t, c):
+            return t if c == n_refs else torch.cat([t, t.new_zeros((1, n_refs - c) + tuple(t.shape[2:]))], dim=1)
+        return (torch.cat([pad(e[2][l][0], c) for e, c in zip(entries, counts)], dim=0),
+                torch.cat([pad(e[2][l][1], c) for e, c in zip(entries, counts)], dim=0))
+
+    def assemble_tables(self, identities: Sequence[Hashable]):
+        """:meth:`assemble` without the copy: per layer an :class:`instantrestore_amd.ops.RefKVTable` of pointers INTO the cached
+        entries instead of a dense ``(B, N, L, C)`` tensor.  Nothing of K/V size is allocated or moved: the pointer arrays of all
+        layers (keys and values) and the valid counts live in one int64 device tensor filled by one host-to-device copy, and each
+        table keeps the entries it points into alive (an evicted or invalidated identity stays readable while a table holds it).
+
+        Identities cached with different numbers of references may share a batch: ``N`` is the largest count, unused slots point at
+        their identity's reference 0 and carry content statistics (0, 0), and ``valid`` says how many references each identity has.
+
+        Returns ``(keys, values, stats, valid)``: ``stats`` as :meth:`assemble` returns them (``None`` when the identities were
+        cached without), ``valid`` an int32 ``(B,)`` device tensor to hand over as ``ref_valid`` when the counts differ, ``None``
+        when every identity has ``N`` references (the call then is the dense call's, kernel for kernel)."""
+        from .ops import RefKVTable, _PinnedStage
+
+        entries, counts, n_refs, with_stats = self._table_plan(identities)
+        n_layers, B = len(entries[0][0]), len(entries)
+        words = self._table_words(entries, counts, n_refs)
+        first = entries[0][0][0]
+        buf = torch.empty(len(words), dtype=torch.int64, device=first.device)
+        if first.is_cuda:
+            stage = _PinnedStage(len(words))
+            with torch.cuda.device(first.device):
+                stage.upload(words, buf)
+        else:
+            stage = None
+            buf.copy_(torch.tensor(words, dtype=torch.int64))
+        ptrs = buf[:2 * n_layers * B * n_refs].view(2, n_layers, B, n_refs)
+        tables = []
+        for side in (0, 1):
+            tables.append([RefKVTable(ptrs[side, l], e0.shape[2], e0.shape[3], e0.stride(2), e0.dtype, [e[side][l] for e in entries])
+                           for l, e0 in enumerate(entries[0][side])])
+            for l, t in enumerate(tables[-1]):
+                if any(e[side][l].shape[2:] != entries[0][side][l].shape[2:] or e[side][l].dtype != t.dtype or
+                       e[side][l].stride(2) != t.row_stride for e in entries):
+                    raise ValueError("assemble_tables(): the identities' cached tensors differ in length, width, dtype or row stride")
+        valid_all = buf[2 * n_layers * B * n_refs:].view(torch.int32)[:B]
+        stats = [self._table_stats(entries, counts, n_refs, l) for l in range(n_layers)] if with_stats else None
+        keys = _TableList(tables[0])
+        keys.buf, keys.stage, keys.valid_all = buf, stage, valid_all
+        return keys, tables[1], stats, (valid_all if min(counts) < n_refs else None)
+
+    def refill_tables(self, tables, identities: Sequence[Hashable]) -> None:
+        """point the set returned by :meth:`assemble_tables` at other identities IN PLACE - pointer arrays, valid counts and
+        statistics keep their addresses, so a captured step that reads them serves the new identities on its next replay.  One
+        host-to-device copy of the pointer block (plus the statistics' few KB).  Same batch size; no identity may have more
+        references than the set's N, and a set assembled without ``valid`` takes identities of exactly N references only."""
+        keys, values, stats, valid = tables
+        n_layers, (B, n_refs) = len(keys), keys[0].shape[:2]
+        entries, counts, n_now, with_stats = self._table_plan(identities, n_refs)
+        if len(entries) != B or n_now != n_refs or len(entries[0][0]) != n_layers:
+            raise ValueError(f"refill_tables(): the set holds {B} identities of up to {n_refs} references in {n_layers} layers")
+        if valid is None and min(counts) < n_refs:
+            raise ValueError("refill_tables(): this set was assembled without valid counts (every identity had N references); "
+                             "assemble a new one for identities with fewer")
+        if with_stats != (stats is not None):
+            raise ValueError("refill_tables(): the set and the identities differ in whether they carry AdaIN content statistics")
+        words = self._table_words(entries, counts, n_refs)
+        if keys.stage is not None:
+            with torch.cuda.device(keys.buf.device):
+                keys.stage.upload(words, keys.buf)
+        else:
+            keys.buf.copy_(torch.tensor(words, dtype=torch.int64))
+        for side, tabs in ((0, keys), (1, values)):
+            for l, t in enumerate(tabs):
+                t.tensors = [e[side][l] for e in entries]
+        if stats is not None:
+            for l, st in enumerate(stats):
+                new = self._table_stats(entries, counts, n_refs, l)
+                if (st is None) != (new is None):
+                    raise ValueError("refill_tables(): layer %d: statistics present on one side only" % l)
+                if st is not None:
+                    st[0].copy_(new[0])
+                    st[1].copy_(new[1])
 
     def nbytes(self, identity: Hashable) -> int:
         """device bytes held for one cached identity"""

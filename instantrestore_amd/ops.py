@@ -62,7 +62,7 @@ def _on_tensor_device(fn):
     def wrapper(*args, **kwargs):
         dev = None
         for a in list(args) + list(kwargs.values()):
-            if isinstance(a, torch.Tensor) and a.is_cuda:
+            if isinstance(a, (torch.Tensor, RefKVTable)) and a.is_cuda:
                 dev = a.device
                 break
         if dev is None or dev.index == torch.cuda.current_device():
@@ -99,7 +99,11 @@ def _tok(t: torch.Tensor, heads: int, name: str) -> torch.Tensor:
     return t
 
 
-def _ref(t: torch.Tensor, heads: int, name: str) -> torch.Tensor:
+def _ref(t, heads: int, name: str):
+    if _is_table(t):      # a pointer table is used as it is (from_tensors checked strides and alignment); never densified
+        if t.shape[-1] != heads * HEAD_DIM:
+            raise ValueError(f"{name}: expected a table of (L, {heads * HEAD_DIM}) entries, got {tuple(t.shape)}")
+        return t
     if t.dim() != 4 or t.shape[-1] != heads * HEAD_DIM:
         raise ValueError(f"{name}: expected (B, N, L, {heads * HEAD_DIM}), got {tuple(t.shape)}")
     if t.stride(-1) != 1 or any(t.stride(i) % 8 for i in range(3)) or t.data_ptr() % 16:
@@ -107,10 +111,146 @@ def _ref(t: torch.Tensor, heads: int, name: str) -> torch.Tensor:
     return t
 
 
+def _grid_pointers(grid, valid=None):
+    """``grid`` (B rows of N ``(L, C)`` tensors) -> (B x N addresses, (L, C, row stride, dtype, device), the tensors).  ``None`` is
+    allowed only in slots ``n >= valid[b]``; such a slot gets the address of the row's reference 0 (of the grid's first tensor
+    when the whole row is empty): a readable address that a call with ``valid_refs`` never uses."""
+    rows = [list(r) for r in grid]
+    if not rows or not rows[0] or any(len(r) != len(rows[0]) for r in rows):
+        raise ValueError("RefKVTable: grid must be B non-empty rows of N entries each")
+    if valid is not None and len(valid) != len(rows):
+        raise ValueError(f"RefKVTable: {len(valid)} valid counts for {len(rows)} rows")
+    tensors = [t for r in rows for t in r if t is not None]
+    if not tensors:
+        raise ValueError("RefKVTable: no tensor in the grid")
+    first = tensors[0]
+    for t in tensors:
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError("RefKVTable: every entry must be an (L, C) tensor with a contiguous channel axis")
+        if t.dtype != first.dtype or t.device != first.device:
+            raise ValueError(f"RefKVTable: mixed dtype / device ({t.dtype} on {t.device} vs {first.dtype} on {first.device})")
+        if t.shape != first.shape:
+            raise ValueError(f"RefKVTable: mixed shapes {tuple(t.shape)} vs {tuple(first.shape)} (every entry has the same L and C)")
+        if t.stride(0) != first.stride(0):
+            raise ValueError(f"RefKVTable: mixed row strides {t.stride(0)} vs {first.stride(0)}")
+        if t.stride(0) % 8:
+            raise ValueError(f"RefKVTable: row stride {t.stride(0)} is not a multiple of 8 elements")
+        if t.data_ptr() % 16:
+            raise ValueError(f"RefKVTable: an entry at address {t.data_ptr():#x} is not 16-byte aligned")
+    ptrs = []
+    for b, r in enumerate(rows):
+        nv = len(r) if valid is None else int(valid[b])
+        if not 0 <= nv <= len(r):
+            raise ValueError(f"RefKVTable: valid count {nv} of row {b} outside [0, {len(r)}]")
+        row = []
+        for n, t in enumerate(r):
+            if t is None:
+                if n < nv:
+                    raise ValueError(f"RefKVTable: entry [{b}][{n}] is None but row {b} has {nv} valid references")
+                t = r[0] if r[0] is not None else first
+            row.append(t.data_ptr())
+        ptrs.append(row)
+    return ptrs, (first.shape[0], first.shape[1], first.stride(0), first.dtype, first.device), tensors
+
+
+class _PinnedStage:
+    """one pinned host tensor that feeds ``copy_(non_blocking=True)`` uploads: before the host rewrites it, the previous upload
+    from it has to have run (an event recorded behind that copy; a few KB, long done in practice)"""
+
+    __slots__ = ("host", "event")
+
+    def __init__(self, numel: int):
+        self.host = torch.empty(numel, dtype=torch.int64, pin_memory=True)
+        self.event = None
+
+    def upload(self, values, dst: torch.Tensor) -> None:
+        if self.event is not None:
+            self.event.synchronize()
+        self.host.copy_(torch.as_tensor(values, dtype=torch.int64).reshape(-1))
+        dst.copy_(self.host.view(dst.shape), non_blocking=True)     # on the current stream
+        self.event = None
+        if not torch.cuda.is_current_stream_capturing():    # (a captured copy re-reads the staging tensor at every replay: fill outside)
+            self.event = torch.cuda.Event()
+            self.event.record(torch.cuda.current_stream(dst.device))
+
+
+class RefKVTable:
+    """The reference K (or V) of one layer as a TABLE of device pointers instead of one dense ``(B, N, L, C)`` tensor
+    (``ir_shared_attn_table_args``): ``ptrs`` is an int64 ``(B, N)`` tensor on the entries' device, ``ptrs[b, n]`` the address of
+    the ``(L, C)`` matrix of reference ``n`` of batch entry ``b`` - which may live anywhere (a per-identity cache entry, a slice
+    of a pool, the K third of a fused ``(L, 3C)`` projection output), as long as all entries share dtype, ``L``, ``C`` and the row
+    stride and are 16-byte aligned.  Nothing of K/V size is allocated or copied.  ``shape`` / ``dtype`` / ``device`` are those of
+    the dense tensor it stands for; ``tensors`` keeps the entries alive.
+
+    The kernels read the table when they run: after :meth:`fill_` a replayed graph attends to the new entries."""
+
+    __slots__ = ("ptrs", "shape", "dtype", "device", "row_stride", "tensors", "_stage")
+
+    def __init__(self, ptrs: torch.Tensor, length: int, channels: int, row_stride: int, dtype: torch.dtype, tensors):
+        if ptrs.dtype != torch.int64 or ptrs.dim() != 2 or not ptrs.is_contiguous():
+            raise ValueError("RefKVTable: ptrs must be a contiguous int64 (B, N) tensor")
+        self.ptrs = ptrs
+        self.shape = torch.Size((ptrs.shape[0], ptrs.shape[1], int(length), int(channels)))
+        self.dtype, self.device, self.row_stride = dtype, ptrs.device, int(row_stride)
+        self.tensors = list(tensors)
+        self._stage = None
+
+    @classmethod
+    def from_tensors(cls, grid, valid=None) -> "RefKVTable":
+        """``grid``: ``B`` rows of ``N`` ``(L, C)`` tensors (same device, dtype, L, C and row stride; ``data_ptr() % 16 == 0``).
+        ``valid`` (optional, ``B`` counts): slots ``n >= valid[b]`` may be ``None``; pass the same counts to the attention call as
+        ``valid_refs``.  One small host-to-device copy on the current stream."""
+        ptrs, (length, channels, row_stride, dtype, device), tensors = _grid_pointers(grid, valid)
+        host = torch.tensor(ptrs, dtype=torch.int64)
+        table = cls(host if device.type == "cpu" else torch.empty(host.shape, dtype=torch.int64, device=device),
+                    length, channels, row_stride, dtype, tensors)
+        if device.type != "cpu":
+            with torch.cuda.device(device):
+                table._upload(ptrs)
+        return table
+
+    def _upload(self, ptrs) -> None:
+        if self._stage is None:
+            self._stage = _PinnedStage(self.ptrs.numel())
+        self._stage.upload(ptrs, self.ptrs)
+
+    def fill_(self, grid, valid=None) -> "RefKVTable":
+        """point the table at other entries of the same geometry, IN PLACE (``ptrs`` keeps its address: a captured graph that
+        reads it follows): one pinned staging tensor, one ``copy_(non_blocking=True)`` on the current stream"""
+        ptrs, (length, channels, row_stride, dtype, device), tensors = _grid_pointers(grid, valid)
+        if (len(ptrs), len(ptrs[0]), length, channels) != tuple(self.shape) or row_stride != self.row_stride or dtype != self.dtype \
+                or device != self.device:
+            raise ValueError(f"RefKVTable.fill_: the entries do not match the table ({tuple(self.shape)}, row stride {self.row_stride}, "
+                             f"{self.dtype} on {self.device})")
+        if self.device.type == "cpu":
+            self.ptrs.copy_(torch.tensor(ptrs, dtype=torch.int64))
+        else:
+            with torch.cuda.device(self.device):
+                self._upload(ptrs)
+        self.tensors = list(tensors)
+        return self
+
+    @property
+    def is_cuda(self) -> bool:
+        return self.device.type == "cuda"
+
+    def dim(self) -> int:
+        return 4
+
+    def record_stream(self, stream) -> None:
+        self.ptrs.record_stream(stream)
+        for t in self.tensors:
+            t.record_stream(stream)
+
+
+def _is_table(t) -> bool:
+    return isinstance(t, RefKVTable)
+
+
 def _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, lse, split=True,
                q_prescaled=False, valid_refs=None, batch_invariant=False):
-    a = _lib.SharedAttnArgs()
-    a.struct_size = C.sizeof(_lib.SharedAttnArgs)
+    a = _lib.SharedAttnTableArgs() if _is_table(ref_k) else _lib.SharedAttnArgs()
+    a.struct_size = C.sizeof(a)
     a.dtype = _dtype_code(q)
     a.flags = (_lib.IR_FLAG_INCLUDE_SELF if include_self else 0) | (_lib.IR_FLAG_Q_PRESCALED if q_prescaled else 0)
     if out is not None and out.dtype == torch.float32:
@@ -128,7 +268,11 @@ def _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adai
         a.k_self, a.v_self = k_self.data_ptr(), v_self.data_ptr()
         a.ks_sb, a.ks_sl, a.ks_sh = k_self.stride(0), k_self.stride(1), HEAD_DIM
         a.vs_sb, a.vs_sl, a.vs_sh = v_self.stride(0), v_self.stride(1), HEAD_DIM
-    if ref_k is not None:
+    if _is_table(ref_k):     # ir_shared_attn_table_args: k_ref / v_ref stay NULL, the batch and reference strides 0
+        a.n_refs, a.len_ref = ref_k.shape[1], ref_k.shape[2]
+        a.k_ref_table, a.v_ref_table = ref_k.ptrs.data_ptr(), ref_v.ptrs.data_ptr()
+        a.kr_sl, a.kr_sh, a.vr_sl, a.vr_sh = ref_k.row_stride, HEAD_DIM, ref_v.row_stride, HEAD_DIM
+    elif ref_k is not None:
         a.n_refs, a.len_ref = ref_k.shape[1], ref_k.shape[2]
         a.k_ref, a.v_ref = ref_k.data_ptr(), ref_v.data_ptr()
         a.kr_sb, a.kr_sn, a.kr_sl, a.kr_sh = ref_k.stride(0), ref_k.stride(1), ref_k.stride(2), HEAD_DIM
@@ -208,13 +352,15 @@ def _workspace(device: torch.device) -> torch.Tensor:
 def _forward_only(*ts) -> None:
     """the HIP path is the inference forward (test.py runs under ``torch.no_grad()``): a tensor that would
     need a backward through it must not pass silently - the result would carry no ``grad_fn``"""
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+    if torch.is_grad_enabled() and any(t is not None and not _is_table(t) and t.requires_grad for t in ts):
         raise NotImplementedError(
             "instantrestore_amd ops are forward-only (inference hot path): run under torch.no_grad() / "
             "inference_mode(); the training backward of the reference (coach.py) is out of scope")
 
 
 def _prep(q, k_self, v_self, ref_k, ref_v, heads, include_self, adain):
+    if ref_k is not None and ref_v is not None and _is_table(ref_k) != _is_table(ref_v):
+        raise TypeError("ref_k and ref_v must both be RefKVTable objects or both be tensors")
     _need_gpu(q, k_self, v_self, ref_k, ref_v)
     _forward_only(q, k_self, v_self, ref_k, ref_v)
     q = _tok(q, heads, "q")
@@ -266,6 +412,11 @@ def shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, s
     inputs and the per-entry parameters only - not on the batch size or position, the other entries, the stream, capture,
     ``return_lse`` / ``return_mass`` or the tuning hook (:func:`shared_attention_plan` shows the plan).  ``split`` is ignored
     in this mode: the plan's K/V-range pieces are part of the result, and their scratch is allocated per call.
+    ``ref_k`` / ``ref_v`` may be :class:`RefKVTable` objects (both or neither): the kernels then take every reference's base
+    address from a device table instead of ``(B, N, L, C)`` tensors - same kernel, same pieces, same bytes as the dense call on
+    ``torch.stack`` of the entries (:func:`attn_probs`, :func:`attn_segment_mass`, :func:`attn_rows` and
+    :func:`shared_attention_kernel_name` take a table as ``ref_k`` too).  With ``valid_refs``, table slots ``n >= valid_refs[b]``
+    are never read.
     """
     q, k_self, v_self, ref_k, ref_v = _prep(q, k_self, v_self, ref_k, ref_v, heads, include_self, adain)
     if out_dtype not in (None, q.dtype, torch.float32):
@@ -497,6 +648,9 @@ def adain_stats(v_self: torch.Tensor, ref_v: torch.Tensor, *, heads: int, eps: f
 
     ``v_self`` (B, L, H*64) supplies the style statistics, ``ref_v`` (B, N, Lr, H*64) the content
     statistics (attn_processors.py:9-10, 244-245: token axis, unbiased std, eps on both)."""
+    if _is_table(ref_v):
+        raise TypeError("adain_stats reads a dense ref_v (ir_adain_stats has no pointer-table form): with a RefKVTable take the affine "
+                        "from cached content statistics (adain_stats_cached / adain_affine_from_partials)")
     _need_gpu(v_self, ref_v)
     _forward_only(v_self, ref_v)
     v_self, ref_v = _tok(v_self, heads, "v_self"), _ref(ref_v, heads, "ref_v")
