@@ -86,7 +86,18 @@ typedef enum ir_dtype { IR_DTYPE_F16 = 0, IR_DTYPE_BF16 = 1 } ir_dtype;
  * i.e. a (B, L, C=H*64) activation is passed as is with sl = C, sh = 64, and the reference's
  * ref_keys[idx] (B, N, L, C) with sn = L*C (pix2pix_turbo.py:265-266): nothing is copied.
  * All base pointers and strides must keep every (row, head) vector 16-byte aligned.
+ * Batch, reference and head strides, and the distances between table entries, may be any such int64 value: every kernel forms
+ * those offsets in 64 bits.  The ROW strides of K and V (ks_sl, vs_sl with IR_FLAG_INCLUDE_SELF; kr_sl, vr_sl with n_refs > 0,
+ * dense or through tables) are limited in the calls that launch or describe the forward (ir_shared_attn_fwd,
+ * ir_time_shared_attn_fwd, ir_shared_attn_kernel_name, ir_shared_attn_plan, ir_shared_attn_workspace_bytes_for): its kernels walk
+ * one (b, segment, head) through a buffer descriptor with signed 32-bit byte offsets, so
+ *     64 * ceil(len / 64) * row_stride * 2 + 128  <=  IR_ATTN_SEG_BYTES_MAX
+ * (the segment's whole 64-key tiles plus one head row; (len - 1) * row_stride * 2 + 128 is the span the descriptor covers).  A
+ * longer segment is refused with IR_ERR_UNSUPPORTED and a message that names the stride and the largest one accepted.  The
+ * read-out entry points (ir_attn_probs, ir_attn_probs_ex, ir_attn_segment_mass, ir_attn_rows) address K through 64-bit pointers
+ * and do not have the limit.
  */
+#define IR_ATTN_SEG_BYTES_MAX 2147483647LL
 typedef struct ir_shared_attn_args {
   uint32_t struct_size; /* = sizeof(ir_shared_attn_args), or sizeof(ir_shared_attn_table_args) when the block is one (below) */
   int32_t dtype;        /* ir_dtype */

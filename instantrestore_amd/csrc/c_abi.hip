@@ -23,7 +23,20 @@ int fail(int code, const char* fmt, ...) {
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 bool stride_ok(int64_t s) { return s >= 0 && (s % 8) == 0; }  // keeps every head row 16-B aligned
 
-int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_out) {
+// The forward kernels walk a K/V segment through a buffer descriptor with 32-bit byte offsets, formed in `int`: the row stride in
+// bytes, (len - 1) * row_bytes + 128 (num_records), 64 * row_bytes per tile, tile * 64 * row_bytes for a piece that starts inside
+// the segment, and the 128-row kernel's offset of the tile behind a run, which reaches the segment's whole tiles:
+// 64 * ceil(len / 64) * row_bytes.  That last one, plus the 128 bytes of a head row, bounds them all; it has to fit a positive int.
+// 0 when it does, else the largest row stride (elements, a multiple of 8) that fits at this length.
+int64_t seg_stride_limit(int32_t len, int64_t sl) {
+  const int64_t rows = ((int64_t)len + IR_KV_TILE - 1) / IR_KV_TILE * IR_KV_TILE;
+  if (rows * sl * 2 + 128 <= IR_ATTN_SEG_BYTES_MAX) return 0;
+  return (IR_ATTN_SEG_BYTES_MAX - 128) / (rows * 2) / 8 * 8;
+}
+
+// `fwd`: the call is (or describes) a launch of the attention forward, whose segment-span limit applies; the read-out entry points
+// (ir_attn_probs*, ir_attn_segment_mass, ir_attn_rows) address K through 64-bit pointers and take any stride
+int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_out, bool fwd) {
   if (a == nullptr) return fail(IR_ERR_INVALID_ARG, "args is NULL");
   // the block up to and including seg_mass (no pointer tables), or ir_shared_attn_table_args; nothing in between
   if (a->struct_size != sizeof(ir_shared_attn_args) && a->struct_size != sizeof(ir_shared_attn_table_args))
@@ -69,6 +82,18 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
                              a->o_sb, a->o_sl, a->o_sh};
   for (int64_t s : strides)
     if (!stride_ok(s)) return fail(IR_ERR_UNSUPPORTED, "stride %lld must be a non-negative multiple of 8 elements", (long long)s);
+  if (fwd) {
+    const struct { const char* name; int64_t sl; int32_t len; bool used; } segs[] = {
+        {"ks_sl", a->ks_sl, a->len_self, inc}, {"vs_sl", a->vs_sl, a->len_self, inc},
+        {"kr_sl", a->kr_sl, a->len_ref, a->n_refs > 0}, {"vr_sl", a->vr_sl, a->len_ref, a->n_refs > 0}};
+    for (const auto& g : segs) {
+      const int64_t most = g.used ? seg_stride_limit(g.len, g.sl) : 0;
+      if (most != 0)
+        return fail(IR_ERR_UNSUPPORTED, "%s %lld: the forward addresses a K/V segment with 32-bit byte offsets, so its whole 64-key tiles and a head row may span "
+                    "at most %lld bytes (IR_ATTN_SEG_BYTES_MAX): at %d keys the row stride is at most %lld elements",
+                    g.name, (long long)g.sl, (long long)IR_ATTN_SEG_BYTES_MAX, g.len, (long long)most);
+    }
+  }
 
   memset(p, 0, sizeof(*p));
   p->q = a->q; p->k_self = a->k_self; p->v_self = a->v_self; p->k_ref = a->k_ref; p->v_ref = a->v_ref;
@@ -183,7 +208,7 @@ const char* ir_last_error_string(void) { return g_err; }
 // valid_refs / seg_mass / pre-scaled flags.  No dispatch rule lives here.
 const char* ir_shared_attn_kernel_name(const ir_shared_attn_args* args) {
   AttnKParams p;
-  if (build_attn_params(args, &p, false) != IR_OK) return "";
+  if (build_attn_params(args, &p, false, true) != IR_OK) return "";
   // the launch takes seg_mass only with an output (need_out); for reporting the by-product counts wherever it is asked for - it
   // decides the 128-row kernel's form and whether the default rule takes that kernel.  Never dereferenced here
   p.seg_cum = (float*)args->seg_mass;
@@ -240,7 +265,7 @@ size_t ir_shared_attn_workspace_bytes(void) {   // the largest remainder split o
 
 size_t ir_shared_attn_workspace_bytes_for(const ir_shared_attn_args* args) {
   AttnKParams p;
-  if (build_attn_params(args, &p, false) != IR_OK) return 0;
+  if (build_attn_params(args, &p, false, true) != IR_OK) return 0;
   if (!batch_invariant(args)) return ir_shared_attn_workspace_bytes();
   return ir_attn_bi_workspace_bytes(bi_plan_of(args, p), p.B);
 }
@@ -250,7 +275,7 @@ int ir_shared_attn_plan(const ir_shared_attn_args* args, ir_shared_attn_plan_inf
   if (plan->struct_size != sizeof(ir_shared_attn_plan_info))
     return fail(IR_ERR_INVALID_ARG, "plan struct_size %u != %zu (ABI mismatch)", plan->struct_size, sizeof(ir_shared_attn_plan_info));
   AttnKParams p;
-  const int rc = build_attn_params(args, &p, false);
+  const int rc = build_attn_params(args, &p, false, true);
   if (rc != IR_OK) return rc;
   if (!batch_invariant(args)) return fail(IR_ERR_INVALID_ARG, "ir_shared_attn_plan reports the IR_FLAG_BATCH_INVARIANT plan (the default dispatch plans per launch)");
   const IrAttnBiPlan pl = bi_plan_of(args, p);
@@ -265,7 +290,7 @@ int ir_shared_attn_plan(const ir_shared_attn_args* args, ir_shared_attn_plan_inf
 
 int ir_shared_attn_fwd(const ir_shared_attn_args* args, void* stream) {
   AttnKParams p;
-  const int rc = build_attn_params(args, &p, true);
+  const int rc = build_attn_params(args, &p, true, true);
   if (rc != IR_OK) return rc;
   return launch_fwd(args, p, (hipStream_t)stream);
 }
@@ -273,7 +298,7 @@ int ir_shared_attn_fwd(const ir_shared_attn_args* args, void* stream) {
 int ir_time_shared_attn_fwd(const ir_shared_attn_args* args, int32_t iters, void* stream, float* ms_per_launch) {
   if (ms_per_launch == nullptr || iters <= 0) return fail(IR_ERR_INVALID_ARG, "iters/ms_per_launch");
   AttnKParams p;
-  const int rc = build_attn_params(args, &p, true);
+  const int rc = build_attn_params(args, &p, true, true);
   if (rc != IR_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   hipEvent_t e0, e1;
@@ -328,7 +353,7 @@ int ir_bench_mfma_stream(int32_t dtype, int32_t zero_operands, int32_t iters, in
 
 int ir_attn_probs_ex(const ir_shared_attn_args* args, void* probs, int32_t kernel, void* stream) {
   AttnKParams p;
-  const int rc = build_attn_params(args, &p, false);
+  const int rc = build_attn_params(args, &p, false, false);
   if (rc != IR_OK) return rc;
   if (probs == nullptr || args->lse == nullptr) return fail(IR_ERR_INVALID_ARG, "probs/lse is NULL");
   if (kernel < IR_PROBS_AUTO || kernel > IR_PROBS_LINES32_K256) return fail(IR_ERR_UNSUPPORTED, "attn_probs kernel %d", kernel);
@@ -345,7 +370,7 @@ int ir_attn_probs(const ir_shared_attn_args* args, void* probs, void* stream) { 
 
 int ir_attn_segment_mass(const ir_shared_attn_args* args, float* mass, void* stream) {
   AttnKParams p;
-  const int rc = build_attn_params(args, &p, false);
+  const int rc = build_attn_params(args, &p, false, false);
   if (rc != IR_OK) return rc;
   if (mass == nullptr || args->lse == nullptr) return fail(IR_ERR_INVALID_ARG, "mass/lse is NULL");
   if (p.q_prescaled) p.scale_log2 = 1.0f;
@@ -359,7 +384,7 @@ int ir_attn_rows(const ir_shared_attn_args* args, const int32_t* row_index, int3
   if ((args->struct_size == sizeof(ir_shared_attn_args) || args->struct_size == sizeof(ir_shared_attn_table_args)) && args->tuning != IR_TUNE_DEFAULT)
     return fail(IR_ERR_UNSUPPORTED, "ir_attn_rows has one kernel: tuning must be 0 (got %d)", args->tuning);
   AttnKParams p;
-  const int rc = build_attn_params(args, &p, false);
+  const int rc = build_attn_params(args, &p, false, false);
   if (rc != IR_OK) return rc;
   if (row_index == nullptr) return fail(IR_ERR_INVALID_ARG, "row_index is NULL");
   if (out == nullptr) return fail(IR_ERR_INVALID_ARG, "out is NULL");
