@@ -51,6 +51,9 @@ def main(argv=None):
     ap.add_argument("--small", action="store_true", help="narrow UNet topology (tests)")
     ap.add_argument("--landmark-maps", action="store_true",
                     help="one more frame that leaves the landmark attention map of every shared layer behind (attention_rows)")
+    ap.add_argument("--ref-weights", default=None,
+                    help="comma-separated weight per reference, e.g. 1,1,0.25,0 (0 masks a reference): prints the top shared layer's "
+                         "per-reference attention masses with and without")
     ap.add_argument("--kv-tables", action="store_true",
                     help="one more cached frame whose reference K/V are pointer tables into the cache entries (assemble_tables: no copy)")
     args = ap.parse_args(argv)
@@ -149,6 +152,24 @@ def main(argv=None):
             top.save_attention_mass = False
             assert float((z3.float() - z4.float()).abs().max()) <= 2e-2 * max(1.0, float(z4.float().abs().max()))
             assert mass.shape[-1] == N + int(top.train_input) and float((mass.sum(-1) - 1).abs().max()) < 2e-3
+        # "Trust photo 2 less, ignore photo 3": per-reference weights ride into the fused kernel as an additive key bias (log w on a
+        # reference's keys; 0 masks it - no attention at all, unlike a zero-filled reference); the masses are the read-back
+        if args.ref_weights:
+            w = torch.tensor([float(t) for t in args.ref_weights.split(",")], device=dev)
+            assert w.numel() == N and bool((w >= 0).all()), f"--ref-weights needs {N} values >= 0"
+            top = [p for p in unet.attn_processors.values() if getattr(p, "self_attn_idx", None) == 8][0]
+            top.save_attention_mass = True
+            kw = {"ref_keys": keys, "ref_values": vals}
+            unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1), cross_attention_kwargs=kw)
+            m0 = top.attention_mass.mean(dim=(1, 2))
+            unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1),
+                 cross_attention_kwargs=dict(kw, ref_weights=w.expand(B, N).contiguous()))
+            m1 = top.attention_mass.mean(dim=(1, 2))
+            top.save_attention_mass = False
+            fmt = lambda m: " ".join(f"{v:.3f}" for v in m.tolist())
+            for b in range(B):
+                print(f"identity {b}: mass [self?] ++ references  unweighted {fmt(m0[b])}  |  weights {args.ref_weights}: {fmt(m1[b])}")
+            assert all(float(m1[:, int(top.train_input) + n].abs().max()) == 0.0 for n in range(N) if float(w[n]) == 0.0)
         # Where do the facial landmarks look (vis_utils.py:88-110)?  Each shared layer is told which query tokens they fall on
         # and leaves the sum of those tokens' head-mean probability rows behind - (B, Lkv) fp32, reshaped to one side x 5*side
         # picture over the degraded image and its references - instead of the (B, H, L, Lkv) tensor of save_self_attentions.

@@ -55,7 +55,7 @@ typedef enum ir_dtype { IR_DTYPE_F16 = 0, IR_DTYPE_BF16 = 1 } ir_dtype;
                                    (tests show the pre-rounding error of the kernel that ships) */
 #define IR_FLAG_BATCH_INVARIANT 8u /* ABI v10, opt-in: the bytes of every output of batch entry b (out, lse, seg_mass) depend on
                                    entry b's own inputs and the per-entry parameters only (dtype, len_q, heads, segment lengths,
-                                   n_refs, INCLUDE_SELF, AdaIN on/off, Q_PRESCALED, valid_refs given or not, OUT_F32) - not on
+                                   n_refs, INCLUDE_SELF, AdaIN on/off, Q_PRESCALED, valid_refs given or not, key_bias given or not, OUT_F32) - not on
                                    the batch size, the entry's position, other entries, the stream, graph capture, the workspace,
                                    whether lse / seg_mass are asked for, IR_ATTN_W128 or the device's CU count.  The kernel and a
                                    fixed cut of every item into K/V-range pieces (merged in piece order) are chosen from those
@@ -99,7 +99,7 @@ typedef enum ir_dtype { IR_DTYPE_F16 = 0, IR_DTYPE_BF16 = 1 } ir_dtype;
  */
 #define IR_ATTN_SEG_BYTES_MAX 2147483647LL
 typedef struct ir_shared_attn_args {
-  uint32_t struct_size; /* = sizeof(ir_shared_attn_args), or sizeof(ir_shared_attn_table_args) when the block is one (below) */
+  uint32_t struct_size; /* = sizeof(ir_shared_attn_args), or sizeof(ir_shared_attn_table_args) / sizeof(ir_shared_attn_bias_args) when the block is one (below) */
   int32_t dtype;        /* ir_dtype */
   uint32_t flags;       /* IR_FLAG_* */
   int32_t batch;        /* B */
@@ -176,6 +176,46 @@ typedef struct ir_shared_attn_table_args {
   const void* const* k_ref_table;
   const void* const* v_ref_table;
 } ir_shared_attn_table_args;
+
+/*
+ * Additive key bias: masks and weights on keys.  A third block, ir_shared_attn_table_args with three fields appended, told apart by
+ * `struct_size` as the table block is (sizeof(ir_shared_attn_bias_args) = the table block's size + 24; every size other than the
+ * three is IR_ERR_INVALID_ARG; IR_ABI_VERSION stays 10).  The tables may be NULL (a dense call); key_bias may be NULL, and then the
+ * call is the call of the shorter blocks in every respect (kernel, plan, bytes).
+ *
+ *   extended key order: [self (iff INCLUDE_SELF)] ++ ref 0 ++ ... ++ ref N-1, lengths len_self and len_ref, PACKED (no tile padding):
+ *                       Lkv = INCLUDE_SELF * len_self + N * len_ref
+ *   bias[b,h,j] = key_bias[b * kb_sb + h * kb_sh + j]            (fp32 on the device; kb_sh = 0: one row shared by all heads)
+ *   P[b,h,i,:]  = softmax_j( scale * <q_i, k_j> + bias[b,h,j] )   (what diffusers' attention_mask is: added to the scaled scores)
+ *   lse         = log sum_j exp(scale * s_j + bias_j), natural units
+ *
+ * A key whose bias is -inf or <= IR_KEY_BIAS_MASKED is MASKED: its probability is exactly 0 and it never moves the kernel's running
+ * reference.  (diffusers' -10000.0 convention; exp(-1e4) is 0 in fp32 and fp64 anyway, so this differs from the literal arithmetic
+ * only where EVERY key of a (b, h) is masked.)  A (b, h) with every key masked gives out = 0 (exact zeros), lse = -inf and all segment
+ * masses 0 - never NaN.  NaN or +inf bias: undefined.  Accuracy: finite unmasked biases of magnitude <= 64 meet the tolerances of the
+ * call without bias; larger finite magnitudes are legal, with an exponent error of 2^-24 * |bias| * log2(e).
+ * The bias is read when the kernel RUNS: a replayed hipGraph follows in-place updates.  Alignment: key_bias, kb_sb and kb_sh are
+ * 4-byte quantities (any float pointer, any element strides >= 0); segment starts need no alignment, len_self and len_ref are arbitrary.
+ * Nothing outside the Lkv floats of a (b, h) row is used.
+ * AdaIN is unchanged by a bias: the affine comes from the statistics over ALL reference tokens, masked or not (the reference's adain()
+ * knows no mask); a masked reference merely takes no attention.
+ * Per-reference weights are a special case: weight w_n on reference n is the bias log(w_n) on every key of its segment (w_n = 0:
+ * masked), with seg_mass as the read-back.  Masked is not zeroed: a zero-filled reference (valid_refs) keeps exp(0) per key.
+ *
+ * Taken by ir_shared_attn_fwd, ir_time_shared_attn_fwd, ir_shared_attn_kernel_name, ir_shared_attn_plan and
+ * ir_shared_attn_workspace_bytes_for.  A call with a bias always runs the software-pipelined 32-row kernel (its BIAS form: the
+ * pre-scaled-Q form with IR_FLAG_Q_PRESCALED or IR_TUNE_PIPE32_PRESCALE_Q, the early-QK form otherwise), at every len_q.
+ * Accepted with it: seg_mass, lse, IR_FLAG_OUT_F32, IR_FLAG_Q_PRESCALED, AdaIN, tables, IR_FLAG_BATCH_INVARIANT, n_refs = 0.
+ * Refused (IR_ERR_UNSUPPORTED): key_bias with valid_refs (the closed form assumes score 0 on the zero suffix); a tuning other than
+ * IR_TUNE_DEFAULT, IR_TUNE_PIPE32_PRESCALE_Q, IR_TUNE_PIPE32_EARLYQK; and ir_attn_probs[_ex], ir_attn_segment_mass, ir_attn_rows
+ * with a non-NULL key_bias (their exp(s - lse) would be wrong without it).
+ */
+typedef struct ir_shared_attn_bias_args {
+  ir_shared_attn_table_args t;   /* t.args.struct_size = sizeof(ir_shared_attn_bias_args); tables may be NULL (dense call) */
+  const float* key_bias;         /* fp32 on the device, or NULL (= a call without bias, same as the shorter blocks) */
+  int64_t kb_sb, kb_sh;          /* strides in fp32 elements over batch and head; kb_sh = 0: one row shared by all heads */
+} ir_shared_attn_bias_args;
+#define IR_KEY_BIAS_MASKED (-1.0e4f)
 
 /* values of ir_shared_attn_args.tuning (csrc/shared_attn_fwd.hip: kAttnVariants has one row per value - kernel family, form, what
  * it takes; ir_attn_choose is the dispatch) */

@@ -18,6 +18,7 @@ ABI_VERSION = 10
 IR_DTYPE_F16, IR_DTYPE_BF16 = 0, 1
 IR_FLAG_INCLUDE_SELF, IR_FLAG_Q_PRESCALED, IR_FLAG_OUT_F32 = 1, 2, 4
 IR_FLAG_BATCH_INVARIANT = 8   # ABI v10
+IR_KEY_BIAS_MASKED = -1.0e4   # a key whose bias is -inf or <= this is masked (probability exactly 0)
 IR_ROWS_NONE, IR_ROWS_HEAD_MEAN, IR_ROWS_MAP = 0, 1, 2   # the `reduce` argument of ir_attn_rows
 IR_LIN_BATCH_INVARIANT = 16   # ABI v10: the kernel selector of ir_linear_fwd_ex / ir_linear_fwd_stats_ex / ir_linear_kernel_for_ex
 
@@ -44,6 +45,13 @@ class SharedAttnTableArgs(SharedAttnArgs):
     and tells the two apart by ``struct_size``"""
 
     _fields_ = [("k_ref_table", vp), ("v_ref_table", vp)]
+
+
+class SharedAttnBiasArgs(SharedAttnTableArgs):
+    """mirror of ``ir_shared_attn_bias_args``: the table block (tables NULL: a dense call) with the additive key bias appended -
+    fp32 on the device, strides in fp32 elements over batch and head (``kb_sh = 0``: one row shared by all heads)"""
+
+    _fields_ = [("key_bias", vp), ("kb_sb", i64), ("kb_sh", i64)]
 
 
 class SharedAttnPlan(C.Structure):

@@ -8,7 +8,7 @@ Appendix A): the projection layers, the head split / merge helpers, the score he
 ``processor`` plug point.  It is host plumbing (plain torch ``nn.Linear``), not the hot path:
 the fused HIP kernels are reached from the processors, never from here.
 
-``get_attention_scores`` exists because third-party processors (and the reference's own, when
+``get_attention_scores`` and ``prepare_attention_mask`` exist because third-party processors (and the reference's own, when
 they are driven through this host to produce golden vectors) call it; the processors of this
 package do not.
 """
@@ -112,9 +112,19 @@ class Attention(nn.Module):
         return scores.softmax(dim=-1).to(dtype)
 
     def prepare_attention_mask(self, attention_mask, target_length, batch_size, out_dim: int = 3):
+        """diffusers 0.24's published behaviour for a mask whose last axis already equals ``target_length``: ``out_dim == 3`` repeats
+        a mask of fewer than ``batch_size * heads`` rows over the heads (``repeat_interleave`` on axis 0), ``out_dim == 4`` inserts a
+        head axis and repeats along it.  A mask of any other length raises: upstream pads it there (by ``target_length`` zeros,
+        whatever it lacks), a quirk this host does not reproduce."""
         if attention_mask is None:
             return None
-        raise NotImplementedError(
-            "attention masks never occur on the InstantRestore path (pix2pix_turbo.py:317-326 "
-            "calls the UNet without one); this host does not prepare them"
-        )
+        if attention_mask.shape[-1] != target_length:
+            raise NotImplementedError(
+                f"attention_mask covers {attention_mask.shape[-1]} keys, target_length is {target_length}: this host prepares only masks "
+                "that already have the target length (diffusers 0.24 pads the others; that quirk is not reproduced)")
+        if out_dim == 3:
+            if attention_mask.shape[0] < batch_size * self.heads:
+                attention_mask = attention_mask.repeat_interleave(self.heads, dim=0)
+        elif out_dim == 4:
+            attention_mask = attention_mask.unsqueeze(1).repeat_interleave(self.heads, dim=1)
+        return attention_mask

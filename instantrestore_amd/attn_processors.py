@@ -19,7 +19,8 @@ reference's own path rounds the scores to 16 bit before its softmax, which this 
 
 The processors own no parameters and no buffers (the reference's checkpoints are loaded with
 ``strict=True``, test.py:47-50).  They never fall back to torch math: CPU tensors, fp32
-activations outside autocast, attention masks and missing libraries raise.
+activations outside autocast, per-query attention masks and missing libraries raise.  A per-key ``attention_mask`` (and the
+``ref_weights`` / ``ref_token_keep`` kwargs of the shared layers) becomes the fused kernel's additive key bias (``_mask_bias``).
 
 Batch-invariant mode (ABI v10; :func:`set_batch_invariant`, or the plain attribute ``batch_invariant`` of
 :class:`SharedAttnProcessor` / :class:`AttnProcessor`): every GEMM, statistics pass and attention of a processor then runs
@@ -64,7 +65,7 @@ def adain(content_features: torch.Tensor, style_mean: torch.Tensor, style_std: t
 # shared prologue / epilogue of every processor (attn_processors.py:42-70, 84-97)
 # ------------------------------------------------------------------------------------------
 class _Prepared:
-    __slots__ = ("hidden", "encoder", "residual", "ndim", "shape4")
+    __slots__ = ("hidden", "encoder", "residual", "ndim", "shape4", "mask")
 
 
 def _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb) -> _Prepared:
@@ -78,14 +79,67 @@ def _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb) 
         st.shape4 = hidden_states.shape
         bsz, ch, hh, ww = st.shape4
         hidden_states = hidden_states.view(bsz, ch, hh * ww).transpose(1, 2)
-    ref = hidden_states if encoder_hidden_states is None else encoder_hidden_states
-    if attn.prepare_attention_mask(attention_mask, ref.shape[1], ref.shape[0]) is not None:
-        raise NotImplementedError("attention masks do not occur on the InstantRestore path")
+    # an attention mask becomes the fused kernel's additive key bias (_mask_bias, once the processor knows its key axis).  The
+    # host's prepare_attention_mask is not called: its target length is the self / encoder length, and a shared layer's mask
+    # runs over the extended key axis
+    st.mask = attention_mask
     if attn.group_norm is not None:
         hidden_states = attn.group_norm(hidden_states.transpose(1, 2)).transpose(1, 2)
     st.hidden = hidden_states
     st.encoder = encoder_hidden_states
     return st
+
+
+def _mask_bias(mask, batch: int, heads: int, lkv: int, len_self: int, shared: bool) -> Optional[torch.Tensor]:
+    """``attention_mask`` as the additive fp32 key bias of ``ops.shared_attention``: ``(B, Lkv)``, ``(B, 1, Lkv)`` (what diffusers'
+    UNet hands the cross-attention layers for padded text, a bias of -10000) or ``(B * H, 1, Lkv)`` (the same after
+    ``prepare_attention_mask``'s ``repeat_interleave`` over heads).  The reference adds it to the scaled scores
+    (``get_attention_scores``: ``baddbmm`` with ``beta = 1``); here it rides into the kernel, nothing is added on the host."""
+    if mask is None:
+        return None
+    if mask.dtype == torch.bool or not mask.is_floating_point():
+        raise ValueError(f"attention_mask must be additive (floating point: 0 keeps, -10000 / -inf masks), got {mask.dtype}")
+    if mask.dim() == 3:
+        if mask.shape[1] != 1:
+            raise NotImplementedError(f"attention_mask {tuple(mask.shape)}: a query axis of {mask.shape[1]} - per-query masks are not supported "
+                                      "(the fused kernel takes one bias per key)")
+        mask = mask[:, 0]
+    elif mask.dim() != 2:
+        raise ValueError(f"attention_mask must be (B, Lkv), (B, 1, Lkv) or (B * H, 1, Lkv), got {tuple(mask.shape)}")
+    if mask.shape[-1] != lkv:
+        if shared and mask.shape[-1] == len_self:
+            raise ValueError(f"attention_mask covers {len_self} keys, the self length, but this shared layer attends over {lkv} keys "
+                             "([self] ++ references): pass a mask of the extended length (the reference itself would fail in baddbmm here)")
+        raise ValueError(f"attention_mask covers {mask.shape[-1]} keys, the layer attends over {lkv}")
+    mask = mask.to(torch.float32)
+    if mask.shape[0] == batch:
+        return mask
+    if mask.shape[0] != batch * heads:
+        raise ValueError(f"attention_mask has {mask.shape[0]} rows for a batch of {batch} with {heads} heads")
+    mask = mask.view(batch, heads, lkv)
+    # identical per-head rows collapse to one shared row only where that is known without a device sync (an expanded view)
+    return mask[:, 0] if mask.stride(1) == 0 else mask
+
+
+# bias rows of ``ref_weights`` / ``ref_token_keep``, built once per (kwargs identity and version, key-axis geometry): the nine shared
+# layers of a step have three geometries, so they build three rows.  In-place changes of the tensors bump their version.
+_BIAS_ROWS: dict = {}
+_BIAS_ROWS_MAX = 8
+
+
+def _ref_bias_row(ref_weights, ref_token_keep, batch: int, len_self: int, n_refs: int, len_ref: int, include_self: bool, device):
+    if ref_weights is None and ref_token_keep is None:
+        return None
+    ver = lambda t: (id(t), getattr(t, "_version", None)) if t is not None else None
+    key = (ver(ref_weights), ver(ref_token_keep), batch, len_self, n_refs, len_ref, include_self, str(device))
+    hit = _BIAS_ROWS.get(key)
+    if hit is not None and hit[0] is ref_weights and hit[1] is ref_token_keep:
+        return hit[2]
+    row = _ops.key_bias(batch, len_self, n_refs, len_ref, include_self, ref_weights=ref_weights, ref_token_keep=ref_token_keep, device=device)
+    while len(_BIAS_ROWS) >= _BIAS_ROWS_MAX:
+        _BIAS_ROWS.pop(next(iter(_BIAS_ROWS)))
+    _BIAS_ROWS[key] = (ref_weights, ref_token_keep, row)
+    return row
 
 
 def _kv_source(attn, st: _Prepared) -> torch.Tensor:
@@ -369,7 +423,9 @@ class AttnProcessor(nn.Module):
                 self.ready = torch.cuda.Event()
                 self.ready.record(self.stream)
 
-    def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None):
+    def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
+                ref_weights=None, ref_token_keep=None):
+        # ref_weights / ref_token_keep: accepted and ignored (no references here), like ref_valid elsewhere
         st = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
         self.is_self_attn = encoder_hidden_states is None
         group = self.stop_after_capture
@@ -388,6 +444,9 @@ class AttnProcessor(nn.Module):
         _same_16bit(query, key, value)
         kw = {"q_prescaled": True} if presc else {}
         kw.update(_bi_kw(bi))
+        bias = _mask_bias(st.mask, query.shape[0], attn.heads, key.shape[1], key.shape[1], False)
+        if bias is not None:
+            kw["key_bias"] = bias
         tokens = _ops.shared_attention(query, key, value, heads=attn.heads, scale=attn.scale, include_self=True, **kw)
         return _epilogue(attn, st, tokens, bi)
 
@@ -413,7 +472,7 @@ class FaceIDAttnProcessor(nn.Module):
         self.is_self_attn = None
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
-                ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None):
+                ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None, ref_weights=None, ref_token_keep=None):
         # ref_* accepted and ignored, like the reference: the host forwards ONE cross_attention_kwargs dict to every processor
         # (unet.py / diffusers), so whatever the harvest hands SharedAttnProcessor (ref_valid included) arrives here too
         st = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
@@ -422,7 +481,9 @@ class FaceIDAttnProcessor(nn.Module):
         src = self.face_projection(_kv_source(attn, st))
         key, value = self.to_k_face_embed(src), self.to_v_face_embed(src)
         _same_16bit(query, key, value)
-        tokens = _ops.shared_attention(query, key, value, heads=attn.heads, scale=attn.scale, include_self=True)
+        bias = _mask_bias(st.mask, query.shape[0], attn.heads, key.shape[1], key.shape[1], False)
+        kw = {"key_bias": bias} if bias is not None else {}
+        tokens = _ops.shared_attention(query, key, value, heads=attn.heads, scale=attn.scale, include_self=True, **kw)
         return _epilogue(attn, st, tokens)
 
 
@@ -473,8 +534,14 @@ class SharedAttnProcessor(nn.Module):
         self.attention_rows = None
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
-                ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None):
-        """``ref_valid`` (optional, round 5): int32 ``(B,)`` device tensor from the harvest (``kv_harvest`` ``with_valid``) when
+                ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None, ref_weights=None, ref_token_keep=None):
+        """``attention_mask``: additive, ``(B, Lkv)``, ``(B, 1, Lkv)`` or ``(B * H, 1, Lkv)`` over this layer's key axis (with references: the
+        extended one) - the fused kernel's key bias.  ``ref_weights`` ``(B, N)`` >= 0 and ``ref_token_keep`` (bool ``(B, N, len_ref)`` or
+        ``(B, N, S, S)``), shared layers only (ignored elsewhere, as ``ref_valid`` is): ``ops.key_bias`` turns them into the bias -
+        ``log w`` on a reference's keys, 0 / dropped tokens MASKED (no attention at all, unlike a zero-filled reference).  AdaIN
+        statistics stay those of every reference token.  ``save_attention_mass`` reads the effect back; ``save_self_attentions`` /
+        ``attention_rows_index`` with a bias raise (the read-out kernels do not take the bias yet).
+        ``ref_valid`` (optional, round 5): int32 ``(B,)`` device tensor from the harvest (``kv_harvest`` ``with_valid``) when
         it zero-filled references ``n >= valid[b]`` (pix2pix_turbo.py:269-273): the kernel then closes those all-zero segments
         analytically instead of walking them (ABI v8 ``valid_refs``).  Same output; the tokens keep their exp(0) weight."""
         st = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
@@ -553,6 +620,19 @@ class SharedAttnProcessor(nn.Module):
         kw.update(_bi_kw(bi))
         if shared and ref_valid is not None:
             kw["valid_refs"] = ref_valid
+        len_self = key.shape[1]
+        lkv = (len_self if include_self else 0) + (ref_k.shape[1] * ref_k.shape[2] if shared else 0)
+        bias = _mask_bias(st.mask, query.shape[0], attn.heads, lkv, len_self, shared)
+        if shared:
+            row = _ref_bias_row(ref_weights, ref_token_keep, query.shape[0], len_self, ref_k.shape[1], ref_k.shape[2], include_self, query.device)
+            if row is not None:
+                bias = row if bias is None else (bias + (row if bias.dim() == 2 else row.unsqueeze(1)))
+        if bias is not None:
+            if want_probs or rows_index is not None:
+                raise NotImplementedError("save_self_attentions / attention_rows_index together with an attention mask, ref_weights or "
+                                          "ref_token_keep: ir_attn_probs and ir_attn_rows do not take the key bias yet (follow-up); "
+                                          "save_attention_mass honours it")
+            kw["key_bias"] = bias
         # the masses are a by-product of the attention launch itself (ABI v9 ``seg_mass``: the kernels hold the row sums at every
         # segment boundary): no second pass over Q and K
         res = _ops.shared_attention(query, key, value, ref_k, ref_v, heads=attn.heads, scale=attn.scale,

@@ -36,13 +36,19 @@ int64_t seg_stride_limit(int32_t len, int64_t sl) {
 
 // `fwd`: the call is (or describes) a launch of the attention forward, whose segment-span limit applies; the read-out entry points
 // (ir_attn_probs*, ir_attn_segment_mass, ir_attn_rows) address K through 64-bit pointers and take any stride
+bool attn_block_size_ok(uint32_t n) {
+  return n == sizeof(ir_shared_attn_args) || n == sizeof(ir_shared_attn_table_args) || n == sizeof(ir_shared_attn_bias_args);
+}
+
 int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_out, bool fwd) {
   if (a == nullptr) return fail(IR_ERR_INVALID_ARG, "args is NULL");
-  // the block up to and including seg_mass (no pointer tables), or ir_shared_attn_table_args; nothing in between
-  if (a->struct_size != sizeof(ir_shared_attn_args) && a->struct_size != sizeof(ir_shared_attn_table_args))
-    return fail(IR_ERR_INVALID_ARG, "struct_size %u != %zu or %zu (ABI mismatch)", a->struct_size, sizeof(ir_shared_attn_args),
-                sizeof(ir_shared_attn_table_args));
-  const ir_shared_attn_table_args* ta = a->struct_size == sizeof(ir_shared_attn_table_args) ? (const ir_shared_attn_table_args*)a : nullptr;
+  // the block up to and including seg_mass (no pointer tables), ir_shared_attn_table_args, or ir_shared_attn_bias_args; nothing in between
+  if (!attn_block_size_ok(a->struct_size))
+    return fail(IR_ERR_INVALID_ARG, "struct_size %u != %zu, %zu or %zu (ABI mismatch)", a->struct_size, sizeof(ir_shared_attn_args),
+                sizeof(ir_shared_attn_table_args), sizeof(ir_shared_attn_bias_args));
+  const ir_shared_attn_table_args* ta = a->struct_size >= sizeof(ir_shared_attn_table_args) ? (const ir_shared_attn_table_args*)a : nullptr;
+  const ir_shared_attn_bias_args* ba = a->struct_size == sizeof(ir_shared_attn_bias_args) ? (const ir_shared_attn_bias_args*)a : nullptr;
+  const float* kbias = ba != nullptr ? ba->key_bias : nullptr;
   const void* const* ktab = ta != nullptr ? ta->k_ref_table : nullptr;
   const void* const* vtab = ta != nullptr ? ta->v_ref_table : nullptr;
   const bool tables = ktab != nullptr;
@@ -74,6 +80,19 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
   if (a->adain_a != nullptr && a->n_refs == 0) return fail(IR_ERR_INVALID_ARG, "AdaIN affine without references");
   if (a->valid_refs != nullptr && (reinterpret_cast<uintptr_t>(a->valid_refs) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "valid_refs must be 4-byte aligned");
   if (a->seg_mass != nullptr && (reinterpret_cast<uintptr_t>(a->seg_mass) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "seg_mass must be 4-byte aligned");
+  if (kbias != nullptr) {
+    if (!fwd)
+      return fail(IR_ERR_UNSUPPORTED, "key_bias: ir_attn_probs[_ex], ir_attn_segment_mass and ir_attn_rows do not take a key bias yet (their exp(s - lse) would "
+                  "leave it out); the forward's seg_mass by-product does");
+    if ((reinterpret_cast<uintptr_t>(kbias) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "key_bias must be 4-byte aligned");
+    if (ba->kb_sb < 0 || ba->kb_sh < 0) return fail(IR_ERR_INVALID_ARG, "key_bias strides kb_sb %lld, kb_sh %lld must be >= 0", (long long)ba->kb_sb, (long long)ba->kb_sh);
+    if (a->valid_refs != nullptr && a->n_refs > 0)
+      return fail(IR_ERR_UNSUPPORTED, "key_bias together with valid_refs: the closed form of the zero-filled suffix assumes score 0 on its keys (pass "
+                  "valid_refs = NULL and let the kernel walk the zeros, or mask those references in the bias)");
+    if (a->tuning != IR_TUNE_DEFAULT && a->tuning != IR_TUNE_PIPE32_PRESCALE_Q && a->tuning != IR_TUNE_PIPE32_EARLYQK)
+      return fail(IR_ERR_UNSUPPORTED, "key_bias: tuning %d has no BIAS form (IR_TUNE_DEFAULT, IR_TUNE_PIPE32_PRESCALE_Q or IR_TUNE_PIPE32_EARLYQK: the "
+                  "32-row kernel runs every call with a key bias)", a->tuning);
+  }
   const void* ptrs[] = {a->q, a->k_self, a->v_self, a->k_ref, a->v_ref, a->out, a->adain_a, a->adain_b};
   for (const void* q : ptrs)
     if (q != nullptr && !aligned16(q)) return fail(IR_ERR_UNSUPPORTED, "pointer %p is not 16-byte aligned", q);
@@ -113,6 +132,7 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
     p->kr_sb = p->vr_sb = (int64_t)a->n_refs * 4; p->kr_sn = p->vr_sn = 4;
   }
   p->include_self = inc ? 1 : 0;
+  if (kbias != nullptr) { p->key_bias = kbias; p->kb_sb = ba->kb_sb; p->kb_sh = ba->kb_sh; }
   p->q_prescaled = (a->flags & IR_FLAG_Q_PRESCALED) ? 1 : 0;
   p->out_f32 = (a->flags & IR_FLAG_OUT_F32) ? 1 : 0;
   if (p->q_prescaled && ((a->tuning >> 5) != 0 || !ir_attn_variant(a->tuning)->presc_q))   // (the availability test above found the row)
@@ -169,6 +189,7 @@ AttnKParams batch_slice(const AttnKParams& p, int b0, int nb) {
   if (p.lse != nullptr) q.lse = p.lse + (int64_t)b0 * p.H * p.Lq;
   if (p.seg_cum != nullptr) q.seg_cum = p.seg_cum + (int64_t)b0 * p.H * p.Lq * p.nseg_out;
   if (p.valid != nullptr) q.valid = p.valid + b0;
+  if (p.key_bias != nullptr) q.key_bias = p.key_bias + (int64_t)b0 * p.kb_sb;
   return q;
 }
 
@@ -250,8 +271,9 @@ const char* ir_shared_attn_kernel_name(const ir_shared_attn_args* args) {
   }
   if (head == nullptr) return "shared_attn_fwd (tuning variant)";
   static thread_local char name[256];
-  int n = snprintf(name, sizeof(name), "%s%s%s%s%s>", head, fold ? fold_text : "", forms && p.valid != nullptr ? ", zero suffix in closed form" : "",
-                   forms && p.seg_cum != nullptr ? ", segment masses" : "", bi && c.family == IR_FAM_W128_FORMS ? ", forms" : "");
+  int n = snprintf(name, sizeof(name), "%s%s%s%s%s%s>", head, fold ? fold_text : "", forms && p.valid != nullptr ? ", zero suffix in closed form" : "",
+                   forms && p.seg_cum != nullptr ? ", segment masses" : "", bi && c.family == IR_FAM_W128_FORMS ? ", forms" : "",
+                   p.key_bias != nullptr ? ", key bias (reference follows every max)" : "");
   if (bi) {   // the plan's cut; the name does not change with seg_mass (the output does not either)
     const IrAttnBiPlan pl = bi_plan_of(args, p);
     snprintf(name + n, sizeof(name) - n, " [batch-invariant: %d piece%s per %d-row item]", pl.pieces, pl.pieces > 1 ? "s" : "", pl.rows);
@@ -381,7 +403,7 @@ int ir_attn_segment_mass(const ir_shared_attn_args* args, float* mass, void* str
 
 int ir_attn_rows(const ir_shared_attn_args* args, const int32_t* row_index, int32_t n_rows, int32_t reduce, void* out, void* stream) {
   if (args == nullptr) return fail(IR_ERR_INVALID_ARG, "args is NULL");
-  if ((args->struct_size == sizeof(ir_shared_attn_args) || args->struct_size == sizeof(ir_shared_attn_table_args)) && args->tuning != IR_TUNE_DEFAULT)
+  if (attn_block_size_ok(args->struct_size) && args->tuning != IR_TUNE_DEFAULT)
     return fail(IR_ERR_UNSUPPORTED, "ir_attn_rows has one kernel: tuning must be 0 (got %d)", args->tuning);
   AttnKParams p;
   const int rc = build_attn_params(args, &p, false, false);

@@ -68,6 +68,11 @@ struct AttnKParams {
   // segment's base address there (ir_ref_entry).  No kernel argument of its own for the tables: the attention kernels have no
   // SGPRs to spare.  Read by the kernels when they run, never by the dispatch or the plans
   int ref_tables;     // 0/1
+  // additive key bias (ir_shared_attn_bias_args): bias[b,h,j] = key_bias[b * kb_sb + h * kb_sh + j] over the packed extended key
+  // axis, added to scale * <q,k> before the softmax; nullptr: none.  Read by the BIAS forms of the 32-row kernel only
+  // (shared_attn_fwd_pipe_bias.hip); appended, so no other kernel's arguments move
+  const float* key_bias;
+  int64_t kb_sb, kb_sh;
 };
 
 // The base address (head 0, token 0) of a reference segment from `at` = k_ref + b * kr_sb + n * kr_sn: `at` itself in the dense
@@ -172,6 +177,7 @@ struct ZeroRefsKParams {
 // launchers (defined next to their kernels); dtype: 0 = f16, 1 = bf16. Return hipError_t.
 hipError_t ir_launch_shared_attn_fwd(const AttnKParams& p, int dtype, int variant, hipStream_t s);
 hipError_t ir_launch_shared_attn_fwd_pipe(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s);
+hipError_t ir_launch_shared_attn_fwd_pipe_bias(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s);   // key_bias: PRESC / EARLYQK (shared_attn_fwd_pipe_bias.hip)
 hipError_t ir_launch_shared_attn_fwd_pipe_abl(const AttnKParams& p, int abl, hipStream_t s);
 hipError_t ir_launch_shared_attn_combine(const AttnKParams& p, int dtype, int qb, int rem, hipStream_t s);
 hipError_t ir_launch_shared_attn_fwd_w64(const AttnKParams& p, int dtype, hipStream_t s);

@@ -497,6 +497,10 @@ __global__ void __launch_bounds__(256) seg_mass_finish_kernel(float* __restrict_
   if (r >= rows) return;
   float* c = cum + r * S;
   const float tot = c[S - 1];
+  if (tot == -INFINITY) {   // key bias: every key of the row masked - no mass anywhere (c - tot would not be a number)
+    for (int s = 0; s < S; ++s) c[s] = 0.f;
+    return;
+  }
   float prev = 0.f;
   for (int s = 0; s < S; ++s) {
     const float e = s == S - 1 ? 1.f : __expf(c[s] - tot);
@@ -515,7 +519,8 @@ hipError_t ir_launch_seg_mass_finish(const AttnKParams& p, hipStream_t s) {
 // ABI v10 batch-invariant plan (IR_FLAG_BATCH_INVARIANT).  The default rules above read the batch size (items512, the remainder
 // split of the last round of workgroup slots) and process state (IR_ATTN_W128); this one reads per-item parameters only:
 //   kernel: the 128-row kernel (its FORMS instantiation, which carries valid_refs and seg_mass at run time) for pre-scaled Q, whole
-//           tiles and Lq >= 4096; the 8-wave 64-row kernel for other Lq >= 4096 calls; the pipelined 32-row kernel below that;
+//           tiles and Lq >= 4096; the 8-wave 64-row kernel for other Lq >= 4096 calls; the pipelined 32-row kernel below that
+//           (and at every Lq when a key bias is given - one more per-entry parameter: only that kernel has the BIAS form);
 //   pieces: every item of a call WITH references (n_refs > 0: the shared layers, whose batch is the identities) is cut into k
 //           K/V-range pieces (tile boundaries from the item's own tile count) merged by the combine kernel in piece order;
 //           k = ceil(256 / items of ONE batch entry) - one entry fills the 256 CUs of an MI355X (a constant, not the device's count) -
@@ -524,6 +529,7 @@ hipError_t ir_launch_seg_mass_finish(const AttnKParams& p, hipStream_t s) {
 //           and cutting it would cost fp32 partials of its whole K/V walk (7 pieces of 1280 items at cfg 2's 64x64 class: 1.2 GB per
 //           launch) for no fill.  k = 1: whole items, no merge pass, no workspace.
 IrAttnChoice ir_attn_choose_bi(const AttnKParams& p) {
+  if (p.key_bias != nullptr) return {IR_FAM_PIPE32, p.q_prescaled ? IR_PIPE_PRESC : IR_PIPE_EARLYQK};   // key bias: the 32-row kernel's BIAS forms, at every Lq
   if (p.Lq >= 4096) return {p.q_prescaled && ir_attn_w128_supports(p) ? IR_FAM_W128_FORMS : IR_FAM_W64X8, IR_PIPE_NONE};
   return {IR_FAM_PIPE32, p.q_prescaled ? IR_PIPE_PRESC : IR_PIPE_EARLYQK};
 }
@@ -556,6 +562,8 @@ IrAttnChoice ir_attn_choose(const AttnKParams& p, int tuning) {
   if (p.out_f32 && (abl || v->family == IR_FAM_DEV)) return {IR_FAM_REFUSED, IR_PIPE_NONE};
   if (abl || v->id == IR_TUNE_W64_ABL_FIRST) return {IR_FAM_DEV, IR_PIPE_NONE};
 #endif
+  // key bias: the 32-row kernel's BIAS forms at every Lq (c_abi.hip admits IR_TUNE_DEFAULT, _PIPE32_PRESCALE_Q and _PIPE32_EARLYQK)
+  if (p.key_bias != nullptr) return {IR_FAM_PIPE32, p.q_prescaled || v->form == IR_PIPE_PRESC ? IR_PIPE_PRESC : IR_PIPE_EARLYQK};
   IrAttnChoice c = {v->family, v->form};
   if (v->id == IR_TUNE_DEFAULT) {
     if (p.q_prescaled && ir_attn_default_is_w128(p)) c = {IR_FAM_W128, IR_PIPE_NONE};
@@ -584,7 +592,7 @@ static hipError_t launch_choice(const AttnKParams& p, int dtype, IrAttnChoice c,
     case IR_FAM_W128_FORMS: return ir_launch_shared_attn_fwd_w128_forms(p, dtype, s);
     case IR_FAM_W64X8: return ir_launch_shared_attn_fwd_w64x8(p, dtype, s);
     case IR_FAM_W64X4: return ir_launch_shared_attn_fwd_w64(p, dtype, s);
-    case IR_FAM_PIPE32: return ir_launch_shared_attn_fwd_pipe(p, dtype, c.form, s);
+    case IR_FAM_PIPE32: return p.key_bias != nullptr ? ir_launch_shared_attn_fwd_pipe_bias(p, dtype, c.form, s) : ir_launch_shared_attn_fwd_pipe(p, dtype, c.form, s);
     default: return hipErrorInvalidValue;
   }
 }

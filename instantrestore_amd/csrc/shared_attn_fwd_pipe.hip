@@ -23,6 +23,7 @@
 
 #include <stdlib.h>
 
+#include "../../include/instantrestore_hip.h"   // IR_KEY_BIAS_MASKED
 #include "ir_common.h"
 #include "ir_kernels.h"
 
@@ -47,6 +48,13 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
   // tile that outgrew it is formed again from its K tile, which therefore stays in LDS one step longer: K ring of 3
   constexpr bool CHK = (ABL & 8192) != 0;
   static_assert(!CHK || (ABL & 2048), "the check after the exponentials needs scores that already carry the reference");
+  // BIAS (ir_shared_attn_bias_args.key_bias; the PRESC and EARLYQK forms, instantiated in shared_attn_fwd_pipe_bias.hip): an additive
+  // fp32 term per key, in the exp2 domain, enters every tile's scores through the C operand of its first QK^T MFMA.  The S
+  // registers of a tile are free between its P.V and the QK^T that refills them, so the 32 bias values a lane needs of tile t+2 are
+  // fetched INTO them at the end of step t (one tile ahead of their use, no registers of their own) and turned into the C operand in
+  // place.  A masked key (-inf or <= IR_KEY_BIAS_MASKED) is -inf in the C operand: -inf leaves the matrix pipe, before any row max.
+  constexpr bool BIAS = (ABL & 16384) != 0;
+  static_assert(!BIAS || (!CHK && (ABL & 256) == 0 && (ABL & 128) != 0 && ((ABL & 2048) != 0) != ((ABL & 4096) != 0)), "the key bias is built into the PRESC and EARLYQK forms only");
   constexpr int KRING = CHK ? 3 : 2;
   constexpr int K_OFF = 0;                       // K ring: 2 tiles (3 with CHK)
   constexpr int V_OFF = KRING * TILE_BYTES;      // V ring: 3 tiles
@@ -218,6 +226,25 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
     }
   };
 
+  // ---- key bias stream (BIAS) ------------------------------------------------------------------
+  // One buffer descriptor over the Lkv floats of this (b, h) row: a load past the row's end returns 0 and faults nowhere.  A ragged
+  // tile's slots behind the segment's last key read the NEXT segment's bias (or that 0); the ragged-tail -inf of step (1) replaces
+  // them.  The whole offset goes through the VGPR: only that one is range-checked.  Register r of c0 holds key (r & 3) + 8 (r >> 2)
+  // + 4 hi of the tile (c1: + 32): eight groups of four consecutive keys, starting at key 8 g + 4 hi - no alignment beyond 4 bytes.
+  __amdgpu_buffer_rsrc_t brs;
+  if (BIAS) brs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.key_bias + (int64_t)b * p.kb_sb + (int64_t)h * p.kb_sh), 0, p.lkv * 4, 0x00020000);
+  auto bias_load = [&](f32x16& a0, f32x16& a1) {   // raw bias of the tile at the prefetch stream's position (seg, t0) -> a0, a1
+    const int key0 = ((p.include_self && seg == 0) ? 0 : p.include_self * p.Ls + (seg - p.include_self) * p.Lr) + t0 * KVB;
+    const unsigned vo = (unsigned)(key0 * 4) + (unsigned)(hi * 16);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(brs, vo + 32 * g, 0, 0);
+      const u32x4 y = __builtin_amdgcn_raw_buffer_load_b128(brs, vo + 128 + 32 * g, 0, 0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { a0[4 * g + i] = __uint_as_float(x[i]); a1[4 * g + i] = __uint_as_float(y[i]); }
+    }
+  };
+
   // ---- state ---------------------------------------------------------------------------------
   f32x16 o0, o1;
 #pragma unroll
@@ -227,7 +254,13 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
   float m_ot = -INFINITY;                   // FOLD: the running max the LDS total is scaled to
   float m_run = PRESC ? 0.f : -INFINITY;    // PRESC: the reference lives in the exp2 domain and starts at 0
   const float c2 = p.scale_log2;
-  const float lazy_thr = PRESC ? 6.0f : 6.0f / c2;  // LAZYMAX: score growth that forces a rescale
+  // LAZYMAX: score growth that forces a rescale.  BIAS: none - the reference follows every growth of a row's max, so the key that
+  // carries a row has probability exactly 1 and takes no 16-bit rounding of its own (with the lazy reference two of 118 bf16
+  // comparisons of tests/test_gpu_key_bias.py left the regression bound: 1.01 and 1.06 of it, 0.53 with the exact reference)
+  const float lazy_thr = BIAS ? 0.f : (PRESC ? 6.0f : 6.0f / c2);
+  bool started = false;                     // BIAS + PRESC: a tile with an unmasked key has set the reference (wave-uniform: the bias has no query axis)
+  // BIAS: loaded bias -> exponent units of the scores as they leave the matrix pipe (PRESC: exp2 domain; else raw scores, scaled by c2 later)
+  const float kb_mul = (ABL & 2048) != 0 ? 1.4426950408889634f : 1.4426950408889634f / c2;
   f32x16 mneg;                              // PRESC: -m_run in every register: C operand of the first QK^T MFMA
 #pragma unroll
   for (int r = 0; r < 16; ++r) mneg[r] = 0.f;
@@ -257,6 +290,20 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
     }
   };
   auto qk_mfma = [&](f32x16& s0, f32x16& s1, const v8 (&kf0)[4], const v8 (&kf1)[4]) {
+    if (BIAS) {   // s0, s1 arrive holding the tile's raw bias: C operand = bias in exponent units (- the reference), -inf on masked keys
+      const float ref = PRESC ? -m_run : 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        s0[r] = s0[r] <= IR_KEY_BIAS_MASKED ? -INFINITY : __builtin_fmaf(s0[r], kb_mul, ref);
+        s1[r] = s1[r] <= IR_KEY_BIAS_MASKED ? -INFINITY : __builtin_fmaf(s1[r], kb_mul, ref);
+      }
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        s0 = Tr::mfma(kf0[ks], qf[ks], s0);
+        s1 = Tr::mfma(kf1[ks], qf[ks], s1);
+      }
+      return;
+    }
     if (PRESC) {
       s0 = Tr::mfma(kf0[0], qf[0], mneg);
       s1 = Tr::mfma(kf1[0], qf[0], mneg);
@@ -306,6 +353,12 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
   // (a = 1, b = 0 for the self segment).  Linear in the keys, so folding a PART of a segment (a
   // K/V-range piece ending mid-segment) is equally valid.
   auto fold_segment = [&]() {
+    // BIAS: every key so far masked - nothing is accumulated (all zeros) and the reference is not set: 2^(m_ot - m_run) would be
+    // 2^(-inf - -inf), or a huge factor once a first unmasked tile far below the start value adopts its max.  m_ot stays -inf.
+    if (BIAS && (PRESC ? !started : !__any(m_run > -INFINITY))) {
+      if (MASS) cum_store(cseg, -INFINITY);
+      return;
+    }
     float lseg = (la[0] + la[1]) + (lb[0] + lb[1]);
     {
       const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(lseg), __float_as_uint(lseg), false, false);
@@ -396,9 +449,17 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
     if (PRESC && !CHK) {
       // S(t) is already c2*s - m_run.  First tile of the piece: adopt its row max whatever its sign (the
       // reference started at 0); later tiles: move only when some row grew by more than 2^6 (lazy).
-      if (t == 0 || __any(mx > lazy_thr)) {
-        const float d = t == 0 ? mx : (mx > 0.f ? mx : 0.f);
-        const float alpha = t == 0 ? 1.f : fast_exp2(-d);
+      // BIAS: "first tile" is the first tile with an unmasked key (a tile of masked keys has mx = -inf in every row, contributes
+      // exactly nothing and must not set the reference: d = -inf would make it NaN)
+      bool adopt = t == 0;
+      if (BIAS) {
+        const bool live = __any(mx > -INFINITY);
+        adopt = live && !started;
+        started = started || live;
+      }
+      if (adopt || __any(mx > lazy_thr)) {
+        const float d = adopt ? mx : (mx > 0.f ? mx : 0.f);
+        const float alpha = adopt ? 1.f : fast_exp2(-d);
 #pragma unroll
         for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; c0[r] -= d; c1[r] -= d; }
         la *= alpha;
@@ -421,7 +482,9 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
       lb *= alpha;
       m_run = m_new;
     }
-    const float mc = (LAZYMAX ? m_run : m_new) * c2;
+    // (BIAS: no unmasked key yet - the reference is still -inf and every score of the tile is: fma(-inf, c2, +inf) would be NaN)
+    const float m_sub = LAZYMAX ? m_run : m_new;
+    const float mc = (BIAS && !(m_sub > -INFINITY)) ? 0.f : m_sub * c2;
     // (4) the overlapped block: prefetch issue, S(t+1) on the matrix pipe, exp/pack on the VALU,
     //     PV(t) on the matrix pipe
     if (!EARLYQK && !NOPIPE && has2 && !(ABL & 4)) {
@@ -500,6 +563,7 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
     pk[0][1] = __builtin_convertvector(__builtin_shufflevector(c0, c0, 8, 9, 10, 11, 12, 13, 14, 15), v8);
     pk[1][0] = __builtin_convertvector(__builtin_shufflevector(c1, c1, 0, 1, 2, 3, 4, 5, 6, 7), v8);
     pk[1][1] = __builtin_convertvector(__builtin_shufflevector(c1, c1, 8, 9, 10, 11, 12, 13, 14, 15), v8);
+    if (BIAS && has2) bias_load(c0, c1);   // S(t) is packed: its registers take the bias of tile t+2 (the prefetch stream's position)
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
@@ -547,10 +611,13 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
   seg_setup(seg);
 #pragma unroll
   for (int c = 0; c < CH; ++c) { kvo[c] += (unsigned)(t0 * kstep); vvo[c] += (unsigned)(t0 * vstep); }
+  f32x16 sa0, sa1, sb0, sb1;
   if (DMA) {
+    if (BIAS) bias_load(sa0, sa1);
     issue_dma(0, 0);
     advance();
     if (!NOPIPE && NTILES > 1) {
+      if (BIAS) bias_load(sb0, sb1);
       issue_dma(1, 1);
       advance();
     }
@@ -569,7 +636,6 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
   for (int ks = 0; ks < 4; ++ks) asm volatile("" ::"v"(qf[ks]));  // retire the Q loads before the loop
   __syncthreads();
 
-  f32x16 sa0, sa1, sb0, sb1;
   if (!NOPIPE) {
     qk(sa0, sa1, 0);
     // S(0) is read by inline-asm v_max3 right away in the first step: pad the MFMA->VALU hazard
@@ -698,12 +764,13 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
       // pre-scaled forms start their reference at 0, and a 0 beside real pieces whose maxima lie below -126 exponent units
       // would flush every weight to zero
       const bool empty_piece = NTILES == 0 && !(nref < p.N && piece == npiece - 1);
-      p.ws_ml[prow * 2] = empty_piece ? -INFINITY : (PRESC ? m_run / c2 : m_run);
+      // (BIAS: a piece whose keys are all masked holds nothing either; without PRESC its m_run is still -inf)
+      p.ws_ml[prow * 2] = (empty_piece || (BIAS && PRESC && !started)) ? -INFINITY : (PRESC ? m_run / c2 : m_run);
       p.ws_ml[prow * 2 + 1] = l_fin;
     }
     return;
   }
-  const float inv = 1.0f / l_fin;
+  const float inv = (BIAS && !(l_fin > 0.f)) ? 0.f : 1.0f / l_fin;   // BIAS: every key of the row masked - exact zeros, lse = -inf
   if (qrow < p.Lq) {
     const int64_t ooff = (int64_t)b * p.o_sb + (int64_t)qrow * p.o_sl + (int64_t)h * p.o_sh;
     T* op = (T*)p.out + ooff;
@@ -726,14 +793,15 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
       }
     }
     if (p.lse != nullptr && hi == 0)
-      p.lse[((int64_t)b * p.H + h) * p.Lq + qrow] = (PRESC ? m_run * 0.69314718f : m_run * p.scale) + __logf(l_fin);
+      p.lse[((int64_t)b * p.H + h) * p.Lq + qrow] = (BIAS && !(l_fin > 0.f)) ? -INFINITY : (PRESC ? m_run * 0.69314718f : m_run * p.scale) + __logf(l_fin);
   }
 }
 
 // Merge the K/V-range pieces of the remainder items: one workgroup per remainder item, thread =
 // (row, 32-channel half).  out = sum_j w_j O_j / sum_j w_j l_j with w_j = 2^((m_j - M) c).
-template <typename T, int QB>
-__global__ void __launch_bounds__(256) shared_attn_combine_kernel(const AttnKParams p) {
+// (BIAS: the combine of a call with a key bias - every piece of a row may be empty, all of its keys masked: exact zeros, lse = -inf)
+template <typename T, int QB, bool BIAS>
+__device__ __forceinline__ void combine_rows(const AttnKParams p) {
   // grid: (8 * remainder items per XCD, QB / 16); 256 threads = 16 rows x 16 four-channel groups, so a
   // wave reads four whole 256-byte partial rows per load and thousands of workgroups are in flight
   // (one workgroup per item left half the CUs idle on a latency-bound kernel)
@@ -755,16 +823,16 @@ __global__ void __launch_bounds__(256) shared_attn_combine_kernel(const AttnKPar
   float L = 0.f;
   for (int j = 0; j < p.sk_k; ++j) {
     const int64_t prow = (base + j) * QB + row;
-    const float w = fast_exp2((p.ws_ml[prow * 2] - M) * p.scale_log2);
+    const float w = (BIAS && M == -INFINITY) ? 0.f : fast_exp2((p.ws_ml[prow * 2] - M) * p.scale_log2);
     L += w * p.ws_ml[prow * 2 + 1];
     const f32x4 x = *(const f32x4*)(p.ws_o + prow * 64 + grp * 4);
     acc += x * w;
   }
-  const float inv = 1.0f / L;
+  const float inv = (BIAS && !(L > 0.f)) ? 0.f : 1.0f / L;
   const int64_t off = (int64_t)b * p.o_sb + (int64_t)qrow * p.o_sl + (int64_t)h * p.o_sh + grp * 4;
   if (p.out_f32) *(f32x4*)((float*)p.out + off) = acc * inv;   // IR_FLAG_OUT_F32: the result before the 16-bit rounding
   else *(v4*)((T*)p.out + off) = __builtin_convertvector(acc * inv, v4);
-  if (p.lse != nullptr && grp == 0) p.lse[((int64_t)b * p.H + h) * p.Lq + qrow] = M * p.scale + __logf(L);
+  if (p.lse != nullptr && grp == 0) p.lse[((int64_t)b * p.H + h) * p.Lq + qrow] = (BIAS && !(L > 0.f)) ? -INFINITY : M * p.scale + __logf(L);
   if (p.seg_cum != nullptr) {
     // ABI v9: a piece's entry s is the log-sum-exp (log2 units) of what ITS key range holds of segments 0 .. s (-inf before its
     // range, its total after it): the item's cumulative value is their log-sum-exp, taken in the fixed piece order
@@ -777,6 +845,11 @@ __global__ void __launch_bounds__(256) shared_attn_combine_kernel(const AttnKPar
     }
   }
 }
+
+template <typename T, int QB>
+__global__ void __launch_bounds__(256) shared_attn_combine_kernel(const AttnKParams p) { combine_rows<T, QB, false>(p); }
+template <typename T, int QB>
+__global__ void __launch_bounds__(256) shared_attn_combine_bias_kernel(const AttnKParams p) { combine_rows<T, QB, true>(p); }
 
 // measurement knob (round 6, VERDICT r5 item 5: "the split-K/V form on purpose"): IR_ATTN_FORCE_SPLIT=k cuts EVERY item of the
 // 32-row kernel's grid into k K/V-range pieces (more resident waves per CU to hide the per-tile latency chain), within the
@@ -798,6 +871,10 @@ hipError_t launch(const AttnKParams& p0, hipStream_t s) {
   hipLaunchKernelGGL((shared_attn_fwd_pipe_kernel<T, NW, FOLD, ABL, MASS>), dim3(pl.grid), dim3(NW * 64), 0, s, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || pl.k <= 1) return e;
+  if ((ABL & 16384) != 0) {   // BIAS
+    hipLaunchKernelGGL((shared_attn_combine_bias_kernel<T, QB>), dim3(kIrXcds * pl.rem, QB / 16), dim3(256), 0, s, p);
+    return hipGetLastError();
+  }
   return ir_launch_shared_attn_combine(p, std::is_same<T, __bf16>::value ? 1 : 0, QB, pl.rem, s);
 }
 
@@ -817,6 +894,23 @@ hipError_t launch_f(const AttnKParams& p, hipStream_t s) {
   return p.aa != nullptr ? launch<T, NW, true, ABL, MASS>(p, s) : launch<T, NW, false, ABL, MASS>(p, s);
 }
 
+#ifdef IR_PIPE_BIAS_TU   // shared_attn_fwd_pipe_bias.hip: the BIAS instantiations and nothing else of this file
+constexpr int kBias = 16384;
+template <typename T>
+hipError_t launch_bias_t(const AttnKParams& p, IrPipeForm form, hipStream_t s) {
+  const bool mass = p.seg_cum != nullptr;
+  if (form == IR_PIPE_PRESC) return mass ? launch_f<T, kFormPresc | kBias, true>(p, s) : launch_f<T, kFormPresc | kBias>(p, s);
+  if (form == IR_PIPE_EARLYQK) return mass ? launch_f<T, kFormEarlyQK | kBias, true>(p, s) : launch_f<T, kFormEarlyQK | kBias>(p, s);
+  return hipErrorInvalidValue;
+}
+
+}  // namespace
+
+hipError_t ir_launch_shared_attn_fwd_pipe_bias(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s) {
+  if (p.key_bias == nullptr || p.valid != nullptr) return hipErrorInvalidValue;
+  return dtype == 1 ? launch_bias_t<__bf16>(p, form, s) : launch_bias_t<_Float16>(p, form, s);
+}
+#else
 template <typename T>
 hipError_t launch_t(const AttnKParams& p, IrPipeForm form, hipStream_t s) {
   if (p.seg_cum != nullptr) {   // ABI v9 seg_mass: the two forms the default dispatch takes
@@ -885,3 +979,4 @@ hipError_t ir_launch_shared_attn_combine(const AttnKParams& p, int dtype, int qb
 hipError_t ir_launch_shared_attn_fwd_pipe(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s) {
   return dtype == 1 ? launch_t<__bf16>(p, form, s) : launch_t<_Float16>(p, form, s);
 }
+#endif  // IR_PIPE_BIAS_TU

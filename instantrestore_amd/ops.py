@@ -248,8 +248,8 @@ def _is_table(t) -> bool:
 
 
 def _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, lse, split=True,
-               q_prescaled=False, valid_refs=None, batch_invariant=False):
-    a = _lib.SharedAttnTableArgs() if _is_table(ref_k) else _lib.SharedAttnArgs()
+               q_prescaled=False, valid_refs=None, batch_invariant=False, key_bias=None):
+    a = _lib.SharedAttnBiasArgs() if key_bias is not None else _lib.SharedAttnTableArgs() if _is_table(ref_k) else _lib.SharedAttnArgs()
     a.struct_size = C.sizeof(a)
     a.dtype = _dtype_code(q)
     a.flags = (_lib.IR_FLAG_INCLUDE_SELF if include_self else 0) | (_lib.IR_FLAG_Q_PRESCALED if q_prescaled else 0)
@@ -279,6 +279,16 @@ def _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adai
         a.vr_sb, a.vr_sn, a.vr_sl, a.vr_sh = ref_v.stride(0), ref_v.stride(1), ref_v.stride(2), HEAD_DIM
     if adain is not None:
         a.adain_a, a.adain_b = adain[0].data_ptr(), adain[1].data_ptr()
+    if key_bias is not None:
+        lkv = (k_self.shape[1] if include_self else 0) + (ref_k.shape[1] * ref_k.shape[2] if ref_k is not None else 0)
+        _check_key_bias(key_bias, q, heads, lkv)
+        a.key_bias = key_bias.data_ptr()
+        a.kb_sb, a.kb_sh = key_bias.stride(0), (key_bias.stride(1) if key_bias.dim() == 3 else 0)
+        a._keepbias = key_bias
+        if valid_refs is not None and _is_table(ref_k):
+            raise ValueError("key_bias with valid_refs on a RefKVTable call: slots n >= valid_refs[b] of the table are not readable, and the kernel "
+                             "with a key bias walks every reference (mask them in the bias and fill the slots, or pass dense tensors)")
+        valid_refs = None   # dense: the promise is about the DATA (all-zero references) - walking the zeros gives the same numbers
     if valid_refs is not None and ref_k is not None:
         if valid_refs.dtype != torch.int32 or valid_refs.device != q.device or valid_refs.numel() != q.shape[0] or not valid_refs.is_contiguous():
             raise ValueError(f"valid_refs must be a contiguous int32 ({q.shape[0]},) tensor on {q.device}")
@@ -293,6 +303,80 @@ def _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adai
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
         a._keepalive = ws
     return a
+
+
+def _check_key_bias(kb, q, heads: int, lkv: int) -> None:
+    """``key_bias``: fp32 ``(B, Lkv)`` or ``(B, H, Lkv)`` on q's device, last axis contiguous (the strides go to the kernel as they are)"""
+    if not isinstance(kb, torch.Tensor) or kb.dtype != torch.float32:
+        raise ValueError(f"key_bias must be a float32 tensor, got {getattr(kb, 'dtype', type(kb))}")
+    want = ((q.shape[0], lkv), (q.shape[0], heads, lkv))
+    if tuple(kb.shape) not in want:
+        raise ValueError(f"key_bias must have shape (B, Lkv) = {want[0]} or (B, H, Lkv) = {want[1]} over the extended key axis, got {tuple(kb.shape)}")
+    if kb.device != q.device:
+        raise ValueError(f"key_bias is on {kb.device}, q on {q.device}")
+    if kb.stride(-1) != 1 or any(st < 0 for st in kb.stride()):
+        raise ValueError("key_bias: the key axis must be contiguous (stride 1) and no stride negative")
+
+
+def key_bias(batch: int, len_self: int, n_refs: int, len_ref: int, include_self: bool, *, attention_mask=None, ref_weights=None,
+             ref_token_keep=None, device=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The fp32 ``(B, Lkv)`` bias row of :func:`shared_attention` over the extended key axis ``[self (iff include_self)] ++ ref 0 ++
+    ... ++ ref N-1`` (``Lkv = include_self * len_self + n_refs * len_ref``), the sum of:
+
+    ``ref_weights`` ``(B, N)``, values >= 0: ``log w`` on every key of the reference's segment - ``mass_n / mass_self`` scales by
+    ``w_n``; 0 masks the reference (``-inf``).
+    ``ref_token_keep`` bool: ``(B, N, len_ref)``, or ``(B, N, S, S)`` pooled by area to the layer's ``side = sqrt(len_ref)`` (a
+    token is kept when >= 0.5 of its area is); dropped tokens are masked.
+    ``attention_mask``: additive (diffusers' prepared form), ``(B, Lkv)`` or ``(B, 1, Lkv)`` over the extended length.
+
+    Plain torch elementwise work, off the hot path, no sync.  ``out=``: refill that tensor in place (a captured step follows)."""
+    B, N = int(batch), int(n_refs)
+    ls = int(len_self) if include_self else 0
+    lkv = ls + N * int(len_ref)
+    if device is None:
+        device = next((t.device for t in (out, attention_mask, ref_weights, ref_token_keep) if isinstance(t, torch.Tensor)), torch.device("cpu"))
+    device = torch.device(device)
+    row = torch.zeros((B, lkv), dtype=torch.float32, device=device)
+    neg = float("-inf")
+    if N > 0:
+        refs = row[:, ls:].view(B, N, int(len_ref))
+        if ref_weights is not None:
+            w = torch.as_tensor(ref_weights).to(device=device, dtype=torch.float32)
+            if tuple(w.shape) != (B, N):
+                raise ValueError(f"ref_weights must have shape (B, N) = {(B, N)}, got {tuple(w.shape)}")
+            if not w.is_cuda and bool((w < 0).any()):
+                raise ValueError("ref_weights must be >= 0")
+            refs += torch.log(w).unsqueeze(-1)   # log 0 = -inf: masked
+        if ref_token_keep is not None:
+            keep = torch.as_tensor(ref_token_keep).to(device=device)
+            if keep.dtype != torch.bool:
+                raise ValueError(f"ref_token_keep must be a bool tensor, got {keep.dtype}")
+            if keep.dim() == 4:
+                side = int(round(int(len_ref) ** 0.5))
+                if keep.shape[:2] != (B, N) or side * side != int(len_ref) or keep.shape[2] != keep.shape[3]:
+                    raise ValueError(f"ref_token_keep (B, N, S, S) needs a square layer (len_ref = {len_ref}) and shape ({B}, {N}, S, S), got {tuple(keep.shape)}")
+                area = torch.nn.functional.adaptive_avg_pool2d(keep.to(torch.float32), side) if keep.shape[2] != side else keep.to(torch.float32)
+                keep = (area >= 0.5).reshape(B, N, side * side)
+            if tuple(keep.shape) != (B, N, int(len_ref)):
+                raise ValueError(f"ref_token_keep must have shape (B, N, len_ref) = {(B, N, int(len_ref))} or (B, N, S, S), got {tuple(keep.shape)}")
+            refs.masked_fill_(~keep, neg)
+    elif ref_weights is not None or ref_token_keep is not None:
+        raise ValueError("ref_weights / ref_token_keep given without references")
+    if attention_mask is not None:
+        m = torch.as_tensor(attention_mask).to(device=device)
+        if m.dtype == torch.bool:
+            raise ValueError("attention_mask must be additive (0 / -10000), not bool")
+        if m.dim() == 3 and m.shape[1] == 1:
+            m = m[:, 0]
+        if tuple(m.shape) != (B, lkv):
+            raise ValueError(f"attention_mask must have shape (B, Lkv) = {(B, lkv)} or (B, 1, Lkv) over the extended key axis, got {tuple(torch.as_tensor(attention_mask).shape)}")
+        row += m.to(torch.float32)
+    if out is not None:
+        if out.dtype != torch.float32 or tuple(out.shape) != (B, lkv):
+            raise ValueError(f"out must be fp32 {(B, lkv)}, got {out.dtype} {tuple(out.shape)}")
+        out.copy_(row)
+        return out
+    return row
 
 
 def _bi_workspace(a, device) -> None:
@@ -394,7 +478,7 @@ def shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, s
                      include_self: bool = True, adain: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                      return_lse: bool = False, split: bool = True, q_prescaled: bool = False,
                      out_dtype: Optional[torch.dtype] = None, valid_refs: Optional[torch.Tensor] = None,
-                     return_mass: bool = False, batch_invariant: bool = False):
+                     return_mass: bool = False, batch_invariant: bool = False, key_bias: Optional[torch.Tensor] = None):
     """Fused extended self-attention (``ir_shared_attn_fwd``).
 
     Returns ``out`` (B, Lq, H*64) in q's dtype [, ``lse`` (B, H, Lq) fp32] [, ``mass`` (B, H, Lq, include_self + N) fp32:
@@ -417,6 +501,13 @@ def shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, s
     ``torch.stack`` of the entries (:func:`attn_probs`, :func:`attn_segment_mass`, :func:`attn_rows` and
     :func:`shared_attention_kernel_name` take a table as ``ref_k`` too).  With ``valid_refs``, table slots ``n >= valid_refs[b]``
     are never read.
+    ``key_bias`` (``ir_shared_attn_bias_args``): fp32 ``(B, Lkv)`` or ``(B, H, Lkv)`` on the device, added to the scaled scores before
+    the softmax over the packed extended key axis (:func:`key_bias` builds the row from masks and per-reference weights).  A key
+    at ``-inf`` or ``<= -10000`` is masked: probability exactly 0; a ``(b, h)`` with every key masked gives zeros, ``lse = -inf``
+    and zero masses.  Read when the kernel runs (a captured call follows in-place updates).  Always the 32-row kernel.  With
+    ``valid_refs``: a dense call drops the promise and walks the zeros (same numbers); a table call raises.  AdaIN statistics are
+    not masked (the reference's ``adain`` knows no mask).  :func:`attn_probs`, :func:`attn_segment_mass` and :func:`attn_rows`
+    take no bias - their ``exp(s - lse)`` would leave it out; ``return_mass`` is the read-back that honours it.
     """
     q, k_self, v_self, ref_k, ref_v = _prep(q, k_self, v_self, ref_k, ref_v, heads, include_self, adain)
     if out_dtype not in (None, q.dtype, torch.float32):
@@ -424,7 +515,7 @@ def shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, s
     out = torch.empty((q.shape[0], q.shape[1], heads * HEAD_DIM), dtype=out_dtype or q.dtype, device=q.device)
     lse = torch.empty((q.shape[0], heads, q.shape[1]), dtype=torch.float32, device=q.device) if return_lse else None
     args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, lse, split, q_prescaled, valid_refs,
-                      batch_invariant)
+                      batch_invariant, key_bias)
     mass = None
     if return_mass:
         nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
@@ -449,13 +540,13 @@ def shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, s
 def time_shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, scale: float,
                           include_self: bool = True, adain=None, iters: int = 10, split: bool = True,
                           q_prescaled: bool = False, valid_refs: Optional[torch.Tensor] = None, return_mass: bool = False,
-                          batch_invariant: bool = False) -> float:
+                          batch_invariant: bool = False, key_bias: Optional[torch.Tensor] = None) -> float:
     """Average ms per launch measured with HIP events on the launch stream (``bench.py``); ``valid_refs`` / ``return_mass`` /
     ``batch_invariant`` as in :func:`shared_attention` (the masses' finishing kernel is part of the timed launch)."""
     q, k_self, v_self, ref_k, ref_v = _prep(q, k_self, v_self, ref_k, ref_v, heads, include_self, adain)
     out = torch.empty((q.shape[0], q.shape[1], heads * HEAD_DIM), dtype=q.dtype, device=q.device)
     args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, None, split, q_prescaled, valid_refs,
-                      batch_invariant)
+                      batch_invariant, key_bias)
     if return_mass:
         nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
         mass = torch.empty((q.shape[0], heads, q.shape[1], nseg), dtype=torch.float32, device=q.device)
@@ -487,14 +578,14 @@ def bench_mfma_stream(dtype: torch.dtype = torch.bfloat16, zero_operands: bool =
 def shared_attention_kernel_name(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, scale: float,
                                  include_self: bool = True, adain=None, q_prescaled: bool = False,
                                  valid_refs: Optional[torch.Tensor] = None, return_mass: bool = False,
-                                 batch_invariant: bool = False) -> str:
+                                 batch_invariant: bool = False, key_bias: Optional[torch.Tensor] = None) -> str:
     """which kernel the dispatcher launches for these tensors (reporting only; ``valid_refs`` / ``return_mass`` as in
     :func:`shared_attention` - they decide the 128-row kernel's form and whether the default rule takes it;
     ``batch_invariant``: the kernel and pieces of the batch-invariant plan)"""
     q, k_self, v_self, ref_k, ref_v = _prep(q, k_self, v_self, ref_k, ref_v, heads, include_self, adain)
     out = torch.empty((q.shape[0], q.shape[1], heads * HEAD_DIM), dtype=q.dtype, device=q.device)
     args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, None, True, q_prescaled, valid_refs,
-                      batch_invariant)
+                      batch_invariant, key_bias)
     if return_mass:   # never written: the name is all this call computes
         nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
         mass = torch.empty((q.shape[0], heads, q.shape[1], nseg), dtype=torch.float32, device=q.device)
@@ -505,13 +596,13 @@ def shared_attention_kernel_name(q, k_self, v_self, ref_k=None, ref_v=None, *, h
 def shared_attention_plan(batch: int, len_q: int, heads: int, *, len_self: int = 0, n_refs: int = 0, len_ref: int = 0,
                           dtype: torch.dtype = torch.bfloat16, include_self: bool = True, adain: bool = False,
                           q_prescaled: bool = False, valid_refs: bool = False, return_mass: bool = False,
-                          out_dtype: Optional[torch.dtype] = None, workspace_bytes: Optional[int] = None) -> dict:
+                          out_dtype: Optional[torch.dtype] = None, workspace_bytes: Optional[int] = None, key_bias: bool = False) -> dict:
     """the batch-invariant plan of a :func:`shared_attention` call of these sizes (``ir_shared_attn_plan``; host only - no tensor,
     no device): ``kernel`` (``IR_TUNE_*``), ``rows_per_item``, ``items_per_batch``, ``pieces_per_item``, ``workspace_bytes`` (the
     scratch of one launch over the batch, what :func:`shared_attention` allocates per call) and ``batch_per_launch`` - the entries
     one launch covers with a workspace of ``workspace_bytes`` bytes (default: the plan's own size)"""
-    a = _lib.SharedAttnArgs()
-    a.struct_size = C.sizeof(_lib.SharedAttnArgs)
+    a = _lib.SharedAttnBiasArgs() if key_bias else _lib.SharedAttnArgs()   # key_bias: one more per-entry parameter (the 32-row kernel at every len_q)
+    a.struct_size = C.sizeof(a)
     a.dtype = _DT[dtype]
     a.flags = _lib.IR_FLAG_BATCH_INVARIANT | (_lib.IR_FLAG_INCLUDE_SELF if include_self else 0) | \
         (_lib.IR_FLAG_Q_PRESCALED if q_prescaled else 0) | (_lib.IR_FLAG_OUT_F32 if out_dtype == torch.float32 else 0)
@@ -541,6 +632,8 @@ def shared_attention_plan(batch: int, len_q: int, heads: int, *, len_self: int =
         a.valid_refs = dummy
     if return_mass:
         a.seg_mass = dummy
+    if key_bias:
+        a.key_bias = dummy
     L = _lib.lib()
     if workspace_bytes is None:
         workspace_bytes = int(L.ir_shared_attn_workspace_bytes_for(C.byref(a)))
