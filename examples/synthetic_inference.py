@@ -54,6 +54,10 @@ def main(argv=None):
     ap.add_argument("--ref-weights", default=None,
                     help="comma-separated weight per reference, e.g. 1,1,0.25,0 (0 masks a reference): prints the top shared layer's "
                          "per-reference attention masses with and without")
+    ap.add_argument("--compact-refs", type=float, default=None, metavar="FRACTION",
+                    help="keep a centred elliptical region of that area of every reference (e.g. 0.5): the kept tokens are packed to the "
+                         "front of their segments once (ops.compact_refs) and the shared layers walk the counts (ref_lens); prints the top "
+                         "shared layer's attention masses with and without")
     ap.add_argument("--kv-tables", action="store_true",
                     help="one more cached frame whose reference K/V are pointer tables into the cache entries (assemble_tables: no copy)")
     args = ap.parse_args(argv)
@@ -170,6 +174,33 @@ def main(argv=None):
             for b in range(B):
                 print(f"identity {b}: mass [self?] ++ references  unweighted {fmt(m0[b])}  |  weights {args.ref_weights}: {fmt(m1[b])}")
             assert all(float(m1[:, int(top.train_input) + n].abs().max()) == 0.0 for n in range(N) if float(w[n]) == 0.0)
+        # "Only the face region of every reference": a keep map is turned into FEWER KEYS, once per identity - the kept tokens of a
+        # reference packed to the front of its segment, per-reference counts for the shared layers (ref_lens) - instead of a mask
+        # that every frame pays for (ref_token_keep: the key bias walks every tile).  The AdaIN statistics stay those of the full
+        # references (cs, taken before compaction), as with a mask.
+        if args.compact_refs is not None:
+            import math
+            frac = float(args.compact_refs)
+            assert 0.0 < frac <= 1.0, "--compact-refs needs a fraction in (0, 1]"
+            a = 64 * math.sqrt(frac / (1.25 * math.pi))                     # a centred ellipse, axes 1 : 1.25, on a 64 x 64 map
+            yy, xx = torch.meshgrid(torch.arange(64) + 0.5 - 32, torch.arange(64) + 0.5 - 32, indexing="ij")
+            keep = ((xx / a) ** 2 + (yy / (1.25 * a)) ** 2 <= 1.0).to(dev).expand(B, N, 64, 64)
+            packed = [ops.compact_refs(k, v, keep, heads=k.shape[-1] // 64) for k, v in zip(ck, cv)]     # pooled to every layer's side
+            top = [p for p in unet.attn_processors.values() if getattr(p, "self_attn_idx", None) == 8][0]
+            top.save_attention_mass = True
+            unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1),
+                 cross_attention_kwargs={"ref_keys": ck, "ref_values": cv, "ref_stats": cs})
+            m0 = top.attention_mass.mean(dim=(1, 2))
+            zc = unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1),
+                      cross_attention_kwargs={"ref_keys": [t[0] for t in packed], "ref_values": [t[1] for t in packed], "ref_stats": cs,
+                                              "ref_lens": [t[2] for t in packed]}).sample
+            m1 = top.attention_mass.mean(dim=(1, 2))
+            top.save_attention_mass = False
+            fmt = lambda m: " ".join(f"{v:.3f}" for v in m.tolist())
+            kept = packed[8][2][0].tolist()
+            for b in range(B):
+                print(f"identity {b}: mass [self?] ++ references  full {fmt(m0[b])}  |  {kept} of {ck[8].shape[2]} tokens kept: {fmt(m1[b])}")
+            assert bool(torch.isfinite(zc).all()) and float((m1.sum(-1) - 1).abs().max()) < 2e-3
         # Where do the facial landmarks look (vis_utils.py:88-110)?  Each shared layer is told which query tokens they fall on
         # and leaves the sum of those tokens' head-mean probability rows behind - (B, Lkv) fp32, reshaped to one side x 5*side
         # picture over the degraded image and its references - instead of the (B, H, L, Lkv) tensor of save_self_attentions.

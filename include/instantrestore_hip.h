@@ -55,7 +55,7 @@ typedef enum ir_dtype { IR_DTYPE_F16 = 0, IR_DTYPE_BF16 = 1 } ir_dtype;
                                    (tests show the pre-rounding error of the kernel that ships) */
 #define IR_FLAG_BATCH_INVARIANT 8u /* ABI v10, opt-in: the bytes of every output of batch entry b (out, lse, seg_mass) depend on
                                    entry b's own inputs and the per-entry parameters only (dtype, len_q, heads, segment lengths,
-                                   n_refs, INCLUDE_SELF, AdaIN on/off, Q_PRESCALED, valid_refs given or not, key_bias given or not, OUT_F32) - not on
+                                   n_refs, INCLUDE_SELF, AdaIN on/off, Q_PRESCALED, valid_refs given or not, key_bias given or not, ref_lens given or not, OUT_F32) - not on
                                    the batch size, the entry's position, other entries, the stream, graph capture, the workspace,
                                    whether lse / seg_mass are asked for, IR_ATTN_W128 or the device's CU count.  The kernel and a
                                    fixed cut of every item into K/V-range pieces (merged in piece order) are chosen from those
@@ -99,7 +99,7 @@ typedef enum ir_dtype { IR_DTYPE_F16 = 0, IR_DTYPE_BF16 = 1 } ir_dtype;
  */
 #define IR_ATTN_SEG_BYTES_MAX 2147483647LL
 typedef struct ir_shared_attn_args {
-  uint32_t struct_size; /* = sizeof(ir_shared_attn_args), or sizeof(ir_shared_attn_table_args) / sizeof(ir_shared_attn_bias_args) when the block is one (below) */
+  uint32_t struct_size; /* = sizeof(ir_shared_attn_args), or sizeof(ir_shared_attn_table_args) / sizeof(ir_shared_attn_bias_args) / sizeof(ir_shared_attn_ragged_args) when the block is one (below) */
   int32_t dtype;        /* ir_dtype */
   uint32_t flags;       /* IR_FLAG_* */
   int32_t batch;        /* B */
@@ -216,6 +216,40 @@ typedef struct ir_shared_attn_bias_args {
   int64_t kb_sb, kb_sh;          /* strides in fp32 elements over batch and head; kb_sh = 0: one row shared by all heads */
 } ir_shared_attn_bias_args;
 #define IR_KEY_BIAS_MASKED (-1.0e4f)
+
+/*
+ * Per-reference token counts (ragged references).  A fourth block, ir_shared_attn_bias_args with two fields appended, told apart by
+ * `struct_size` as the others are (sizeof(ir_shared_attn_ragged_args) = the bias block's size + 16; every size other than the four is
+ * IR_ERR_INVALID_ARG; IR_ABI_VERSION stays 10).  Tables and key_bias may be NULL; ref_lens may be NULL, and then the call is the call
+ * of the shorter blocks in every respect (kernel, plan, bytes).
+ *
+ *   c[b,n] = clamp(ref_lens[b * rl_sb + n], 0, len_ref)    the number of keys reference n of batch entry b HAS
+ *
+ * len_ref becomes the CAPACITY of a reference segment: its allocation, its strides and the 32-bit span rule stay as they are.  Keys
+ * t >= c[b,n] do not exist: they are never used, whatever bytes lie there (NaN included), and in a table call an entry whose count is
+ * 0 is never read or dereferenced.  The self segment is untouched.  The extended key order is unchanged; lse and seg_mass are over
+ * the existing keys, and a reference with count 0 has mass 0: ABSENT (probability exactly 0), not zero-filled (valid_refs: exp(0)
+ * per key).  A (b, h) with no key at all (no self block, every count 0) gives out = 0, lse = -inf and masses 0 - never NaN: the
+ * rule of a wholly masked row of the key bias.  The AdaIN affine (adain_a, adain_b) is an input as before; which tokens its
+ * statistics are taken over is the caller's business.  ref_lens is read when the kernel RUNS: a replayed hipGraph follows in-place
+ * updates.  ir_compact_ref_tokens (below) packs the kept tokens of a reference to the front of a segment and writes the counts.
+ *
+ * Taken by ir_shared_attn_fwd, ir_time_shared_attn_fwd, ir_shared_attn_kernel_name, ir_shared_attn_plan and
+ * ir_shared_attn_workspace_bytes_for.  A call with counts always runs the software-pipelined 32-row kernel (its RAGGED form: the
+ * pre-scaled-Q form with IR_FLAG_Q_PRESCALED or IR_TUNE_PIPE32_PRESCALE_Q, the early-QK form otherwise), at every len_q; the cut
+ * into K/V-range pieces and the workspace are planned for full references (a piece of a short entry may be empty).  With every count
+ * equal to len_ref the bytes are those of the same form without counts.
+ * Accepted with it: seg_mass, lse, IR_FLAG_OUT_F32, IR_FLAG_Q_PRESCALED, AdaIN, tables, IR_FLAG_BATCH_INVARIANT.
+ * Refused (IR_ERR_UNSUPPORTED): ref_lens with valid_refs (a count of 0 says "absent", valid_refs says "zero-filled": pick one);
+ * ref_lens with a non-NULL key_bias (the bias indexes the packed uniform key axis: a follow-up); n_refs == 0; a tuning other than
+ * IR_TUNE_DEFAULT, IR_TUNE_PIPE32_PRESCALE_Q, IR_TUNE_PIPE32_EARLYQK; a ref_lens that is not 4-byte aligned; and ir_attn_probs[_ex],
+ * ir_attn_segment_mass, ir_attn_rows with a non-NULL ref_lens (they would walk the tails).  rl_sb < n_refs is IR_ERR_INVALID_ARG.
+ */
+typedef struct ir_shared_attn_ragged_args {
+  ir_shared_attn_bias_args b;    /* b.t.args.struct_size = sizeof(ir_shared_attn_ragged_args); tables and key_bias may be NULL */
+  const int32_t* ref_lens;       /* device, int32 [B][N] rows rl_sb apart, or NULL (= the call of the shorter blocks in every respect) */
+  int64_t rl_sb;                 /* elements between batch rows, >= N */
+} ir_shared_attn_ragged_args;
 
 /* values of ir_shared_attn_args.tuning (csrc/shared_attn_fwd.hip: kAttnVariants has one row per value - kernel family, form, what
  * it takes; ir_attn_choose is the dispatch) */
@@ -411,6 +445,25 @@ int ir_adain_apply(int32_t dtype, int32_t batch, int32_t heads, int32_t n_refs, 
 int ir_zero_invalid_refs(int32_t batch, int32_t heads, int32_t n_refs, int32_t len, const int32_t* valid,
                          void* k, int64_t k_sb, int64_t k_sn, int64_t k_sl, int64_t k_sh,
                          void* v, int64_t v_sb, int64_t v_sn, int64_t v_sl, int64_t v_sh, void* stream);
+
+/*
+ * ir_compact_ref_tokens - pack the kept tokens of every reference to the front of its segment (stable stream compaction).
+ *
+ * For every (b, n): the rows t of k_in / v_in with keep[b, n, t] != 0 are copied, in their order, to rows 0 .. c-1 of k_out / v_out,
+ * and ref_lens[b * rl_sb + n] = c - the counts a call with ir_shared_attn_ragged_args then walks instead of a masked full reference.
+ * Rows of the outputs behind the count are NOT written.  keep: uint8 (B, N, len_ref) contiguous on the device.
+ *   k_in, v_in, k_out, v_out (B, N, len_ref, H, 64) with strides *_sb, *_sn, *_sl, *_sh (elements, multiples of 8; 16-byte aligned
+ *   bases); the byte span of each output (base to the last element its strides reach) must not overlap the span of an input or of
+ *   the other output (aliasing, at any offset, is IR_ERR_INVALID_ARG).
+ * One launch, no host synchronisation, no atomics, deterministic, capturable; runs once per identity.
+ */
+int ir_compact_ref_tokens(int32_t dtype, int32_t batch, int32_t heads, int32_t n_refs, int32_t len_ref,
+                          const void* k_in, int64_t ki_sb, int64_t ki_sn, int64_t ki_sl, int64_t ki_sh,
+                          const void* v_in, int64_t vi_sb, int64_t vi_sn, int64_t vi_sl, int64_t vi_sh,
+                          const uint8_t* keep,
+                          void* k_out, int64_t ko_sb, int64_t ko_sn, int64_t ko_sl, int64_t ko_sh,
+                          void* v_out, int64_t vo_sb, int64_t vo_sn, int64_t vo_sl, int64_t vo_sh,
+                          int32_t* ref_lens, int64_t rl_sb, void* stream);
 
 /*
  * ir_tensor2im_u8 - the caller's output path on the device.

@@ -54,6 +54,13 @@ class SharedAttnBiasArgs(SharedAttnTableArgs):
     _fields_ = [("key_bias", vp), ("kb_sb", i64), ("kb_sh", i64)]
 
 
+class SharedAttnRaggedArgs(SharedAttnBiasArgs):
+    """mirror of ``ir_shared_attn_ragged_args``: the bias block (tables and key_bias may be NULL) with the per-reference token
+    counts appended - int32 ``[B][N]`` on the device, rows ``rl_sb`` elements apart"""
+
+    _fields_ = [("ref_lens", vp), ("rl_sb", i64)]
+
+
 class SharedAttnPlan(C.Structure):
     """mirror of ``ir_shared_attn_plan_info`` (ABI v10: the batch-invariant plan of a call)"""
 
@@ -111,6 +118,8 @@ SYMBOLS = {
     "ir_token_stats_from_partials": (C.c_int, [i32, i32, i32, vp, i32, vp, vp, vp]),
     "ir_zero_invalid_refs": (C.c_int, [i32, i32, i32, i32, vp, vp, i64, i64, i64, i64,
                                        vp, i64, i64, i64, i64, vp]),
+    "ir_compact_ref_tokens": (C.c_int, [i32, i32, i32, i32, i32, vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, vp,
+                                        vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, vp, i64, vp]),
 }
 
 _lock = threading.Lock()

@@ -424,8 +424,8 @@ class AttnProcessor(nn.Module):
                 self.ready.record(self.stream)
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
-                ref_weights=None, ref_token_keep=None):
-        # ref_weights / ref_token_keep: accepted and ignored (no references here), like ref_valid elsewhere
+                ref_weights=None, ref_token_keep=None, ref_lens=None):
+        # ref_weights / ref_token_keep / ref_lens: accepted and ignored (no references here), like ref_valid elsewhere
         st = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
         self.is_self_attn = encoder_hidden_states is None
         group = self.stop_after_capture
@@ -472,7 +472,8 @@ class FaceIDAttnProcessor(nn.Module):
         self.is_self_attn = None
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
-                ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None, ref_weights=None, ref_token_keep=None):
+                ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None, ref_weights=None, ref_token_keep=None,
+                ref_lens=None):
         # ref_* accepted and ignored, like the reference: the host forwards ONE cross_attention_kwargs dict to every processor
         # (unet.py / diffusers), so whatever the harvest hands SharedAttnProcessor (ref_valid included) arrives here too
         st = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
@@ -534,7 +535,8 @@ class SharedAttnProcessor(nn.Module):
         self.attention_rows = None
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
-                ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None, ref_weights=None, ref_token_keep=None):
+                ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None, ref_weights=None, ref_token_keep=None,
+                ref_lens=None):
         """``attention_mask``: additive, ``(B, Lkv)``, ``(B, 1, Lkv)`` or ``(B * H, 1, Lkv)`` over this layer's key axis (with references: the
         extended one) - the fused kernel's key bias.  ``ref_weights`` ``(B, N)`` >= 0 and ``ref_token_keep`` (bool ``(B, N, len_ref)`` or
         ``(B, N, S, S)``), shared layers only (ignored elsewhere, as ``ref_valid`` is): ``ops.key_bias`` turns them into the bias -
@@ -543,7 +545,15 @@ class SharedAttnProcessor(nn.Module):
         ``attention_rows_index`` with a bias raise (the read-out kernels do not take the bias yet).
         ``ref_valid`` (optional, round 5): int32 ``(B,)`` device tensor from the harvest (``kv_harvest`` ``with_valid``) when
         it zero-filled references ``n >= valid[b]`` (pix2pix_turbo.py:269-273): the kernel then closes those all-zero segments
-        analytically instead of walking them (ABI v8 ``valid_refs``).  Same output; the tokens keep their exp(0) weight."""
+        analytically instead of walking them (ABI v8 ``valid_refs``).  Same output; the tokens keep their exp(0) weight.
+        ``ref_lens`` (optional), shared layers only (ignored elsewhere, as ``ref_valid`` is): a list with one int32 ``(B, N)`` device
+        tensor per shared layer (or ``None``) - the number of keys every reference HAS (``ops.compact_refs``,
+        ``ReferenceKVCache.assemble_tables``); the reference tensors' token axis is then only their capacity, and the kernel walks the
+        existing keys alone (``ir_shared_attn_ragged_args``).  Raises with ``ref_valid`` (absent is not zero-filled), with a mask /
+        ``ref_weights`` / ``ref_token_keep`` (counts with a key bias are a follow-up; ``ref_token_keep`` alone keeps running the bias
+        path), with ``save_self_attentions`` and ``attention_rows_index`` (the read-out kernels would walk the tails);
+        ``save_attention_mass`` works.  With ``use_adain`` it needs ``ref_stats``: the content statistics are those of the FULL
+        reference, taken before compaction - the rule of the bias path, so a compacted call and a masked call agree."""
         st = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
         shared = self.self_attn_idx is not None and ref_keys is not None and ref_values is not None
         # the GEMM's statistics tail (style partials of this layer's own V) only pays when the content statistics arrive
@@ -555,6 +565,7 @@ class SharedAttnProcessor(nn.Module):
         ref_k = ref_v = None
         include_self = True
         affine = None
+        counts = None     # ref_lens of this shared layer
         if shared:
             ref_k = ref_keys[self.self_attn_idx]
             ref_v = ref_values[self.self_attn_idx]
@@ -574,6 +585,21 @@ class SharedAttnProcessor(nn.Module):
             elif hasattr(cstats, "sync_to_current"):
                 cstats.sync_to_current()      # no event handed over: order this stream behind the partials' producer (no-op on one stream)
             include_self = bool(self.train_input)
+            if ref_lens is not None:
+                counts = ref_lens[self.self_attn_idx]
+            if counts is not None:
+                if ref_valid is not None:
+                    raise ValueError("ref_lens with ref_valid: a count of 0 says the reference is absent, ref_valid says it is zero-filled "
+                                     "(its tokens keep exp(0)) - pass one of the two")
+                if st.mask is not None or ref_weights is not None or ref_token_keep is not None:
+                    raise NotImplementedError("ref_lens together with an attention mask, ref_weights or ref_token_keep: the key bias indexes the "
+                                              "packed uniform key axis; counts with a bias are a follow-up (compact the kept tokens instead)")
+                if self.save_self_attentions or getattr(self, "attention_rows_index", None) is not None:
+                    raise NotImplementedError("ref_lens together with save_self_attentions / attention_rows_index: ir_attn_probs and ir_attn_rows "
+                                              "would walk the tails behind the counts (follow-up); save_attention_mass honours the counts")
+                if self.use_adain and cstats is None:
+                    raise ValueError("ref_lens with use_adain needs ref_stats: the AdaIN content statistics are those of the full reference, "
+                                     "taken before compaction - computing them here would read the packed rows and whatever lies behind them")
             if self.use_adain:
                 # style = this image's own post-projection V; content = each reference V.  With the content statistics
                 # handed over (``ref_stats``: computed once per identity by the K/V-capture layer, kv_harvest with_stats)
@@ -620,6 +646,8 @@ class SharedAttnProcessor(nn.Module):
         kw.update(_bi_kw(bi))
         if shared and ref_valid is not None:
             kw["valid_refs"] = ref_valid
+        if counts is not None:
+            kw["ref_lens"] = counts
         len_self = key.shape[1]
         lkv = (len_self if include_self else 0) + (ref_k.shape[1] * ref_k.shape[2] if shared else 0)
         bias = _mask_bias(st.mask, query.shape[0], attn.heads, lkv, len_self, shared)

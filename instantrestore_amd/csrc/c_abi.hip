@@ -37,18 +37,22 @@ int64_t seg_stride_limit(int32_t len, int64_t sl) {
 // `fwd`: the call is (or describes) a launch of the attention forward, whose segment-span limit applies; the read-out entry points
 // (ir_attn_probs*, ir_attn_segment_mass, ir_attn_rows) address K through 64-bit pointers and take any stride
 bool attn_block_size_ok(uint32_t n) {
-  return n == sizeof(ir_shared_attn_args) || n == sizeof(ir_shared_attn_table_args) || n == sizeof(ir_shared_attn_bias_args);
+  return n == sizeof(ir_shared_attn_args) || n == sizeof(ir_shared_attn_table_args) || n == sizeof(ir_shared_attn_bias_args) ||
+         n == sizeof(ir_shared_attn_ragged_args);
 }
 
 int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_out, bool fwd) {
   if (a == nullptr) return fail(IR_ERR_INVALID_ARG, "args is NULL");
-  // the block up to and including seg_mass (no pointer tables), ir_shared_attn_table_args, or ir_shared_attn_bias_args; nothing in between
+  // the block up to and including seg_mass (no pointer tables), ir_shared_attn_table_args, ir_shared_attn_bias_args or
+  // ir_shared_attn_ragged_args; nothing in between
   if (!attn_block_size_ok(a->struct_size))
-    return fail(IR_ERR_INVALID_ARG, "struct_size %u != %zu, %zu or %zu (ABI mismatch)", a->struct_size, sizeof(ir_shared_attn_args),
-                sizeof(ir_shared_attn_table_args), sizeof(ir_shared_attn_bias_args));
+    return fail(IR_ERR_INVALID_ARG, "struct_size %u != %zu, %zu, %zu or %zu (ABI mismatch)", a->struct_size, sizeof(ir_shared_attn_args),
+                sizeof(ir_shared_attn_table_args), sizeof(ir_shared_attn_bias_args), sizeof(ir_shared_attn_ragged_args));
   const ir_shared_attn_table_args* ta = a->struct_size >= sizeof(ir_shared_attn_table_args) ? (const ir_shared_attn_table_args*)a : nullptr;
-  const ir_shared_attn_bias_args* ba = a->struct_size == sizeof(ir_shared_attn_bias_args) ? (const ir_shared_attn_bias_args*)a : nullptr;
+  const ir_shared_attn_bias_args* ba = a->struct_size >= sizeof(ir_shared_attn_bias_args) ? (const ir_shared_attn_bias_args*)a : nullptr;
+  const ir_shared_attn_ragged_args* ra = a->struct_size == sizeof(ir_shared_attn_ragged_args) ? (const ir_shared_attn_ragged_args*)a : nullptr;
   const float* kbias = ba != nullptr ? ba->key_bias : nullptr;
+  const int32_t* rlens = ra != nullptr ? ra->ref_lens : nullptr;
   const void* const* ktab = ta != nullptr ? ta->k_ref_table : nullptr;
   const void* const* vtab = ta != nullptr ? ta->v_ref_table : nullptr;
   const bool tables = ktab != nullptr;
@@ -93,6 +97,23 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
       return fail(IR_ERR_UNSUPPORTED, "key_bias: tuning %d has no BIAS form (IR_TUNE_DEFAULT, IR_TUNE_PIPE32_PRESCALE_Q or IR_TUNE_PIPE32_EARLYQK: the "
                   "32-row kernel runs every call with a key bias)", a->tuning);
   }
+  if (rlens != nullptr) {
+    if (!fwd)
+      return fail(IR_ERR_UNSUPPORTED, "ref_lens: ir_attn_probs[_ex], ir_attn_segment_mass and ir_attn_rows do not take per-reference counts yet (they would "
+                  "walk the tails behind the counts); the forward's seg_mass by-product does");
+    if ((reinterpret_cast<uintptr_t>(rlens) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "ref_lens must be 4-byte aligned");
+    if (a->n_refs == 0) return fail(IR_ERR_UNSUPPORTED, "ref_lens with n_refs == 0: there is no reference to count");
+    if (ra->rl_sb < a->n_refs) return fail(IR_ERR_INVALID_ARG, "ref_lens row stride rl_sb %lld must be >= n_refs %d", (long long)ra->rl_sb, a->n_refs);
+    if (a->valid_refs != nullptr)
+      return fail(IR_ERR_UNSUPPORTED, "ref_lens together with valid_refs: a count of 0 says the reference is absent, valid_refs says it is zero-filled "
+                  "(exp(0) per key) - pass one of the two");
+    if (kbias != nullptr)
+      return fail(IR_ERR_UNSUPPORTED, "ref_lens together with key_bias: the bias indexes the packed uniform key axis (len_ref keys per reference); counts "
+                  "with a bias are a follow-up");
+    if (a->tuning != IR_TUNE_DEFAULT && a->tuning != IR_TUNE_PIPE32_PRESCALE_Q && a->tuning != IR_TUNE_PIPE32_EARLYQK)
+      return fail(IR_ERR_UNSUPPORTED, "ref_lens: tuning %d has no RAGGED form (IR_TUNE_DEFAULT, IR_TUNE_PIPE32_PRESCALE_Q or IR_TUNE_PIPE32_EARLYQK: the "
+                  "32-row kernel runs every call with per-reference counts)", a->tuning);
+  }
   const void* ptrs[] = {a->q, a->k_self, a->v_self, a->k_ref, a->v_ref, a->out, a->adain_a, a->adain_b};
   for (const void* q : ptrs)
     if (q != nullptr && !aligned16(q)) return fail(IR_ERR_UNSUPPORTED, "pointer %p is not 16-byte aligned", q);
@@ -133,6 +154,7 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
   }
   p->include_self = inc ? 1 : 0;
   if (kbias != nullptr) { p->key_bias = kbias; p->kb_sb = ba->kb_sb; p->kb_sh = ba->kb_sh; }
+  if (rlens != nullptr) { p->ref_lens = rlens; p->rl_sb = ra->rl_sb; }
   p->q_prescaled = (a->flags & IR_FLAG_Q_PRESCALED) ? 1 : 0;
   p->out_f32 = (a->flags & IR_FLAG_OUT_F32) ? 1 : 0;
   if (p->q_prescaled && ((a->tuning >> 5) != 0 || !ir_attn_variant(a->tuning)->presc_q))   // (the availability test above found the row)
@@ -190,6 +212,7 @@ AttnKParams batch_slice(const AttnKParams& p, int b0, int nb) {
   if (p.seg_cum != nullptr) q.seg_cum = p.seg_cum + (int64_t)b0 * p.H * p.Lq * p.nseg_out;
   if (p.valid != nullptr) q.valid = p.valid + b0;
   if (p.key_bias != nullptr) q.key_bias = p.key_bias + (int64_t)b0 * p.kb_sb;
+  if (p.ref_lens != nullptr) q.ref_lens = p.ref_lens + (int64_t)b0 * p.rl_sb;
   return q;
 }
 
@@ -271,9 +294,9 @@ const char* ir_shared_attn_kernel_name(const ir_shared_attn_args* args) {
   }
   if (head == nullptr) return "shared_attn_fwd (tuning variant)";
   static thread_local char name[256];
-  int n = snprintf(name, sizeof(name), "%s%s%s%s%s%s>", head, fold ? fold_text : "", forms && p.valid != nullptr ? ", zero suffix in closed form" : "",
+  int n = snprintf(name, sizeof(name), "%s%s%s%s%s%s%s>", head, fold ? fold_text : "", forms && p.valid != nullptr ? ", zero suffix in closed form" : "",
                    forms && p.seg_cum != nullptr ? ", segment masses" : "", bi && c.family == IR_FAM_W128_FORMS ? ", forms" : "",
-                   p.key_bias != nullptr ? ", key bias (reference follows every max)" : "");
+                   p.key_bias != nullptr ? ", key bias (reference follows every max)" : "", p.ref_lens != nullptr ? ", ragged refs (per-reference counts)" : "");
   if (bi) {   // the plan's cut; the name does not change with seg_mass (the output does not either)
     const IrAttnBiPlan pl = bi_plan_of(args, p);
     snprintf(name + n, sizeof(name) - n, " [batch-invariant: %d piece%s per %d-row item]", pl.pieces, pl.pieces > 1 ? "s" : "", pl.rows);
@@ -548,6 +571,50 @@ int ir_zero_invalid_refs(int32_t batch, int32_t heads, int32_t n_refs, int32_t l
   p.B = batch; p.H = heads; p.N = n_refs; p.L = len;
   const hipError_t e = ir_launch_zero_refs(p, (hipStream_t)stream);
   if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "zero_refs launch: %s", hipGetErrorString(e));
+  return IR_OK;
+}
+
+int ir_compact_ref_tokens(int32_t dtype, int32_t batch, int32_t heads, int32_t n_refs, int32_t len_ref,
+                          const void* k_in, int64_t ki_sb, int64_t ki_sn, int64_t ki_sl, int64_t ki_sh,
+                          const void* v_in, int64_t vi_sb, int64_t vi_sn, int64_t vi_sl, int64_t vi_sh,
+                          const uint8_t* keep,
+                          void* k_out, int64_t ko_sb, int64_t ko_sn, int64_t ko_sl, int64_t ko_sh,
+                          void* v_out, int64_t vo_sb, int64_t vo_sn, int64_t vo_sl, int64_t vo_sh,
+                          int32_t* ref_lens, int64_t rl_sb, void* stream) {
+  if (dtype != IR_DTYPE_F16 && dtype != IR_DTYPE_BF16) return fail(IR_ERR_UNSUPPORTED, "dtype %d", dtype);
+  if (batch <= 0 || heads <= 0 || n_refs <= 0 || len_ref <= 0) return fail(IR_ERR_INVALID_ARG, "sizes must be > 0");
+  if (!k_in || !v_in || !keep || !k_out || !v_out || !ref_lens) return fail(IR_ERR_INVALID_ARG, "NULL pointer");
+  if (!aligned16(k_in) || !aligned16(v_in) || !aligned16(k_out) || !aligned16(v_out)) return fail(IR_ERR_UNSUPPORTED, "k/v must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(ref_lens) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "ref_lens must be 4-byte aligned");
+  if (rl_sb < n_refs) return fail(IR_ERR_INVALID_ARG, "ref_lens row stride rl_sb %lld must be >= n_refs %d", (long long)rl_sb, n_refs);
+  const int64_t st[] = {ki_sb, ki_sn, ki_sl, ki_sh, vi_sb, vi_sn, vi_sl, vi_sh, ko_sb, ko_sn, ko_sl, ko_sh, vo_sb, vo_sn, vo_sl, vo_sh};
+  for (int64_t s : st) if (!stride_ok(s)) return fail(IR_ERR_UNSUPPORTED, "stride %lld must be a non-negative multiple of 8", (long long)s);
+  if ((int64_t)batch * n_refs > 0x7fffffffLL) return fail(IR_ERR_UNSUPPORTED, "grid too large");
+  {
+    // no aliasing: the byte span of each output (first to last element the strides reach) must not meet the span of an input or of the
+    // other output - a kernel that reads rows another workgroup has already overwritten would not be deterministic.  Spans, not
+    // elements: outputs interleaved with anything else in one allocation are refused too
+    struct Span { uintptr_t lo, hi; };
+    auto span = [&](const void* base, int64_t sb, int64_t sn, int64_t sl, int64_t sh) {
+      const int64_t last = (int64_t)(batch - 1) * sb + (int64_t)(n_refs - 1) * sn + (int64_t)(len_ref - 1) * sl + (int64_t)(heads - 1) * sh + 64;
+      return Span{reinterpret_cast<uintptr_t>(base), reinterpret_cast<uintptr_t>(base) + (uintptr_t)last * 2};
+    };
+    auto meet = [](Span a, Span b) { return a.lo < b.hi && b.lo < a.hi; };
+    const Span ki = span(k_in, ki_sb, ki_sn, ki_sl, ki_sh), vi = span(v_in, vi_sb, vi_sn, vi_sl, vi_sh);
+    const Span ko = span(k_out, ko_sb, ko_sn, ko_sl, ko_sh), vo = span(v_out, vo_sb, vo_sn, vo_sl, vo_sh);
+    if (meet(ko, ki) || meet(ko, vi) || meet(vo, ki) || meet(vo, vi) || meet(ko, vo))
+      return fail(IR_ERR_INVALID_ARG, "ir_compact_ref_tokens: the byte spans of the outputs must not overlap the inputs or each other (no aliasing)");
+  }
+  CompactRefsKParams p;
+  memset(&p, 0, sizeof(p));
+  p.k_in = k_in; p.v_in = v_in; p.k_out = k_out; p.v_out = v_out; p.keep = keep; p.ref_lens = ref_lens; p.rl_sb = rl_sb;
+  p.ki_sb = ki_sb; p.ki_sn = ki_sn; p.ki_sl = ki_sl; p.ki_sh = ki_sh;
+  p.vi_sb = vi_sb; p.vi_sn = vi_sn; p.vi_sl = vi_sl; p.vi_sh = vi_sh;
+  p.ko_sb = ko_sb; p.ko_sn = ko_sn; p.ko_sl = ko_sl; p.ko_sh = ko_sh;
+  p.vo_sb = vo_sb; p.vo_sn = vo_sn; p.vo_sl = vo_sl; p.vo_sh = vo_sh;
+  p.B = batch; p.H = heads; p.N = n_refs; p.L = len_ref;
+  const hipError_t e = ir_launch_compact_refs(p, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "compact_refs launch: %s", hipGetErrorString(e));
   return IR_OK;
 }
 

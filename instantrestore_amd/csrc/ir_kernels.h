@@ -73,6 +73,11 @@ struct AttnKParams {
   // (shared_attn_fwd_pipe_bias.hip); appended, so no other kernel's arguments move
   const float* key_bias;
   int64_t kb_sb, kb_sh;
+  // per-reference token counts (ir_shared_attn_ragged_args): reference n of entry b has clamp(ref_lens[b * rl_sb + n], 0, Lr) keys;
+  // Lr is the capacity of a segment (allocation, strides).  nullptr: every reference has Lr keys.  Read by the RAGGED forms of the
+  // 32-row kernel only (shared_attn_fwd_pipe_ragged.hip), when they run; appended, so no other kernel's arguments move
+  const int32_t* ref_lens;
+  int64_t rl_sb;
 };
 
 // The base address (head 0, token 0) of a reference segment from `at` = k_ref + b * kr_sb + n * kr_sn: `at` itself in the dense
@@ -178,6 +183,7 @@ struct ZeroRefsKParams {
 hipError_t ir_launch_shared_attn_fwd(const AttnKParams& p, int dtype, int variant, hipStream_t s);
 hipError_t ir_launch_shared_attn_fwd_pipe(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s);
 hipError_t ir_launch_shared_attn_fwd_pipe_bias(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s);   // key_bias: PRESC / EARLYQK (shared_attn_fwd_pipe_bias.hip)
+hipError_t ir_launch_shared_attn_fwd_pipe_ragged(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s);   // ref_lens: PRESC / EARLYQK (shared_attn_fwd_pipe_ragged.hip)
 hipError_t ir_launch_shared_attn_fwd_pipe_abl(const AttnKParams& p, int abl, hipStream_t s);
 hipError_t ir_launch_shared_attn_combine(const AttnKParams& p, int dtype, int qb, int rem, hipStream_t s);
 hipError_t ir_launch_shared_attn_fwd_w64(const AttnKParams& p, int dtype, hipStream_t s);
@@ -227,6 +233,22 @@ hipError_t ir_launch_bench_mfma_stream(int dtype, int zero, int iters, int block
 int ir_adain_partials_max_chunks(void);   // partials per matrix the merge kernels hold in registers (len / rows <= this)
 hipError_t ir_launch_adain_apply(const AdainApplyKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_zero_refs(const ZeroRefsKParams& p, hipStream_t s);
+// compact_refs.hip: stable compaction of the kept token rows of every reference to the front of its output segment
+struct CompactRefsKParams {
+  const void* k_in;
+  const void* v_in;
+  void* k_out;
+  void* v_out;
+  const uint8_t* keep;   // (B, N, L) contiguous, non-zero = kept
+  int32_t* ref_lens;     // (B, N) rows rl_sb apart: the counts
+  int64_t rl_sb;
+  int64_t ki_sb, ki_sn, ki_sl, ki_sh;
+  int64_t vi_sb, vi_sn, vi_sl, vi_sh;
+  int64_t ko_sb, ko_sn, ko_sl, ko_sh;
+  int64_t vo_sb, vo_sn, vo_sl, vo_sh;
+  int B, H, N, L;
+};
+hipError_t ir_launch_compact_refs(const CompactRefsKParams& p, hipStream_t s);
 hipError_t ir_launch_tensor2im(const void* x, void* out, int dtype, int64_t sb, int64_t sc, int64_t sh, int64_t sw,
                                int B, int C, int H, int W, hipStream_t s);
 

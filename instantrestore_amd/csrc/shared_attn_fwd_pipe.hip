@@ -55,6 +55,14 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
   // place.  A masked key (-inf or <= IR_KEY_BIAS_MASKED) is -inf in the C operand: -inf leaves the matrix pipe, before any row max.
   constexpr bool BIAS = (ABL & 16384) != 0;
   static_assert(!BIAS || (!CHK && (ABL & 256) == 0 && (ABL & 128) != 0 && ((ABL & 2048) != 0) != ((ABL & 4096) != 0)), "the key bias is built into the PRESC and EARLYQK forms only");
+  // RAGGED (ir_shared_attn_ragged_args.ref_lens; the PRESC and EARLYQK forms, instantiated in shared_attn_fwd_pipe_ragged.hip): reference
+  // n of this batch entry has c_n = clamp(ref_lens[b, n], 0, Lr) keys and ceil(c_n / 64) tiles; Lr is the capacity of its segment.
+  // Only what is wave-uniform and outside the tile loop changes: the item's tile count, where a piece's first tile lies, the length
+  // and tile count a segment is set up with (its descriptors end at the count: the bounds check zero-fills the last tile's rows
+  // behind it and the ragged-tail -inf of step (1) masks them), and the step to the next segment, which passes over c_n == 0
+  // without a descriptor, a load or a fold.  The counts come through the constant address space, as table entries do.
+  constexpr bool RAGGED = (ABL & 32768) != 0;
+  static_assert(!RAGGED || (!BIAS && !CHK && (ABL & 256) == 0 && (ABL & 128) != 0 && ((ABL & 2048) != 0) != ((ABL & 4096) != 0)), "per-reference counts are built into the PRESC and EARLYQK forms only");
   constexpr int KRING = CHK ? 3 : 2;
   constexpr int K_OFF = 0;                       // K ring: 2 tiles (3 with CHK)
   constexpr int V_OFF = KRING * TILE_BYTES;      // V ring: 3 tiles
@@ -95,7 +103,23 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
     const int vb = p.valid[b];
     nref = vb < 0 ? 0 : (vb < p.N ? vb : p.N);
   }
-  const int ntiles_b = p.tiles_self + nref * p.tiles_ref;
+  // Parameters that are needed at segment boundaries only are read from the kernel-argument segment through a pointer the compiler
+  // cannot see through, so nothing of them stays in registers across the tile loop (the seg_mass stores and the counts use it)
+  typedef const __attribute__((address_space(4))) AttnKParams* KArgs;
+  auto cold = [&]() -> KArgs { KArgs q = (KArgs)__builtin_amdgcn_kernarg_segment_ptr(); asm volatile("" : "+s"(q)); return q; };
+  auto seg_keys = [&](int s) {     // RAGGED: keys of segment s (one scalar load through the constant address space, as ir_ref_entry's)
+    typedef const __attribute__((address_space(4))) int32_t* ConstCounts;
+    const KArgs a = cold();
+    if (a->include_self && s == 0) return a->Ls;
+    const int c = *(ConstCounts)(uintptr_t)(a->ref_lens + (int64_t)b * a->rl_sb + (s - a->include_self));
+    return c < 0 ? 0 : (c < a->Lr ? c : a->Lr);
+  };
+  int ntiles_b = p.tiles_self + nref * p.tiles_ref;
+  if (RAGGED) {
+    ntiles_b = p.tiles_self;
+#pragma nounroll
+    for (int n = 0; n < p.N; ++n) ntiles_b += (seg_keys(p.include_self + n) + KVB - 1) / KVB;
+  }
   const int tile_begin = (int)(((long)ntiles_b * piece) / npiece);
   const int tile_end = (int)(((long)ntiles_b * (piece + 1)) / npiece);
 
@@ -165,6 +189,7 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
       sk = ir_ref_entry((const T*)p.k_ref + (int64_t)b * p.kr_sb + (int64_t)n * p.kr_sn, p.ref_tables) + (int64_t)h * p.kr_sh;
       sv = ir_ref_entry((const T*)p.v_ref + (int64_t)b * p.vr_sb + (int64_t)n * p.vr_sn, p.ref_tables) + (int64_t)h * p.vr_sh;
       ksl_b = (int)p.kr_sl * 2; vsl_b = (int)p.vr_sl * 2; slen = p.Lr; sntile = p.tiles_ref;
+      if (RAGGED) { slen = seg_keys(s); sntile = (slen + KVB - 1) / KVB; }   // (never 0: the walk steps over an empty reference)
     }
     krs = __builtin_amdgcn_make_buffer_rsrc((void*)sk, 0, (slen - 1) * ksl_b + 128, 0x00020000);
     vrs = __builtin_amdgcn_make_buffer_rsrc((void*)sv, 0, (slen - 1) * vsl_b + 128, 0x00020000);
@@ -222,7 +247,9 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
   auto advance = [&]() {
     if (++t0 == sntile) {
       t0 = 0;
-      if (++seg < nseg) seg_setup(seg);
+      ++seg;
+      if (RAGGED) while (seg < nseg && seg_keys(seg) == 0) ++seg;   // an absent reference: no descriptor, no load
+      if (seg < nseg) seg_setup(seg);
     }
   };
 
@@ -258,6 +285,7 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
   // carries a row has probability exactly 1 and takes no 16-bit rounding of its own (with the lazy reference two of 118 bf16
   // comparisons of tests/test_gpu_key_bias.py left the regression bound: 1.01 and 1.06 of it, 0.53 with the exact reference)
   const float lazy_thr = BIAS ? 0.f : (PRESC ? 6.0f : 6.0f / c2);
+  float cum_last = -INFINITY;               // RAGGED + MASS: the cumulative value stored last - an absent reference repeats it
   bool started = false;                     // BIAS + PRESC: a tile with an unmasked key has set the reference (wave-uniform: the bias has no query axis)
   // BIAS: loaded bias -> exponent units of the scores as they leave the matrix pipe (PRESC: exp2 domain; else raw scores, scaled by c2 later)
   const float kb_mul = (ABL & 2048) != 0 ? 1.4426950408889634f : 1.4426950408889634f / c2;
@@ -274,10 +302,24 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
     seg_b = p.include_self + r / p.tiles_ref;
     t0_b = r - (r / p.tiles_ref) * p.tiles_ref;
   }
+  if (RAGGED) {   // the segment that holds tile_begin: a short scan over the counts (an empty piece ends up behind the last segment)
+    seg_b = 0;
+    t0_b = tile_begin;
+#pragma nounroll
+    for (; seg_b < nseg; ++seg_b) {
+      const int nt = (seg_keys(seg_b) + KVB - 1) / KVB;
+      if (t0_b < nt) break;
+      t0_b -= nt;
+    }
+  }
   int cseg = seg_b, ct0 = t0_b;
   const bool first_is_self = (p.include_self && seg_b == 0);
   int c_ntile = first_is_self ? p.tiles_self : p.tiles_ref;
   int c_len = first_is_self ? p.Ls : p.Lr;
+  if (RAGGED) {
+    c_len = seg_b < nseg ? seg_keys(seg_b) : 0;
+    c_ntile = (c_len + KVB - 1) / KVB;
+  }
 
   constexpr bool NOPIPE = (ABL & 256) != 0;  // no S double buffer: fewer VGPRs, three waves per SIMD (implies asm DMA)
   constexpr bool DMA = (ABL & (64 | 128 | 256)) != 0;    // global->LDS staging by LDS-DMA (buffer_load ... lds), no registers (real variant)
@@ -329,11 +371,10 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
   };
   // ABI v9 (seg_mass): cumulative log-sum-exp through segment s of this lane pair's row (log2 units) -> seg_cum, or this
   // piece's slot of ws_cum (shared_attn_fwd_w64.hip has the scheme).  The parameters are read from the kernel-argument segment
-  // through a pointer the compiler cannot see through, so nothing of this stays in registers across the tile loop.
-  typedef const __attribute__((address_space(4))) AttnKParams* KArgs;
-  auto cold = [&]() -> KArgs { KArgs q = (KArgs)__builtin_amdgcn_kernarg_segment_ptr(); asm volatile("" : "+s"(q)); return q; };
+  // through a pointer the compiler cannot see through (cold(), above), so nothing of this stays in registers across the tile loop.
   auto cum_store = [&](int s, float v2) {
     const KArgs c = cold();
+    if (RAGGED) cum_last = v2;
     if (hi != 0) return;
     if (npiece > 1) {
       const int64_t prow = ((int64_t)((xcd * (c->sk_ix - c->sk_full) + (item_local - c->sk_full)) * npiece + piece)) * QB + wid * 32 + lq;
@@ -590,6 +631,15 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
       ++cseg;
       c_ntile = p.tiles_ref;
       c_len = p.Lr;
+      if constexpr (RAGGED) {   // step over absent references: nothing to fold (l_s = 0), the cumulative value stays what it was
+        // (`if constexpr`: what this block names must not become a capture of `step` in the other instantiations - their code is to stay as it was)
+        while (cseg < nseg && seg_keys(cseg) == 0) {
+          if (MASS) cum_store(cseg, cum_last);
+          ++cseg;
+        }
+        c_len = cseg < nseg ? seg_keys(cseg) : 0;
+        c_ntile = (c_len + KVB - 1) / KVB;
+      }
     }
     // (6) land pair t+2 in LDS
     if (!NOPIPE && has2) {
@@ -608,11 +658,14 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
   // ---- prologue: pairs 0 and 1 into LDS, S(0) ---------------------------------------------------
   seg = seg_b;
   t0 = t0_b;
-  seg_setup(seg);
+  if (!RAGGED || NTILES > 0) seg_setup(seg);   // RAGGED: an empty piece (an item without keys among them) touches no segment
 #pragma unroll
   for (int c = 0; c < CH; ++c) { kvo[c] += (unsigned)(t0 * kstep); vvo[c] += (unsigned)(t0 * vstep); }
   f32x16 sa0, sa1, sb0, sb1;
-  if (DMA) {
+  if (RAGGED && NTILES == 0) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { sa0[r] = 0.f; sa1[r] = 0.f; sb0[r] = 0.f; sb1[r] = 0.f; }
+  } else if (DMA) {
     if (BIAS) bias_load(sa0, sa1);
     issue_dma(0, 0);
     advance();
@@ -675,7 +728,12 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
   constexpr bool want_cum = MASS;
   if (!FOLD && want_cum && mid) cum_store(cseg, ref_log2() + __log2f(row_sum_now()));
   const int s_next = cseg + (mid ? 1 : 0);        // first segment whose cumulative value this piece has not stored yet
-  if (want_cum && npiece > 1)
+  // RAGGED: the piece's total AS IT WAS STORED for its last segment (-inf: an empty piece).  The absent references right behind the
+  // range repeat these bits: formed again below (the reference times c2 kept in a variable there, contracted into a multiply-add
+  // above) the total can differ in its last place, and an absent reference would show that as a mass of 1e-6 instead of 0.  From
+  // the first reference WITH keys on the value is the one formed below, as in the form without counts (full counts: its bytes)
+  const float cum_tot = cum_last;
+  if (want_cum && (npiece > 1 || RAGGED))                       // (RAGGED: also the absent references a whole item starts with)
     for (int s = 0; s < seg_b; ++s) cum_store(s, -INFINITY);   // segments before this piece's range
   float l_pre = -1.f, pz_seg = 0.f;               // zero suffix: row sum before it (final frame), weight of one zero segment
   if (nref < p.N && piece == npiece - 1) {
@@ -737,7 +795,15 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
     const KArgs c = cold();
     const float lp = l_pre < 0.f ? l_fin : l_pre, mref = ref_log2();
     const int sz = c->include_self + nref;
+    bool absent_run = RAGGED;
     for (int s = s_next; s < c->nseg_out; ++s) {
+      if constexpr (RAGGED) {
+        absent_run = absent_run && seg_keys(s) == 0;
+        if (absent_run) {
+          cum_store(s, cum_tot);
+          continue;
+        }
+      }
       const int j = s - sz + 1;
       cum_store(s, mref + __log2f(lp + pz_seg * (float)(j > 0 ? j : 0)));
     }
@@ -770,7 +836,8 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
     }
     return;
   }
-  const float inv = (BIAS && !(l_fin > 0.f)) ? 0.f : 1.0f / l_fin;   // BIAS: every key of the row masked - exact zeros, lse = -inf
+  constexpr bool NOKEY = BIAS || RAGGED;   // a row may have no key at all (BIAS: every key masked; RAGGED: no self block, every count 0)
+  const float inv = (NOKEY && !(l_fin > 0.f)) ? 0.f : 1.0f / l_fin;   // then exact zeros, lse = -inf
   if (qrow < p.Lq) {
     const int64_t ooff = (int64_t)b * p.o_sb + (int64_t)qrow * p.o_sl + (int64_t)h * p.o_sh;
     T* op = (T*)p.out + ooff;
@@ -793,13 +860,14 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
       }
     }
     if (p.lse != nullptr && hi == 0)
-      p.lse[((int64_t)b * p.H + h) * p.Lq + qrow] = (BIAS && !(l_fin > 0.f)) ? -INFINITY : (PRESC ? m_run * 0.69314718f : m_run * p.scale) + __logf(l_fin);
+      p.lse[((int64_t)b * p.H + h) * p.Lq + qrow] = (NOKEY && !(l_fin > 0.f)) ? -INFINITY : (PRESC ? m_run * 0.69314718f : m_run * p.scale) + __logf(l_fin);
   }
 }
 
 // Merge the K/V-range pieces of the remainder items: one workgroup per remainder item, thread =
 // (row, 32-channel half).  out = sum_j w_j O_j / sum_j w_j l_j with w_j = 2^((m_j - M) c).
-// (BIAS: the combine of a call with a key bias - every piece of a row may be empty, all of its keys masked: exact zeros, lse = -inf)
+// (BIAS: the combine of a call with a key bias or with per-reference counts - every piece of a row may be empty, all of its keys
+//  masked or absent: exact zeros, lse = -inf)
 template <typename T, int QB, bool BIAS>
 __device__ __forceinline__ void combine_rows(const AttnKParams p) {
   // grid: (8 * remainder items per XCD, QB / 16); 256 threads = 16 rows x 16 four-channel groups, so a
@@ -871,7 +939,7 @@ hipError_t launch(const AttnKParams& p0, hipStream_t s) {
   hipLaunchKernelGGL((shared_attn_fwd_pipe_kernel<T, NW, FOLD, ABL, MASS>), dim3(pl.grid), dim3(NW * 64), 0, s, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || pl.k <= 1) return e;
-  if ((ABL & 16384) != 0) {   // BIAS
+  if ((ABL & (16384 | 32768)) != 0) {   // BIAS, RAGGED
     hipLaunchKernelGGL((shared_attn_combine_bias_kernel<T, QB>), dim3(kIrXcds * pl.rem, QB / 16), dim3(256), 0, s, p);
     return hipGetLastError();
   }
@@ -909,6 +977,22 @@ hipError_t launch_bias_t(const AttnKParams& p, IrPipeForm form, hipStream_t s) {
 hipError_t ir_launch_shared_attn_fwd_pipe_bias(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s) {
   if (p.key_bias == nullptr || p.valid != nullptr) return hipErrorInvalidValue;
   return dtype == 1 ? launch_bias_t<__bf16>(p, form, s) : launch_bias_t<_Float16>(p, form, s);
+}
+#elif defined(IR_PIPE_RAGGED_TU)   // shared_attn_fwd_pipe_ragged.hip: the RAGGED instantiations and nothing else of this file
+constexpr int kRagged = 32768;
+template <typename T>
+hipError_t launch_ragged_t(const AttnKParams& p, IrPipeForm form, hipStream_t s) {
+  const bool mass = p.seg_cum != nullptr;
+  if (form == IR_PIPE_PRESC) return mass ? launch_f<T, kFormPresc | kRagged, true>(p, s) : launch_f<T, kFormPresc | kRagged>(p, s);
+  if (form == IR_PIPE_EARLYQK) return mass ? launch_f<T, kFormEarlyQK | kRagged, true>(p, s) : launch_f<T, kFormEarlyQK | kRagged>(p, s);
+  return hipErrorInvalidValue;
+}
+
+}  // namespace
+
+hipError_t ir_launch_shared_attn_fwd_pipe_ragged(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s) {
+  if (p.ref_lens == nullptr || p.valid != nullptr || p.key_bias != nullptr || p.N <= 0) return hipErrorInvalidValue;
+  return dtype == 1 ? launch_ragged_t<__bf16>(p, form, s) : launch_ragged_t<_Float16>(p, form, s);
 }
 #else
 template <typename T>
@@ -979,4 +1063,4 @@ hipError_t ir_launch_shared_attn_combine(const AttnKParams& p, int dtype, int qb
 hipError_t ir_launch_shared_attn_fwd_pipe(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s) {
   return dtype == 1 ? launch_t<__bf16>(p, form, s) : launch_t<_Float16>(p, form, s);
 }
-#endif  // IR_PIPE_BIAS_TU
+#endif  // IR_PIPE_BIAS_TU / IR_PIPE_RAGGED_TU

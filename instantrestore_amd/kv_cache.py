@@ -32,6 +32,7 @@ class ReferenceKVCache:
             raise ValueError("max_identities must be >= 1")
         self.max_identities = max_identities
         self._store: "OrderedDict[Hashable, KV]" = OrderedDict()
+        self._lens = {}   # identity -> per-layer token counts of its references (set_ref_lens); absent: every reference is full
         self.hits = 0
         self.misses = 0
 
@@ -75,9 +76,42 @@ class ReferenceKVCache:
         if stats is not None:
             entry = entry + ([None if st is None else (st[0].detach().clone(), st[1].detach().clone()) for st in stats],)
         self._store[identity] = entry
+        self._lens.pop(identity, None)   # a recomputed entry is full again
         while len(self._store) > self.max_identities:
-            self._store.popitem(last=False)
+            self._lens.pop(self._store.popitem(last=False)[0], None)
         return entry
+
+    def set_ref_lens(self, identity: Hashable, ref_lens) -> None:
+        """per-layer token counts of a cached identity's references: a list with, per layer, ``N`` integers (or an int tensor of ``N``
+        elements, e.g. a row of ``ops.compact_refs``' counts - read back once, here) or ``None`` for a layer whose references are
+        full.  The entry's tensors keep their shape: the token axis is the capacity, the kept rows lie in front.  ``None`` drops
+        the counts.  :meth:`assemble_tables` hands them to the attention call as ``ref_lens``."""
+        entry = self._store[identity]
+        if ref_lens is None:
+            self._lens.pop(identity, None)
+            return
+        if len(ref_lens) != len(entry[0]):
+            raise ValueError(f"set_ref_lens(): {len(entry[0])} layers are cached, got counts for {len(ref_lens)}")
+        rows = []
+        for l, c in enumerate(ref_lens):
+            n, cap = int(entry[0][l].shape[1]), int(entry[0][l].shape[2])
+            if c is None:
+                rows.append([cap] * n)
+                continue
+            c = [int(x) for x in (c.reshape(-1).tolist() if isinstance(c, torch.Tensor) else c)]
+            if len(c) != n or any(x < 0 or x > cap for x in c):
+                raise ValueError(f"set_ref_lens(): layer {l} needs {n} counts in [0, {cap}], got {c}")
+            rows.append(c)
+        self._lens[identity] = rows
+
+    def _count_rows(self, identities, entries, counts, n_refs: int):
+        """host side of the per-layer ``(B, N)`` counts: an identity's own counts, the capacity for one without, 0 for a slot it does
+        not have"""
+        out = []
+        for l in range(len(entries[0][0])):
+            cap = int(entries[0][0][l].shape[2])
+            out.append([(self._lens[i][l] if i in self._lens else [cap] * c) + [0] * (n_refs - c) for i, c in zip(identities, counts)])
+        return out
 
     def assemble(self, identities: Sequence[Hashable]) -> KV:
         """``(B, N, L, C)`` lists for a batch of cached identities (raises KeyError on a miss)."""
@@ -112,9 +146,10 @@ class ReferenceKVCache:
         return entries, counts, max(max(counts), n_max), all(with_stats)
 
     @staticmethod
-    def _table_words(entries, counts, n_refs: int):
+    def _table_words(entries, counts, n_refs: int, lens_rows):
         """the int64 words of one table set: 2 * layers * B * N addresses (keys of every layer, then values; an unused slot points
-        at its identity's reference 0), then the B valid counts packed as int32 pairs"""
+        at its identity's reference 0), then the B valid counts packed as int32 pairs, then the layers * B * N per-reference token
+        counts (``lens_rows``: :meth:`_count_rows`) packed the same way"""
         n_layers = len(entries[0][0])
         words = []
         for side in (0, 1):
@@ -126,6 +161,9 @@ class ReferenceKVCache:
                     words += [t[0, n if n < c else 0].data_ptr() for n in range(n_refs)]
         valid = counts + [0] * (len(counts) % 2)
         words += [valid[i] | (valid[i + 1] << 32) for i in range(0, len(valid), 2)]     # little-endian int32 pairs
+        flat = [c for layer in lens_rows for row in layer for c in row]
+        flat += [0] * (len(flat) % 2)
+        words += [flat[i] | (flat[i + 1] << 32) for i in range(0, len(flat), 2)]
         return words
 
     @staticmethod
@@ -142,7 +180,7 @@ class ReferenceKVCache:
     def assemble_tables(self, identities: Sequence[Hashable]):
         """:meth:`assemble` without the copy: per layer an :class:`instantrestore_amd.ops.RefKVTable` of pointers INTO the cached
         entries instead of a dense ``(B, N, L, C)`` tensor.  Nothing of K/V size is allocated or moved: the pointer arrays of all
-        layers (keys and values) and the valid counts live in one int64 device tensor filled by one host-to-device copy, and each
+        layers (keys and values), the valid counts and the per-reference token counts live in one int64 device tensor filled by one host-to-device copy, and each
         table keeps the entries it points into alive (an evicted or invalidated identity stays readable while a table holds it).
 
         Identities cached with different numbers of references may share a batch: ``N`` is the largest count, unused slots point at
@@ -150,12 +188,20 @@ class ReferenceKVCache:
 
         Returns ``(keys, values, stats, valid)``: ``stats`` as :meth:`assemble` returns them (``None`` when the identities were
         cached without), ``valid`` an int32 ``(B,)`` device tensor to hand over as ``ref_valid`` when the counts differ, ``None``
-        when every identity has ``N`` references (the call then is the dense call's, kernel for kernel)."""
+        when every identity has ``N`` references (the call then is the dense call's, kernel for kernel).
+
+        Per-reference token counts ride beside the tables: ``keys.ref_lens`` is a list with one int32 ``(B, N)`` device tensor per
+        layer - an identity's :meth:`set_ref_lens` counts, ``len_ref`` for an identity without, 0 for a slot it does not have -
+        to hand over as ``ref_lens`` INSTEAD of ``ref_valid`` (a missing slot is then absent, not zero-filled; without ``ref_lens``
+        those slots keep the meaning they have today).  They are views into the set's one pointer block: no copy of their own, and
+        :meth:`refill_tables` refills them in place with the same upload.  Counts given to :meth:`set_ref_lens` AFTER this call reach
+        the device with the next :meth:`refill_tables`, not before.  The list hangs on the returned key list: hand ``keys`` itself (not
+        ``list(keys)``) to :meth:`refill_tables`."""
         from .ops import RefKVTable, _PinnedStage
 
         entries, counts, n_refs, with_stats = self._table_plan(identities)
         n_layers, B = len(entries[0][0]), len(entries)
-        words = self._table_words(entries, counts, n_refs)
+        words = self._table_words(entries, counts, n_refs, self._count_rows(identities, entries, counts, n_refs))
         first = entries[0][0][0]
         buf = torch.empty(len(words), dtype=torch.int64, device=first.device)
         if first.is_cuda:
@@ -178,12 +224,16 @@ class ReferenceKVCache:
         stats = [self._table_stats(entries, counts, n_refs, l) for l in range(n_layers)] if with_stats else None
         keys = _TableList(tables[0])
         keys.buf, keys.stage, keys.valid_all = buf, stage, valid_all
+        n_ptr, n_valid = 2 * n_layers * B * n_refs, (B + 1) // 2
+        lens = buf[n_ptr + n_valid:].view(torch.int32)[:n_layers * B * n_refs].view(n_layers, B, n_refs)   # views: the block's one upload fills them
+        keys.ref_lens = [lens[l] for l in range(n_layers)]
         return keys, tables[1], stats, (valid_all if min(counts) < n_refs else None)
 
     def refill_tables(self, tables, identities: Sequence[Hashable]) -> None:
         """point the set returned by :meth:`assemble_tables` at other identities IN PLACE - pointer arrays, valid counts and
         statistics keep their addresses, so a captured step that reads them serves the new identities on its next replay.  One
-        host-to-device copy of the pointer block (plus the statistics' few KB).  Same batch size; no identity may have more
+        host-to-device copy of the pointer block - addresses, valid counts and the per-reference token counts of ``keys.ref_lens``
+        (the identities' :meth:`set_ref_lens` counts as they are now) - plus the statistics' few KB.  Same batch size; no identity may have more
         references than the set's N, and a set assembled without ``valid`` takes identities of exactly N references only."""
         keys, values, stats, valid = tables
         n_layers, (B, n_refs) = len(keys), keys[0].shape[:2]
@@ -195,7 +245,9 @@ class ReferenceKVCache:
                              "assemble a new one for identities with fewer")
         if with_stats != (stats is not None):
             raise ValueError("refill_tables(): the set and the identities differ in whether they carry AdaIN content statistics")
-        words = self._table_words(entries, counts, n_refs)
+        if not isinstance(keys, _TableList) or not hasattr(keys, "ref_lens"):
+            raise ValueError("refill_tables(): pass the key list assemble_tables() returned itself (it carries the set's pointer block and counts)")
+        words = self._table_words(entries, counts, n_refs, self._count_rows(identities, entries, counts, n_refs))
         if keys.stage is not None:
             with torch.cuda.device(keys.buf.device):
                 keys.stage.upload(words, keys.buf)
@@ -222,5 +274,7 @@ class ReferenceKVCache:
     def invalidate(self, identity: Hashable = None) -> None:
         if identity is None:
             self._store.clear()
+            self._lens.clear()
         else:
             self._store.pop(identity, None)
+            self._lens.pop(identity, None)

@@ -248,8 +248,10 @@ def _is_table(t) -> bool:
 
 
 def _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, lse, split=True,
-               q_prescaled=False, valid_refs=None, batch_invariant=False, key_bias=None):
-    a = _lib.SharedAttnBiasArgs() if key_bias is not None else _lib.SharedAttnTableArgs() if _is_table(ref_k) else _lib.SharedAttnArgs()
+               q_prescaled=False, valid_refs=None, batch_invariant=False, key_bias=None, ref_lens=None):
+    if ref_lens is not None:   # validated before anything else is touched
+        _check_ref_lens(ref_lens, q, ref_k, valid_refs, key_bias)
+    a = _lib.SharedAttnRaggedArgs() if ref_lens is not None else _lib.SharedAttnBiasArgs() if key_bias is not None else _lib.SharedAttnTableArgs() if _is_table(ref_k) else _lib.SharedAttnArgs()
     a.struct_size = C.sizeof(a)
     a.dtype = _dtype_code(q)
     a.flags = (_lib.IR_FLAG_INCLUDE_SELF if include_self else 0) | (_lib.IR_FLAG_Q_PRESCALED if q_prescaled else 0)
@@ -289,6 +291,9 @@ def _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adai
             raise ValueError("key_bias with valid_refs on a RefKVTable call: slots n >= valid_refs[b] of the table are not readable, and the kernel "
                              "with a key bias walks every reference (mask them in the bias and fill the slots, or pass dense tensors)")
         valid_refs = None   # dense: the promise is about the DATA (all-zero references) - walking the zeros gives the same numbers
+    if ref_lens is not None:
+        a.ref_lens, a.rl_sb = ref_lens.data_ptr(), ref_lens.stride(0)
+        a._keeplens = ref_lens
     if valid_refs is not None and ref_k is not None:
         if valid_refs.dtype != torch.int32 or valid_refs.device != q.device or valid_refs.numel() != q.shape[0] or not valid_refs.is_contiguous():
             raise ValueError(f"valid_refs must be a contiguous int32 ({q.shape[0]},) tensor on {q.device}")
@@ -303,6 +308,26 @@ def _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adai
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
         a._keepalive = ws
     return a
+
+
+def _check_ref_lens(rl, q, ref_k, valid_refs=None, key_bias=None) -> None:
+    """``ref_lens``: int32 ``(B, N)`` on q's device, last axis contiguous (the row stride goes to the kernel as it is); not together
+    with ``valid_refs`` or ``key_bias``"""
+    if not isinstance(rl, torch.Tensor) or rl.dtype != torch.int32:
+        raise ValueError(f"ref_lens must be an int32 tensor, got {getattr(rl, 'dtype', type(rl))}")
+    if ref_k is None:
+        raise ValueError("ref_lens given without references")
+    want = (q.shape[0], ref_k.shape[1])
+    if tuple(rl.shape) != want:
+        raise ValueError(f"ref_lens must have shape (B, N) = {want}, got {tuple(rl.shape)}")
+    if rl.device != q.device:
+        raise ValueError(f"ref_lens is on {rl.device}, q on {q.device}")
+    if rl.stride(-1) != 1 or rl.stride(0) < want[1]:
+        raise ValueError("ref_lens: the reference axis must be contiguous (stride 1) and the rows at least N apart")
+    if valid_refs is not None:
+        raise ValueError("ref_lens with valid_refs: a count of 0 says the reference is absent, valid_refs says it is zero-filled - pass one of the two")
+    if key_bias is not None:
+        raise ValueError("ref_lens with key_bias: the bias indexes the packed uniform key axis; counts together with a bias are a follow-up")
 
 
 def _check_key_bias(kb, q, heads: int, lkv: int) -> None:
@@ -478,7 +503,8 @@ def shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, s
                      include_self: bool = True, adain: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                      return_lse: bool = False, split: bool = True, q_prescaled: bool = False,
                      out_dtype: Optional[torch.dtype] = None, valid_refs: Optional[torch.Tensor] = None,
-                     return_mass: bool = False, batch_invariant: bool = False, key_bias: Optional[torch.Tensor] = None):
+                     return_mass: bool = False, batch_invariant: bool = False, key_bias: Optional[torch.Tensor] = None,
+                     ref_lens: Optional[torch.Tensor] = None):
     """Fused extended self-attention (``ir_shared_attn_fwd``).
 
     Returns ``out`` (B, Lq, H*64) in q's dtype [, ``lse`` (B, H, Lq) fp32] [, ``mass`` (B, H, Lq, include_self + N) fp32:
@@ -508,6 +534,16 @@ def shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, s
     ``valid_refs``: a dense call drops the promise and walks the zeros (same numbers); a table call raises.  AdaIN statistics are
     not masked (the reference's ``adain`` knows no mask).  :func:`attn_probs`, :func:`attn_segment_mass` and :func:`attn_rows`
     take no bias - their ``exp(s - lse)`` would leave it out; ``return_mass`` is the read-back that honours it.
+    ``ref_lens`` (``ir_shared_attn_ragged_args``): int32 ``(B, N)`` on the device, last axis contiguous - reference ``n`` of entry ``b``
+    HAS ``clamp(ref_lens[b, n], 0, len_ref)`` keys, and ``len_ref`` (the tensors' token axis) is only the capacity of its segment.
+    Keys behind the count do not exist: they are never used whatever lies there, ``lse`` and the masses are over the existing keys,
+    a count of 0 is an absent reference (mass 0, its table slot never read), and a ``(b, h)`` without any key gives zeros,
+    ``lse = -inf`` and zero masses.  Read when the kernel runs (a captured call follows in-place updates); always the 32-row kernel,
+    time proportional to the tiles that exist.  :func:`compact_refs` packs kept tokens to the front and returns the counts.
+    ``adain`` is taken as given - for a compacted reference pass the affine of the FULL reference (statistics before compaction).
+    Raises with ``valid_refs`` (absent is not zero-filled) and with ``key_bias`` (the bias indexes the uniform key axis: a
+    follow-up); the C ABI refuses ``n_refs == 0`` and tunings other than the default and the two 32-row forms, and
+    :func:`attn_probs`, :func:`attn_segment_mass` and :func:`attn_rows` take no counts (``return_mass`` honours them).
     """
     q, k_self, v_self, ref_k, ref_v = _prep(q, k_self, v_self, ref_k, ref_v, heads, include_self, adain)
     if out_dtype not in (None, q.dtype, torch.float32):
@@ -515,7 +551,7 @@ def shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, s
     out = torch.empty((q.shape[0], q.shape[1], heads * HEAD_DIM), dtype=out_dtype or q.dtype, device=q.device)
     lse = torch.empty((q.shape[0], heads, q.shape[1]), dtype=torch.float32, device=q.device) if return_lse else None
     args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, lse, split, q_prescaled, valid_refs,
-                      batch_invariant, key_bias)
+                      batch_invariant, key_bias, ref_lens)
     mass = None
     if return_mass:
         nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
@@ -540,13 +576,14 @@ def shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, s
 def time_shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, scale: float,
                           include_self: bool = True, adain=None, iters: int = 10, split: bool = True,
                           q_prescaled: bool = False, valid_refs: Optional[torch.Tensor] = None, return_mass: bool = False,
-                          batch_invariant: bool = False, key_bias: Optional[torch.Tensor] = None) -> float:
+                          batch_invariant: bool = False, key_bias: Optional[torch.Tensor] = None,
+                          ref_lens: Optional[torch.Tensor] = None) -> float:
     """Average ms per launch measured with HIP events on the launch stream (``bench.py``); ``valid_refs`` / ``return_mass`` /
     ``batch_invariant`` as in :func:`shared_attention` (the masses' finishing kernel is part of the timed launch)."""
     q, k_self, v_self, ref_k, ref_v = _prep(q, k_self, v_self, ref_k, ref_v, heads, include_self, adain)
     out = torch.empty((q.shape[0], q.shape[1], heads * HEAD_DIM), dtype=q.dtype, device=q.device)
     args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, None, split, q_prescaled, valid_refs,
-                      batch_invariant, key_bias)
+                      batch_invariant, key_bias, ref_lens)
     if return_mass:
         nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
         mass = torch.empty((q.shape[0], heads, q.shape[1], nseg), dtype=torch.float32, device=q.device)
@@ -578,14 +615,15 @@ def bench_mfma_stream(dtype: torch.dtype = torch.bfloat16, zero_operands: bool =
 def shared_attention_kernel_name(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, scale: float,
                                  include_self: bool = True, adain=None, q_prescaled: bool = False,
                                  valid_refs: Optional[torch.Tensor] = None, return_mass: bool = False,
-                                 batch_invariant: bool = False, key_bias: Optional[torch.Tensor] = None) -> str:
+                                 batch_invariant: bool = False, key_bias: Optional[torch.Tensor] = None,
+                                 ref_lens: Optional[torch.Tensor] = None) -> str:
     """which kernel the dispatcher launches for these tensors (reporting only; ``valid_refs`` / ``return_mass`` as in
     :func:`shared_attention` - they decide the 128-row kernel's form and whether the default rule takes it;
     ``batch_invariant``: the kernel and pieces of the batch-invariant plan)"""
     q, k_self, v_self, ref_k, ref_v = _prep(q, k_self, v_self, ref_k, ref_v, heads, include_self, adain)
     out = torch.empty((q.shape[0], q.shape[1], heads * HEAD_DIM), dtype=q.dtype, device=q.device)
     args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, None, True, q_prescaled, valid_refs,
-                      batch_invariant, key_bias)
+                      batch_invariant, key_bias, ref_lens)
     if return_mass:   # never written: the name is all this call computes
         nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
         mass = torch.empty((q.shape[0], heads, q.shape[1], nseg), dtype=torch.float32, device=q.device)
@@ -596,12 +634,14 @@ def shared_attention_kernel_name(q, k_self, v_self, ref_k=None, ref_v=None, *, h
 def shared_attention_plan(batch: int, len_q: int, heads: int, *, len_self: int = 0, n_refs: int = 0, len_ref: int = 0,
                           dtype: torch.dtype = torch.bfloat16, include_self: bool = True, adain: bool = False,
                           q_prescaled: bool = False, valid_refs: bool = False, return_mass: bool = False,
-                          out_dtype: Optional[torch.dtype] = None, workspace_bytes: Optional[int] = None, key_bias: bool = False) -> dict:
+                          out_dtype: Optional[torch.dtype] = None, workspace_bytes: Optional[int] = None, key_bias: bool = False,
+                          ref_lens: bool = False) -> dict:
     """the batch-invariant plan of a :func:`shared_attention` call of these sizes (``ir_shared_attn_plan``; host only - no tensor,
     no device): ``kernel`` (``IR_TUNE_*``), ``rows_per_item``, ``items_per_batch``, ``pieces_per_item``, ``workspace_bytes`` (the
     scratch of one launch over the batch, what :func:`shared_attention` allocates per call) and ``batch_per_launch`` - the entries
-    one launch covers with a workspace of ``workspace_bytes`` bytes (default: the plan's own size)"""
-    a = _lib.SharedAttnBiasArgs() if key_bias else _lib.SharedAttnArgs()   # key_bias: one more per-entry parameter (the 32-row kernel at every len_q)
+    one launch covers with a workspace of ``workspace_bytes`` bytes (default: the plan's own size).  ``ref_lens``: the call carries
+    per-reference counts (the pieces are planned for full references)"""
+    a = _lib.SharedAttnRaggedArgs() if ref_lens else _lib.SharedAttnBiasArgs() if key_bias else _lib.SharedAttnArgs()   # key_bias: one more per-entry parameter (the 32-row kernel at every len_q)
     a.struct_size = C.sizeof(a)
     a.dtype = _DT[dtype]
     a.flags = _lib.IR_FLAG_BATCH_INVARIANT | (_lib.IR_FLAG_INCLUDE_SELF if include_self else 0) | \
@@ -634,6 +674,8 @@ def shared_attention_plan(batch: int, len_q: int, heads: int, *, len_self: int =
         a.seg_mass = dummy
     if key_bias:
         a.key_bias = dummy
+    if ref_lens:
+        a.ref_lens, a.rl_sb = dummy, int(n_refs)
     L = _lib.lib()
     if workspace_bytes is None:
         workspace_bytes = int(L.ir_shared_attn_workspace_bytes_for(C.byref(a)))
@@ -842,6 +884,61 @@ def zero_invalid_refs(k: torch.Tensor, v: torch.Tensor, valid_indices: torch.Ten
                                          k.data_ptr(), k.stride(0), k.stride(1), k.stride(2), HEAD_DIM,
                                          v.data_ptr(), v.stride(0), v.stride(1), v.stride(2), HEAD_DIM, _stream())
     _lib.check(rc, "ir_zero_invalid_refs")
+
+
+def _pool_keep(keep: torch.Tensor, B: int, N: int, len_ref: int) -> torch.Tensor:
+    """bool ``(B, N, len_ref)`` from ``(B, N, len_ref)`` or ``(B, N, S, S)``: pooled by area to the layer's side, a token kept when
+    >= 0.5 of its area is - the rule of :func:`key_bias` for ``ref_token_keep``"""
+    if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool:
+        raise ValueError(f"keep must be a bool tensor, got {getattr(keep, 'dtype', type(keep))}")
+    if keep.dim() == 4:
+        side = int(round(int(len_ref) ** 0.5))
+        if keep.shape[:2] != (B, N) or side * side != int(len_ref) or keep.shape[2] != keep.shape[3]:
+            raise ValueError(f"keep (B, N, S, S) needs a square layer (len_ref = {len_ref}) and shape ({B}, {N}, S, S), got {tuple(keep.shape)}")
+        area = torch.nn.functional.adaptive_avg_pool2d(keep.to(torch.float32), side) if keep.shape[2] != side else keep.to(torch.float32)
+        keep = (area >= 0.5).reshape(B, N, side * side)
+    if tuple(keep.shape) != (B, N, int(len_ref)):
+        raise ValueError(f"keep must have shape (B, N, len_ref) = {(B, N, int(len_ref))} or (B, N, S, S), got {tuple(keep.shape)}")
+    return keep
+
+
+@_on_tensor_device
+def compact_refs(ref_k: torch.Tensor, ref_v: torch.Tensor, keep: torch.Tensor, *, heads: int, out=None):
+    """Pack the kept tokens of every reference to the front of its segment (``ir_compact_ref_tokens``): returns ``(k, v, ref_lens)``
+    - ``k`` / ``v`` of ``ref_k``'s shape whose rows ``0 .. ref_lens[b, n] - 1`` of reference ``(b, n)`` are the kept rows in their
+    order (rows behind the count are not written: ``torch.empty`` bytes, or what ``out`` held), and ``ref_lens`` int32 ``(B, N)`` -
+    the ``ref_lens`` of :func:`shared_attention`, which then walks the kept keys only.
+    ``keep``: bool ``(B, N, len_ref)``, or ``(B, N, S, S)`` pooled as :func:`key_bias` pools ``ref_token_keep``.
+    ``out=(k, v, ref_lens)``: refill those buffers (a captured step follows).  One launch, no host sync.  Runs once per identity;
+    AdaIN statistics belong to the FULL reference - take them before compacting."""
+    _need_gpu(ref_k, ref_v, keep)
+    _forward_only(ref_k, ref_v)
+    if _is_table(ref_k) or _is_table(ref_v):
+        raise TypeError("compact_refs takes dense (B, N, L, C) tensors")
+    ref_k, ref_v = _ref(ref_k, heads, "ref_k"), _ref(ref_v, heads, "ref_v")
+    if ref_k.shape != ref_v.shape or ref_k.dtype != ref_v.dtype:
+        raise ValueError("ref_k / ref_v shape or dtype mismatch")
+    B, N, L, _ = ref_k.shape
+    mask = _pool_keep(keep, B, N, L).to(torch.uint8).contiguous()
+    if out is None:
+        k, v = torch.empty_like(ref_k, memory_format=torch.contiguous_format), torch.empty_like(ref_v, memory_format=torch.contiguous_format)
+        lens = torch.empty((B, N), dtype=torch.int32, device=ref_k.device)
+    else:
+        k, v, lens = out
+        for t, src in ((k, ref_k), (v, ref_v)):
+            if t.shape != src.shape or t.dtype != src.dtype or t.device != src.device or t.stride(-1) != 1 or any(t.stride(i) % 8 for i in range(3)) or t.data_ptr() % 16:
+                raise ValueError("out k / v must match ref_k / ref_v in shape, dtype and device, with 16-byte aligned rows")
+        if lens.dtype != torch.int32 or tuple(lens.shape) != (B, N) or lens.device != ref_k.device or lens.stride(-1) != 1 or lens.stride(0) < N:
+            raise ValueError(f"out ref_lens must be int32 {(B, N)} on {ref_k.device}")
+    _lib.check(_lib.lib().ir_compact_ref_tokens(
+        _dtype_code(ref_k), B, heads, N, L,
+        ref_k.data_ptr(), ref_k.stride(0), ref_k.stride(1), ref_k.stride(2), HEAD_DIM,
+        ref_v.data_ptr(), ref_v.stride(0), ref_v.stride(1), ref_v.stride(2), HEAD_DIM,
+        mask.data_ptr(),
+        k.data_ptr(), k.stride(0), k.stride(1), k.stride(2), HEAD_DIM,
+        v.data_ptr(), v.stride(0), v.stride(1), v.stride(2), HEAD_DIM,
+        lens.data_ptr(), lens.stride(0), _stream()), "ir_compact_ref_tokens")
+    return k, v, lens
 
 
 @_on_tensor_device
