@@ -51,6 +51,9 @@ def main(argv=None):
     ap.add_argument("--small", action="store_true", help="narrow UNet topology (tests)")
     ap.add_argument("--landmark-maps", action="store_true",
                     help="one more frame that leaves the landmark attention map of every shared layer behind (attention_rows)")
+    ap.add_argument("--matches", action="store_true",
+                    help="one more frame that leaves the best-matching token of every reference behind for every query token "
+                         "(attention_match): prints, per shared layer, the mean best probability per reference and where the best matches lie")
     ap.add_argument("--ref-weights", default=None,
                     help="comma-separated weight per reference, e.g. 1,1,0.25,0 (0 masks a reference): prints the top shared layer's "
                          "per-reference attention masses with and without")
@@ -228,6 +231,30 @@ def main(argv=None):
                 print(f"shared layer {p.self_attn_idx}: landmark map {tuple(m.shape)} fp32, sum per identity {[round(float(t), 3) for t in m.sum(-1)]} "
                       f"(68 rows of probabilities), picture {pic.shape}")
                 assert float((m.sum(-1) - 68).abs().max()) < 68 * 8e-3
+        # Which token of each reference does every token of the degraded face draw from, and how strongly?  Each shared layer
+        # leaves (index, prob) of the head-mean attention behind - int32 / fp32 (B, L, [self?] + N): the best key of every segment
+        # and its probability - instead of the (B, H, L, Lkv) tensor; attn_maps.match_coordinates turns the indices into (y, x).
+        if args.matches:
+            from instantrestore_amd.attn_maps import match_coordinates
+            shared = sorted((p for p in unet.attn_processors.values() if getattr(p, "self_attn_idx", None) is not None),
+                            key=lambda p: p.self_attn_idx)
+            for p in shared:
+                p.attention_match_index = "all"
+            unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1),
+                 cross_attention_kwargs={"ref_keys": ck, "ref_values": cv, "ref_stats": cs})
+            fmt = lambda m: " ".join(f"{v:.4f}" for v in m.tolist())
+            for p in shared:
+                (index, prob), p.attention_match_index = p.attention_match, None
+                first = int(p.train_input)                                       # column of reference 0
+                rp, ri = prob[..., first:], index[..., first:]                   # (B, L, N)
+                tokens = ck[p.self_attn_idx].shape[2]
+                share = torch.bincount(rp.argmax(-1).flatten(), minlength=N).float() / rp[..., 0].numel()
+                side_len = int(round(tokens ** 0.5))
+                y, xq = match_coordinates(ri, side_len)
+                print(f"shared layer {p.self_attn_idx}: match {tuple(index.shape)}; mean best probability per reference {fmt(rp.mean(dim=(0, 1)))}; "
+                      f"share of tokens whose best match lies in each reference {fmt(share)}")
+                assert int(ri.min()) >= 0 and int(ri.max()) < tokens and int(y.max()) < side_len and 0 <= int(xq.min()) and int(xq.max()) < side_len
+                assert float(prob.min()) > 0 and float(prob.sum(-1).max()) <= 1.0 + 8e-3 and abs(float(share.sum()) - 1) < 1e-5
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     assert out_u8.shape == (B, S, S, 3) and out_u8.dtype == torch.uint8

@@ -376,6 +376,41 @@ int ir_attn_segment_mass(const ir_shared_attn_args* args, float* mass, void* str
 int ir_attn_rows(const ir_shared_attn_args* args, const int32_t* row_index, int32_t n_rows, int32_t reduce, void* out, void* stream);
 
 /*
+ * ir_attn_match (opt-in) - the best-matching key of every K/V segment for a caller-chosen set of query tokens, without the
+ * probability matrix.
+ *
+ * Replaces `attention_probs[..., segment].max(-1)` / `.argmax(-1)` per segment s of the column order above
+ * ([self (iff INCLUDE_SELF)] ++ ref 0 ++ ... ++ ref N-1, S = include_self + N): for this token of the degraded face, which token
+ * of each reference it draws from, and how strongly - a dense correspondence field with a confidence, at resolutions where the
+ * dump cannot be formed.  Same args as ir_attn_rows (q, the K pointers or the K table, lse; v_*, adain_*, out, valid_refs, seg_mass
+ * and workspace are ignored - every reference is walked - and `tuning` must be 0) plus
+ *   row_index  int32 (B, n_rows) contiguous on the device, as for ir_attn_rows: duplicates are rows like any other; an index
+ *              outside [0, len_q) gives index = -1, prob = 0 and is never used as an address.  Read by the kernel when it runs:
+ *              a replayed hipGraph follows in-place updates of it (and of the pointer tables).
+ *   n_rows     1 ... len_q
+ *   reduce     IR_MATCH_PER_HEAD   index int32 (B, H, n_rows, S), prob fp32 (B, H, n_rows, S):
+ *                                  prob = max over the keys j of segment s of the fp32
+ *                                  p = exp2(fma(<q[idx[b,r]], k_j>, scale*log2(e), -lse[b,h,idx[b,r]]*log2(e))) - the value ir_attn_probs and
+ *                                  ir_attn_rows round to `dtype`, so prob rounded to `dtype` IS the maximum of their row segment
+ *                                  (IR_FLAG_Q_PRESCALED: same rule as there)
+ *              IR_MATCH_HEAD_MEAN  index int32 (B, n_rows, S), prob fp32 (B, n_rows, S): the maximum of the head mean formed as
+ *                                  IR_ROWS_HEAD_MEAN forms it ((sum over heads, ascending, of the fp32 p) * (1/H)) - bit for bit
+ *                                  the maximum of ir_attn_rows' head-mean row segment
+ *   index      the LOWEST key j, counted from 0 inside its segment, that attains prob (ties go to the lowest key)
+ *   index, prob  contiguous, 4-byte aligned
+ * Bound: K read once per group of 96 rows (ceil(n_rows / 96) * B * H * Lkv * 128 bytes) and two numbers per (row, segment)
+ * written; no workspace, no atomics, one launch; asynchronous and capturable.  One wave walks a whole segment for up to 96
+ * rows, so every output element has one writer and one order; the cut follows len_self, len_ref, n_refs, n_rows and reduce only:
+ * the call is batch invariant with or without IR_FLAG_BATCH_INVARIANT.  Any segment length.
+ * Refused: a key_bias or ref_lens block (IR_ERR_UNSUPPORTED, as for the other read-outs), tuning != 0, NULL or misaligned
+ * row_index / index / prob, NULL lse, n_rows outside 1 ... len_q, another reduce, more than 2^31 - 4 work items.
+ */
+#define IR_MATCH_PER_HEAD 0
+#define IR_MATCH_HEAD_MEAN 1
+int ir_attn_match(const ir_shared_attn_args* args, const int32_t* row_index, int32_t n_rows, int32_t reduce, int32_t* index, float* prob,
+                  void* stream);
+
+/*
  * ir_adain_stats - per-(b, n, channel) AdaIN affine from token statistics.
  *
  * Replaces the statistics half of adain() (attn_processors.py:9-10) and of its call site

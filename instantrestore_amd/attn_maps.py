@@ -3,7 +3,8 @@ landmarks fall on, and the heat-map picture of a summed row.
 
 The reference does both inside ``get_visualization_image`` (face_replace/training/utils/vis_utils.py:97-108) on the head
 mean of the whole ``attention_probs``; here the index list goes IN (``attention_rows_index``) and only the chosen rows are
-ever computed."""
+ever computed.  ``match_coordinates`` / ``match_field`` turn the key indices of ``ops.attn_match`` /
+``SharedAttnProcessor.attention_match`` into grid coordinates and displacements."""
 import numpy as np
 
 
@@ -29,3 +30,51 @@ def landmark_picture(map_row, side: int) -> np.ndarray:
     if row.ndim != 1 or row.size % (side * side):
         raise ValueError(f"expected a ({side * side} * S,) row, got {row.shape}")
     return row.reshape(side, row.size // side)
+
+
+def _divmod_side(index, side: int):
+    """``index`` -> ``(index // side, index % side)`` with negative entries kept as they are (torch tensor on either device,
+    or anything NumPy takes)"""
+    if hasattr(index, "detach"):
+        import torch
+        idx = index.detach().long()
+        neg = idx < 0
+        return (torch.where(neg, idx, torch.div(idx, side, rounding_mode="floor")), torch.where(neg, idx, idx % side))
+    idx = np.asarray(index).astype(np.int64)
+    neg = idx < 0
+    return np.where(neg, idx, idx // side), np.where(neg, idx, idx % side)
+
+
+def match_coordinates(index, side: int):
+    """``index`` of ``ops.attn_match`` / ``SharedAttnProcessor.attention_match`` (any shape; the token inside its segment, row-major
+    on a ``side x side`` grid) -> ``(y, x)`` of the matched token, two int64 arrays of ``index``'s shape on its device.  ``-1`` (a row
+    index out of range) stays ``-1`` in both.  Index arithmetic only: nothing is read back from the device."""
+    return _divmod_side(index, side)
+
+
+def match_field(index, rows, side: int):
+    """the displacement ``(dy, dx)`` from every query token's own place to its match: ``index`` as for
+    :func:`match_coordinates`, shaped ``(..., R, S)``; ``rows`` the query tokens the call was given - ``(R,)``, ``(B, R)`` or
+    ``None`` / ``"all"`` for ``arange(R)``.  Where ``index`` or the row is negative (out of range) both displacements are 0."""
+    y, x = match_coordinates(index, side)
+    torch_in = hasattr(index, "detach")
+    R = index.shape[-2]
+    if rows is None or isinstance(rows, str):
+        if torch_in:
+            import torch
+            rows = torch.arange(R, device=index.device)
+        else:
+            rows = np.arange(R)
+    elif torch_in:
+        import torch
+        rows = torch.as_tensor(rows).to(index.device)
+    qy, qx = _divmod_side(rows, side)
+    if qy.ndim == 2 and index.ndim == 4:         # (B, R) against (B, H, R, S)
+        qy, qx = qy[:, None], qx[:, None]
+    qy, qx = qy[..., None], qx[..., None]         # over the segments
+    bad = (y < 0) | (qy < 0)
+    zero = 0 * y
+    if torch_in:
+        import torch
+        return torch.where(bad, zero, y - qy), torch.where(bad, zero, x - qx)
+    return np.where(bad, zero, y - qy), np.where(bad, zero, x - qx)

@@ -533,6 +533,15 @@ class SharedAttnProcessor(nn.Module):
         self.attention_rows_index = None
         self.attention_rows_reduce = "head_mean"
         self.attention_rows = None
+        # opt-in (plain attributes like ``attention_rows_index``): ``attention_match_index`` - ``"all"`` (every query token) or an integer
+        # tensor ``(R,)`` / ``(B, R)`` - makes every call of a shared layer leave ``attention_match = (index, prob)``: per K/V segment the
+        # largest probability of each chosen token and the key, counted inside its segment, that attains it (``ir_attn_match``) -
+        # ``attention_probs[..., segment].max(-1)`` / ``.argmax(-1)`` without the (B, H, L, Lkv) tensor.  ``attention_match_reduce``:
+        # "head_mean" - int32 / fp32 (B, R, S), of the head mean; "none" - (B, H, R, S), per head.  ``attn_maps.match_coordinates`` /
+        # ``match_field`` turn the indices into grid positions.  Uses the LSE of the same attention call.  ``None``: off, nothing changes.
+        self.attention_match_index = None
+        self.attention_match_reduce = "head_mean"
+        self.attention_match = None
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                 ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None, ref_weights=None, ref_token_keep=None,
@@ -597,6 +606,9 @@ class SharedAttnProcessor(nn.Module):
                 if self.save_self_attentions or getattr(self, "attention_rows_index", None) is not None:
                     raise NotImplementedError("ref_lens together with save_self_attentions / attention_rows_index: ir_attn_probs and ir_attn_rows "
                                               "would walk the tails behind the counts (follow-up); save_attention_mass honours the counts")
+                if getattr(self, "attention_match_index", None) is not None:
+                    raise NotImplementedError("ref_lens together with attention_match_index: ir_attn_match would walk the tails behind the "
+                                              "counts (follow-up)")
                 if self.use_adain and cstats is None:
                     raise ValueError("ref_lens with use_adain needs ref_stats: the AdaIN content statistics are those of the full reference, "
                                      "taken before compaction - computing them here would read the packed rows and whatever lies behind them")
@@ -641,7 +653,8 @@ class SharedAttnProcessor(nn.Module):
         want_probs = bool(self.save_self_attentions)
         want_mass = bool(getattr(self, "save_attention_mass", False))
         rows_index = getattr(self, "attention_rows_index", None) if shared else None
-        want_lse = want_probs or rows_index is not None
+        match_index = getattr(self, "attention_match_index", None) if shared else None
+        want_lse = want_probs or rows_index is not None or match_index is not None
         kw = {"q_prescaled": True} if presc else {}
         kw.update(_bi_kw(bi))
         if shared and ref_valid is not None:
@@ -660,6 +673,9 @@ class SharedAttnProcessor(nn.Module):
                 raise NotImplementedError("save_self_attentions / attention_rows_index together with an attention mask, ref_weights or "
                                           "ref_token_keep: ir_attn_probs and ir_attn_rows do not take the key bias yet (follow-up); "
                                           "save_attention_mass honours it")
+            if match_index is not None:
+                raise NotImplementedError("attention_match_index together with an attention mask, ref_weights or ref_token_keep: "
+                                          "ir_attn_match does not take the key bias yet (follow-up)")
             kw["key_bias"] = bias
         # the masses are a by-product of the attention launch itself (ABI v9 ``seg_mass``: the kernels hold the row sums at every
         # segment boundary): no second pass over Q and K
@@ -677,6 +693,14 @@ class SharedAttnProcessor(nn.Module):
             self.attention_rows = _ops.attn_rows(query, key, ref_k, lse, rows_index, heads=attn.heads,
                                                  scale=0.6931471805599453 if presc else attn.scale, include_self=include_self,
                                                  reduce=getattr(self, "attention_rows_reduce", "head_mean"), **_bi_kw(bi))
+        if match_index is not None:
+            # the best key of every segment for the chosen tokens ("all": every token) from the same LSE
+            if isinstance(match_index, str) and match_index != "all":
+                raise ValueError(f"attention_match_index must be None, \"all\" or an integer tensor, got {match_index!r}")
+            self.attention_match = _ops.attn_match(query, key, ref_k, lse, None if isinstance(match_index, str) else match_index,
+                                                   heads=attn.heads, scale=0.6931471805599453 if presc else attn.scale,
+                                                   include_self=include_self,
+                                                   reduce=getattr(self, "attention_match_reduce", "head_mean"), **_bi_kw(bi))
         if want_probs:
             # (B, H, L, Lkv), columns [self?] ++ ref0 ++ ... ++ refN-1, in the compute dtype.  A pre-scaled query
             # already carries scale * log2(e): its scores are exponents, ln 2 turns them into the logits of the LSE

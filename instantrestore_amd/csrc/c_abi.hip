@@ -445,6 +445,31 @@ int ir_attn_rows(const ir_shared_attn_args* args, const int32_t* row_index, int3
   return IR_OK;
 }
 
+int ir_attn_match(const ir_shared_attn_args* args, const int32_t* row_index, int32_t n_rows, int32_t reduce, int32_t* index, float* prob,
+                  void* stream) {
+  if (args == nullptr) return fail(IR_ERR_INVALID_ARG, "args is NULL");
+  if (attn_block_size_ok(args->struct_size) && args->tuning != IR_TUNE_DEFAULT)
+    return fail(IR_ERR_UNSUPPORTED, "ir_attn_match has one kernel: tuning must be 0 (got %d)", args->tuning);
+  AttnKParams p;
+  const int rc = build_attn_params(args, &p, false, false);
+  if (rc != IR_OK) return rc;
+  if (row_index == nullptr) return fail(IR_ERR_INVALID_ARG, "row_index is NULL");
+  if (index == nullptr) return fail(IR_ERR_INVALID_ARG, "index is NULL");
+  if (prob == nullptr) return fail(IR_ERR_INVALID_ARG, "prob is NULL");
+  if (args->lse == nullptr) return fail(IR_ERR_INVALID_ARG, "lse is NULL");
+  if (n_rows < 1 || n_rows > args->len_q) return fail(IR_ERR_INVALID_ARG, "n_rows %d outside [1, len_q = %d]", n_rows, args->len_q);
+  if (reduce != IR_MATCH_PER_HEAD && reduce != IR_MATCH_HEAD_MEAN)
+    return fail(IR_ERR_UNSUPPORTED, "reduce %d: IR_MATCH_PER_HEAD (0) or IR_MATCH_HEAD_MEAN (1)", reduce);
+  if ((reinterpret_cast<uintptr_t>(row_index) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "row_index must be 4-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(index) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "index must be 4-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(prob) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "prob must be 4-byte aligned");
+  if (ir_attn_match_items(p, n_rows, reduce) > kMatchMaxItems) return fail(IR_ERR_UNSUPPORTED, "grid too large");
+  if (p.q_prescaled) p.scale_log2 = 1.0f;   // as in ir_attn_probs: the products of a pre-scaled q and k ARE the exponents
+  const hipError_t e = ir_launch_attn_match(p, args->dtype, row_index, n_rows, reduce, index, prob, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "attn_match launch: %s", hipGetErrorString(e));
+  return IR_OK;
+}
+
 static int adain_nchunk(int32_t len_self, int32_t len_ref) {
   const int a = (len_self + IR_ADAIN_ROWS - 1) / IR_ADAIN_ROWS;
   const int b = (len_ref + IR_ADAIN_ROWS - 1) / IR_ADAIN_ROWS;

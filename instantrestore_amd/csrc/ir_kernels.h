@@ -211,6 +211,14 @@ hipError_t ir_launch_attn_segment_mass(const AttnKParams& p, int dtype, float* m
 // as they are or reduced over heads / over heads and rows; `reduce` is IR_ROWS_* of the public header
 constexpr int kRowsNone = 0, kRowsHeadMean = 1, kRowsMap = 2;
 hipError_t ir_launch_attn_rows(const AttnKParams& p, int dtype, const int32_t* row_index, int n_rows, int reduce, void* out, hipStream_t s);
+// attn_match.hip: per K/V segment, the largest probability of each of `n_rows` chosen query tokens and the key that attains it
+// (index int32, prob fp32: (B, H, n_rows, S) per head, (B, n_rows, S) of the head mean); `reduce` is IR_MATCH_* of the public header.
+// One wave per item, four items per workgroup: ir_attn_match_items is the item count, at most kMatchMaxItems
+constexpr int kMatchPerHead = 0, kMatchHeadMean = 1;
+constexpr int64_t kMatchMaxItems = 0x7fffffffLL - 3;
+int64_t ir_attn_match_items(const AttnKParams& p, int n_rows, int reduce);
+hipError_t ir_launch_attn_match(const AttnKParams& p, int dtype, const int32_t* row_index, int n_rows, int reduce, int32_t* index, float* prob,
+                                hipStream_t s);
 hipError_t ir_launch_adain_stats(const AdainKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_token_stats(const AdainKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_adain_stats_cached(const AdainKParams& p, int dtype, hipStream_t s);

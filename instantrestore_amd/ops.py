@@ -777,6 +777,42 @@ def attn_rows(q, k_self, ref_k, lse, rows, *, heads: int, scale: float, include_
     return out
 
 
+MATCH_REDUCE = {"none": _lib.IR_MATCH_PER_HEAD, "head_mean": _lib.IR_MATCH_HEAD_MEAN}
+
+
+@_on_tensor_device
+def attn_match(q, k_self, ref_k, lse, rows=None, *, heads: int, scale: float, include_self: bool = True, reduce: str = "none",
+               q_prescaled: bool = False, batch_invariant: bool = False):
+    """The best-matching key of every K/V segment for the query tokens ``rows`` from the LSE of the fused forward, without the
+    ``(B, H, Lq, Lkv)`` tensor (``ir_attn_match``): ``attention_probs[..., segment].max(-1)`` / ``.argmax(-1)`` per segment of
+    ``[self (iff include_self)] ++ ref 0 ++ ... ++ ref N-1``.
+
+    ``rows``: ``None`` - every query token, in order - or an integer tensor ``(R,)`` / ``(B, R)`` as for :func:`attn_rows`
+    (duplicates are rows like any other; a device index outside ``[0, Lq)`` gives ``index = -1``, ``prob = 0``).  Returns
+    ``(index, prob)``: int32 and fp32, ``(B, H, R, S)`` with ``reduce="none"`` (per head), ``(B, R, S)`` with ``"head_mean"`` (of
+    the head mean as :func:`attn_rows` forms it).  ``prob`` is the largest fp32 probability of the segment - rounded to q's dtype
+    it is the maximum of :func:`attn_probs` there; the head-mean ``prob`` is the maximum of :func:`attn_rows`' head-mean row bit
+    for bit - and ``index`` the lowest key, counted inside its segment, that attains it
+    (:func:`instantrestore_amd.attn_maps.match_coordinates` turns it into ``(y, x)``).  ``q_prescaled`` as in :func:`attn_probs`.
+    Batch invariant by construction; ``batch_invariant`` is accepted and changes nothing."""
+    if reduce not in MATCH_REDUCE:
+        raise ValueError(f"reduce must be one of {sorted(MATCH_REDUCE)}, got {reduce!r}")
+    args, q, B, Lq, _, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant)
+    args.tuning = 0   # one kernel: the A/B hook of the forward does not apply
+    if rows is None:
+        idx = torch.arange(Lq, dtype=torch.int32, device=q.device).unsqueeze(0).expand(B, -1).contiguous()
+    else:
+        idx = _row_index(rows, B, Lq, q.device)
+    R = idx.shape[1]
+    nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
+    shape = (B, heads, R, nseg) if reduce == "none" else (B, R, nseg)
+    index = torch.empty(shape, dtype=torch.int32, device=q.device)
+    prob = torch.empty(shape, dtype=torch.float32, device=q.device)
+    _lib.check(_lib.lib().ir_attn_match(C.byref(args), idx.data_ptr(), R, MATCH_REDUCE[reduce], index.data_ptr(), prob.data_ptr(), _stream()),
+               "ir_attn_match")
+    return index, prob
+
+
 @_on_tensor_device
 def adain_stats(v_self: torch.Tensor, ref_v: torch.Tensor, *, heads: int, eps: float = ADAIN_EPS):
     """AdaIN as a per-(b, n, head, channel) affine ``x*a + b`` (``ir_adain_stats``).

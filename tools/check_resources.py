@@ -9,8 +9,8 @@ import re
 import subprocess
 import sys
 
-NO_SCRATCH = ("linear_tiled", "shared_attn_fwd_w128", "attn_rows_kernel")     # mangled-name substrings: scratch / spills are a build error for these kernels
-# (attn_rows_kernel holds up to 96 fp32 sums per lane across its head walk: a spill would put them in scratch memory)
+NO_SCRATCH = ("linear_tiled", "shared_attn_fwd_w128", "attn_rows_kernel", "attn_match_kernel")     # mangled-name substrings: scratch / spills are a build error for these kernels
+# (attn_rows_kernel / attn_match_kernel hold up to 96 / 192 fp32 sums per lane across their head walk: a spill would put them in scratch memory)
 
 
 def demangle(name):
