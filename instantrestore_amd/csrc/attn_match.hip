@@ -8,8 +8,7 @@
 //
 //   p[b,h,r,j] = exp2(fma(<q[b, idx[b,r], h, :], k_seg[b, j, h, :]>, scale*log2(e), -lse[b,h,idx[b,r]]*log2(e)))
 //
-// the expression of attn_probs.hip / attn_rows.hip on the same fp32 MFMA result (v_mfma_f32_32x32x16, the four 16-wide steps
-// over d in ascending order).
+// the expression and the contraction of ir_readout.h, which attn_probs.hip and attn_rows.hip share.
 //
 //   IR_MATCH_PER_HEAD   index int32 / prob fp32 (B, H, R, S)   prob = max_j p,  index = the lowest j (inside the segment) attaining it
 //   IR_MATCH_HEAD_MEAN  index int32 / prob fp32 (B, R, S)      the same of the head mean, formed as IR_ROWS_HEAD_MEAN forms it:
@@ -17,8 +16,7 @@
 //
 // so prob rounded to the 16-bit format is the maximum of the dump's row segment, and the head-mean prob is the maximum of
 // ir_attn_rows' head-mean row segment bit for bit.  Shape of the work:
-//   * the lane layout of attn_rows.hip: the contraction is issued SWAPPED (keys on the MFMA rows through keymap, the gathered
-//     rows on its columns), so a lane holds 16 CONSECUTIVE keys of ONE row per 32 x 32 block;
+//   * the lane layout of ir_readout.h: a lane holds 16 CONSECUTIVE keys of ONE gathered row per 32 x 32 block;
 //   * a wave owns one segment and up to 96 rows (NQ <= 3 blocks of 32; more rows are further row groups) and walks the WHOLE
 //     segment: every output element has one writer and one order, nothing is combined across waves or through memory.  The
 //     per-head form keeps the Q fragments of its head in registers for the walk; the head-mean form walks the heads in
@@ -33,10 +31,10 @@
 //   * an index outside [0, len_q) reads row 0 of q and lse (always a valid address) and gives index -1, prob 0; rows of the
 //     padding to 32 are not written.  Duplicated indices are rows like any other.  Keys past the end of a segment are clamped
 //     to its last key as addresses and never compared.
-#include "ir_common.h"
-#include "ir_kernels.h"
+#include "ir_readout.h"
 
 namespace {
+using namespace ir_readout;
 
 constexpr int RW = 4;   // waves per workgroup (independent of each other: one item each)
 constexpr int KB = 2;   // 32-key blocks per step of the per-head walk (the next step's are in flight meanwhile)
@@ -58,10 +56,6 @@ struct MatchPlan {
   float inv_h;  // 1 / H
 };
 
-// MFMA row i of a swapped 32 x 32 block carries key keymap(i) of the block (attn_probs.hip): lane (lq, hi) then holds
-// keys 16*hi + r, r = 0..15, of row lq
-static __device__ __forceinline__ int keymap(int i) { return (i & 3) + 4 * (i >> 3) + 16 * ((i >> 2) & 1); }
-
 // the 16 values of one row and block against the row's running pair; `key0`: the key of e[0] inside the segment
 static __device__ __forceinline__ void take_best(const float (&e)[16], int key0, float& bv, int& bk) {
   float m = e[0];
@@ -78,8 +72,7 @@ static __device__ __forceinline__ void take_best(const float (&e)[16], int key0,
 
 template <typename T, int NQ, int RED>
 __global__ void __launch_bounds__(RW * 64) attn_match_kernel(const AttnKParams p, const MatchPlan pl) {
-  using Tr = ElemTraits<T>;
-  using v8 = typename Tr::v8;
+  using v8 = typename ElemTraits<T>::v8;
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int hi = lane >> 5, lq = lane & 31;
@@ -96,56 +89,13 @@ __global__ void __launch_bounds__(RW * 64) attn_match_kernel(const AttnKParams p
   if constexpr (RED == kMatchPerHead) { h0 = id % p.H; id /= p.H; }
   const int b = id;
 
-  const T* kb;   // head 0 of the segment's keys
-  int64_t ksl, ksh;
-  int len;
-  if (p.include_self && seg == 0) {
-    kb = (const T*)p.k_self + (int64_t)b * p.ks_sb; ksl = p.ks_sl; ksh = p.ks_sh; len = p.Ls;
-  } else {
-    const int n = seg - p.include_self;
-    kb = ir_ref_entry((const T*)p.k_ref + (int64_t)b * p.kr_sb + (int64_t)n * p.kr_sn, p.ref_tables); ksl = p.kr_sl; ksh = p.kr_sh; len = p.Lr;
-  }
-
-  const float LOG2E = 1.4426950408889634f;
+  const KeySeg<T> ks = key_segment<T>(p, b, seg);   // keys past its end are clamped as addresses and never compared
+  const int len = ks.len;
   const int km = keymap(lq);
-  const int32_t* idx = pl.idx + (int64_t)b * pl.R;
 
-  // rows held by this lane: r = (g0 * NQ + qi) * 32 + lq; their token index (row 0 for padding and indices out of range)
   int qrow[NQ];
   bool ok[NQ];
-#pragma unroll
-  for (int qi = 0; qi < NQ; ++qi) {
-    const int r = (g0 * NQ + qi) * 32 + lq;
-    const int ix = r < pl.R ? idx[r] : -1;
-    ok[qi] = (unsigned)ix < (unsigned)p.Lq;
-    qrow[qi] = ok[qi] ? ix : 0;
-  }
-  // B operand: Q[row][d = 16ks + 8hi ..] of head h; the LSE of that row in the exp2 domain
-  auto load_q = [&](int h, v8 (&qf)[NQ][4], float (&lse2)[NQ]) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi) {
-      const T* qp = (const T*)p.q + (int64_t)b * p.q_sb + (int64_t)qrow[qi] * p.q_sl + (int64_t)h * p.q_sh + hi * 8;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) qf[qi][ks] = *(const v8*)(qp + ks * 16);
-      lse2[qi] = p.lse[((int64_t)b * p.H + h) * p.Lq + qrow[qi]] * LOG2E;
-    }
-  };
-  // A operand: K[key j + keymap(lq)][d = 16ks + 8hi ..] of head h, keys past the segment clamped (their values are never compared)
-  auto load_k = [&](int h, int j, v8 (&kf)[4]) {
-    const int key = j + km;
-    const T* kp = kb + (int64_t)h * ksh + (int64_t)(key < len ? key : len - 1) * ksl + hi * 8;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) kf[ks] = *(const v8*)(kp + ks * 16);
-  };
-  // sc[r] = <K[j + 16 hi + r], Q[row of qi]>
-  auto scores = [&](const v8 (&kf)[4], const v8 (&qf)[4]) {
-    f32x16 sc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) sc[r] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) sc = Tr::mfma(kf[ks], qf[ks], sc);
-    return sc;
-  };
+  gather_rows<NQ>(pl.idx + (int64_t)b * pl.R, pl.R, p.Lq, g0, lq, qrow, ok);
 
   // the running pair of each row: every probability is >= 0, so the first compared key replaces the start value
   float bv[NQ];
@@ -156,24 +106,24 @@ __global__ void __launch_bounds__(RW * 64) attn_match_kernel(const AttnKParams p
   if constexpr (RED == kMatchPerHead) {
     v8 qf[NQ][4];
     float lse2[NQ];
-    load_q(h0, qf, lse2);
+    load_q<T, NQ>(p, b, h0, hi, qrow, qf, lse2);
     v8 kf[KB][4];
 #pragma unroll
-    for (int kblk = 0; kblk < KB; ++kblk) load_k(h0, 32 * kblk, kf[kblk]);
+    for (int kblk = 0; kblk < KB; ++kblk) load_k(ks, h0, 32 * kblk + km, hi, kf[kblk]);
     for (int j = 0; j < len; j += 32 * KB) {
 #pragma unroll
       for (int kblk = 0; kblk < KB; ++kblk) {
         f32x16 sc[NQ];
 #pragma unroll
-        for (int qi = 0; qi < NQ; ++qi) sc[qi] = scores(kf[kblk], qf[qi]);
-        load_k(h0, j + 32 * (KB + kblk), kf[kblk]);   // the next step's fragments arrive while this step's exponentials run (clamped: a valid address)
+        for (int qi = 0; qi < NQ; ++qi) sc[qi] = scores<T>(kf[kblk], qf[qi]);
+        load_k(ks, h0, j + 32 * (KB + kblk) + km, hi, kf[kblk]);   // the next step's fragments arrive while this step's exponentials run (clamped: a valid address)
         const int key0 = j + 32 * kblk + 16 * hi;
         const bool whole = j + 32 * kblk + 32 <= len;   // wave-uniform: every key of the block exists
 #pragma unroll
         for (int qi = 0; qi < NQ; ++qi) {
           float e[16];
 #pragma unroll
-          for (int t = 0; t < 16; ++t) e[t] = fast_exp2(__builtin_fmaf(sc[qi][t], p.scale_log2, -lse2[qi]));
+          for (int t = 0; t < 16; ++t) e[t] = prob(sc[qi][t], p.scale_log2, lse2[qi]);
           if (!whole) {
 #pragma unroll
             for (int t = 0; t < 16; ++t) e[t] = key0 + t < len ? e[t] : -1.f;
@@ -197,15 +147,15 @@ __global__ void __launch_bounds__(RW * 64) attn_match_kernel(const AttnKParams p
         float lse2[NQ];
         v8 kf[KBM][4];
 #pragma unroll
-        for (int kblk = 0; kblk < KBM; ++kblk) load_k(h, j + 32 * kblk, kf[kblk]);
-        load_q(h, qf, lse2);
+        for (int kblk = 0; kblk < KBM; ++kblk) load_k(ks, h, j + 32 * kblk + km, hi, kf[kblk]);
+        load_q<T, NQ>(p, b, h, hi, qrow, qf, lse2);
 #pragma unroll
         for (int kblk = 0; kblk < KBM; ++kblk) {
 #pragma unroll
           for (int qi = 0; qi < NQ; ++qi) {
-            const f32x16 sc = scores(kf[kblk], qf[qi]);
+            const f32x16 sc = scores<T>(kf[kblk], qf[qi]);
 #pragma unroll
-            for (int t = 0; t < 16; ++t) acc[kblk][qi][t] += fast_exp2(__builtin_fmaf(sc[t], p.scale_log2, -lse2[qi]));
+            for (int t = 0; t < 16; ++t) acc[kblk][qi][t] += prob(sc[t], p.scale_log2, lse2[qi]);
           }
         }
       }
@@ -244,37 +194,10 @@ __global__ void __launch_bounds__(RW * 64) attn_match_kernel(const AttnKParams p
   }
 }
 
-template <typename T, int NQ>
-hipError_t launch_nq(const AttnKParams& p, const MatchPlan& pl, int reduce, hipStream_t s) {
-  const dim3 grid((pl.items + RW - 1) / RW), block(RW * 64);
-  switch (reduce) {
-    case kMatchPerHead: hipLaunchKernelGGL((attn_match_kernel<T, NQ, kMatchPerHead>), grid, block, 0, s, p, pl); break;
-    case kMatchHeadMean: hipLaunchKernelGGL((attn_match_kernel<T, NQ, kMatchHeadMean>), grid, block, 0, s, p, pl); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_t(const AttnKParams& p, const MatchPlan& pl, int nq, int reduce, hipStream_t s) {
-  switch (nq) {
-    case 1: return launch_nq<T, 1>(p, pl, reduce, s);
-    case 2: return launch_nq<T, 2>(p, pl, reduce, s);
-    default: return launch_nq<T, 3>(p, pl, reduce, s);
-  }
-}
-
-// 32-row blocks a wave holds: the padded row count up to 96, three beyond (the rule of attn_rows.hip)
-int rows_nq(int n_rows) {
-  const int nblk = (n_rows + 31) / 32;
-  return nblk < 3 ? nblk : 3;
-}
-
 }  // namespace
 
 int64_t ir_attn_match_items(const AttnKParams& p, int n_rows, int reduce) {
-  const int nblk = (n_rows + 31) / 32, nq = rows_nq(n_rows);
-  return (int64_t)((nblk + nq - 1) / nq) * (p.include_self + p.N) * (reduce == kMatchPerHead ? p.H : 1) * p.B;
+  return (int64_t)rows_ngroups(n_rows) * (p.include_self + p.N) * (reduce == kMatchPerHead ? p.H : 1) * p.B;
 }
 
 hipError_t ir_launch_attn_match(const AttnKParams& p, int dtype, const int32_t* row_index, int n_rows, int reduce, int32_t* index, float* prob,
@@ -286,10 +209,19 @@ hipError_t ir_launch_attn_match(const AttnKParams& p, int dtype, const int32_t* 
   pl.index = index;
   pl.prob = prob;
   pl.R = n_rows;
-  const int nq = rows_nq(n_rows);
-  pl.ngroups = ((n_rows + 31) / 32 + nq - 1) / nq;
+  pl.ngroups = rows_ngroups(n_rows);
   pl.nseg = p.include_self + p.N;
   pl.items = (int)items;
   pl.inv_h = 1.0f / (float)p.H;
-  return dtype == 1 ? launch_t<__bf16>(p, pl, nq, reduce, s) : launch_t<_Float16>(p, pl, nq, reduce, s);
+  return dispatch_rows(dtype, n_rows, [&](auto t, auto nq) {
+    using T = typename decltype(t)::type;
+    constexpr int NQ = decltype(nq)::value;
+    const dim3 grid((pl.items + RW - 1) / RW), block(RW * 64);
+    switch (reduce) {
+      case kMatchPerHead: hipLaunchKernelGGL((attn_match_kernel<T, NQ, kMatchPerHead>), grid, block, 0, s, p, pl); break;
+      case kMatchHeadMean: hipLaunchKernelGGL((attn_match_kernel<T, NQ, kMatchHeadMean>), grid, block, 0, s, p, pl); break;
+      default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+  });
 }

@@ -8,10 +8,9 @@
 // attn_probs_lines_kernel (round 5; every shape whose segment lengths are multiples of 8 keys) - bound: HBM WRITES,
 // H*L*Lkv*2 bytes per identity (0.84 GB at the 64x64-token layer, N = 4, t = 1).  The only thing that matters
 // is the shape of the stores:
-//   * the contraction is issued SWAPPED (S^T = K Q^T: keys on the MFMA rows, queries on its columns), and the key a lane
-//     supplies for MFMA row i is keymap(i): after it a lane holds 16 CONSECUTIVE keys of ONE query row per 32 x 32
-//     block (the un-swapped form of round 1 left a lane one key of 16 different rows: 2-byte stores, 64 B per row and
-//     instruction - 12.5x the time per byte of 16-byte stores, MI355X_MICROARCH.md "stores of each flavour");
+//   * the lane layout of ir_readout.h: a lane holds 16 CONSECUTIVE keys of ONE query row per 32 x 32 block (the un-swapped
+//     form of round 1 left a lane one key of 16 different rows: 2-byte stores, 64 B per row and instruction - 12.5x the
+//     time per byte of 16-byte stores, MI355X_MICROARCH.md "stores of each flavour");
 //   * the exponentiated block is rounded, packed and written to a wave-private LDS tile (rows x 128 B, 16-byte chunks
 //     XOR-swizzled by the row: both directions conflict-free) and read back row-major, so that one store instruction
 //     writes 8 whole 128-B lines (8 lanes x 16 B per row);
@@ -26,10 +25,10 @@
 // attn_segment_mass (round 5, opt-in): mass[b,h,i,s] = sum of the probabilities of row i over segment s
 // ([self?] ++ ref 0 ++ ...), fp32 - what gradio_demo.py:119-127 reduces the 6.7 GB tensor to.  Same recompute, no big
 // tensor: bound by the exponentials (B*H*L*Lkv of them), not by memory.
-#include "ir_common.h"
-#include "ir_kernels.h"
+#include "ir_readout.h"
 
 namespace {
+using namespace ir_readout;
 
 constexpr int PW = 4;  // waves per workgroup
 
@@ -42,23 +41,9 @@ struct ProbsPlan {
   int items;      // B * H * nch_total * nqb
 };
 
-// MFMA row i of a swapped 32 x 32 block carries key keymap(i) of the block: lane (lq, hi) then holds C rows
-// (r&3) + 8(r>>2) + 4hi, r = 0..15  ==  keys 16*hi + r.
-static __device__ __forceinline__ int keymap(int i) { return (i & 3) + 4 * (i >> 3) + 16 * ((i >> 2) & 1); }
-
-template <typename T>
-static __device__ __forceinline__ unsigned pack2(float a, float b) {
-  typedef T T2 __attribute__((ext_vector_type(2)));
-  T2 v;
-  v[0] = (T)a;
-  v[1] = (T)b;
-  return __builtin_bit_cast(unsigned, v);
-}
-
 template <typename T, int NQ, int NK, bool MASS>
 __global__ void __launch_bounds__(PW * 64) attn_probs_lines_kernel(const AttnKParams p, const ProbsPlan pl, float* __restrict__ mass) {
-  using Tr = ElemTraits<T>;
-  using v8 = typename Tr::v8;
+  using v8 = typename ElemTraits<T>::v8;
   constexpr int ROWS = 32 * NQ;                   // query rows per wave
   constexpr int STEP = 32 * NK;                   // keys per step
   constexpr int PITCH = 2 * STEP;                 // bytes of one row of the wave's LDS tile (NK * 64)
@@ -81,24 +66,14 @@ __global__ void __launch_bounds__(PW * 64) attn_probs_lines_kernel(const AttnKPa
   const int q0 = (qb * PW + wid) * ROWS;
   if (q0 >= p.Lq) return;
 
-  const T* kb;
-  int64_t ksl;
-  int len, col0, chunk, seg;
-  if (c < pl.nch_self) {
-    kb = (const T*)p.k_self + (int64_t)b * p.ks_sb + (int64_t)h * p.ks_sh; ksl = p.ks_sl; len = p.Ls; col0 = 0; chunk = c; seg = 0;
-  } else {
-    const int cr = c - pl.nch_self;
-    const int n = cr / pl.nch_ref;
-    chunk = cr - n * pl.nch_ref;
-    kb = ir_ref_entry((const T*)p.k_ref + (int64_t)b * p.kr_sb + (int64_t)n * p.kr_sn, p.ref_tables) + (int64_t)h * p.kr_sh; ksl = p.kr_sl; len = p.Lr;
-    col0 = p.include_self * p.Ls + n * p.Lr;
-    seg = p.include_self + n;
-  }
-  const int j_begin = chunk * pl.kc;
+  const KeyChunk<T> kc = key_chunk<T>(p, b, c, pl.nch_self, pl.nch_ref, h);   // one head per item
+  const KeySeg<T> ks = kc.ks;
+  const int len = ks.len, col0 = kc.col0, seg = kc.seg;
+  const int j_begin = kc.chunk * pl.kc;
   const int j_end = (j_begin + pl.kc < len) ? j_begin + pl.kc : len;
 
-  // B operand: Q[row 32*qi + lq][d = 16ks + 8hi ..]; the LSE of that row in the exp2 domain
-  const float LOG2E = 1.4426950408889634f;
+  // B operand: Q[row 32*qi + lq][d = 16ks + 8hi ..]; the LSE of that row in the exp2 domain.  ir_readout.h's load_q, kept here:
+  // it takes the parameter block by reference (see key_segment there)
   v8 qf[NQ][4];
   float lse2[NQ];
 #pragma unroll
@@ -107,18 +82,20 @@ __global__ void __launch_bounds__(PW * 64) attn_probs_lines_kernel(const AttnKPa
     const int qr = q < p.Lq ? q : p.Lq - 1;
     const T* qp = (const T*)p.q + (int64_t)b * p.q_sb + (int64_t)qr * p.q_sl + (int64_t)h * p.q_sh + hi * 8;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[qi][ks] = *(const v8*)(qp + ks * 16);
+    for (int d = 0; d < 4; ++d) qf[qi][d] = *(const v8*)(qp + d * 16);
     lse2[qi] = p.lse[((int64_t)b * p.H + h) * p.Lq + qr] * LOG2E;
   }
 
-  // A operand: K[key j + 32*kblk + keymap(lq)][d = 16ks + 8hi ..], keys past the segment clamped (their columns are not stored)
+  // A operand: K[key j + 32*kblk + keymap(lq)][d = 16ks + 8hi ..], keys past the segment clamped (their columns are not stored).
+  // ir_readout.h's load_k, kept here as the lambda it was: through the helper the 64-row kernel's main loop is scheduled
+  // differently (the next step's K loads move ahead of the exponentials) and the dump measured 1.8 % slower at L 4096
   const int km = keymap(lq);
   v8 kf[NK][4];
   auto load_k = [&](int j, int kblk) {   // one 32-key block of fragments
     const int key = j + 32 * kblk + km;
-    const T* kp = kb + (int64_t)(key < len ? key : len - 1) * ksl + hi * 8;
+    const T* kp = ks.kb + (int64_t)(key < len ? key : len - 1) * ks.ksl + hi * 8;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) kf[kblk][ks] = *(const v8*)(kp + ks * 16);
+    for (int d = 0; d < 4; ++d) kf[kblk][d] = *(const v8*)(kp + d * 16);
   };
 #pragma unroll
   for (int kblk = 0; kblk < NK; ++kblk) load_k(j_begin, kblk);
@@ -144,12 +121,7 @@ __global__ void __launch_bounds__(PW * 64) attn_probs_lines_kernel(const AttnKPa
     for (int kblk = 0; kblk < NK; ++kblk) {
       f32x16 sc[NQ];
 #pragma unroll
-      for (int qi = 0; qi < NQ; ++qi) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sc[qi][r] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) sc[qi] = Tr::mfma(kf[kblk][ks], qf[qi][ks], sc[qi]);
-      }
+      for (int qi = 0; qi < NQ; ++qi) sc[qi] = scores<T>(kf[kblk], qf[qi]);
       // the block's fragments are dead: the next step's arrive in the same registers while this step's exponentials run
       // (clamped past the end of the segment: always a valid address)
       load_k(j + STEP, kblk);
@@ -160,11 +132,11 @@ __global__ void __launch_bounds__(PW * 64) attn_probs_lines_kernel(const AttnKPa
           const int kfirst = j + 32 * kblk + 16 * hi;
           if (j + STEP <= j_end) {   // wave-uniform: whole steps need no key mask
 #pragma unroll
-            for (int r = 0; r < 16; ++r) msum[qi] += fast_exp2(__builtin_fmaf(sc[qi][r], p.scale_log2, -lse2[qi]));
+            for (int r = 0; r < 16; ++r) msum[qi] += prob(sc[qi][r], p.scale_log2, lse2[qi]);
           } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-              const float e = fast_exp2(__builtin_fmaf(sc[qi][r], p.scale_log2, -lse2[qi]));
+              const float e = prob(sc[qi][r], p.scale_log2, lse2[qi]);
               msum[qi] += (kfirst + r < j_end) ? e : 0.f;
             }
           }
@@ -172,8 +144,7 @@ __global__ void __launch_bounds__(PW * 64) attn_probs_lines_kernel(const AttnKPa
           unsigned w[8];
 #pragma unroll
           for (int r = 0; r < 16; r += 2)
-            w[r >> 1] = pack2<T>(fast_exp2(__builtin_fmaf(sc[qi][r], p.scale_log2, -lse2[qi])),
-                                 fast_exp2(__builtin_fmaf(sc[qi][r + 1], p.scale_log2, -lse2[qi])));
+            w[r >> 1] = pack2<T>(prob(sc[qi][r], p.scale_log2, lse2[qi]), prob(sc[qi][r + 1], p.scale_log2, lse2[qi]));
           const int R = 32 * qi + lq;
           unsigned char* rowp = tile + R * PITCH;
           const int c0 = kblk * 4 + hi * 2;
@@ -240,7 +211,6 @@ __global__ void __launch_bounds__(PW * 64) attn_probs_generic_kernel(const AttnK
   for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const v8*)(qp + ks * 16);
 
   // output rows of this lane: q0 + crow(r,hi); their LSE in the exp2 domain
-  const float LOG2E = 1.4426950408889634f;
   float lse2[16];
   int64_t orow[16];
   bool rok[16];
@@ -257,46 +227,28 @@ __global__ void __launch_bounds__(PW * 64) attn_probs_generic_kernel(const AttnK
   const int nseg = p.include_self + p.N;
   int col0 = 0;
   for (int s = 0; s < nseg; ++s) {
-    const T* kb;
-    int64_t ksl;
-    int len;
-    if (p.include_self && s == 0) {
-      kb = (const T*)p.k_self + (int64_t)b * p.ks_sb + (int64_t)h * p.ks_sh; ksl = p.ks_sl; len = p.Ls;
-    } else {
-      const int n = s - p.include_self;
-      kb = ir_ref_entry((const T*)p.k_ref + (int64_t)b * p.kr_sb + (int64_t)n * p.kr_sn, p.ref_tables) + (int64_t)h * p.kr_sh; ksl = p.kr_sl; len = p.Lr;
-    }
+    const KeySeg<T> ks = key_segment<T>(p, b, s, h);
+    const T* kb = ks.kb;
+    const int len = ks.len;
     for (int j0 = 0; j0 < len; j0 += 32) {
       const int key = j0 + lq;
       const bool kok = key < len;
-      const T* kp = kb + (int64_t)(kok ? key : len - 1) * ksl + hi * 8;
+      const T* kp = kb + (int64_t)(kok ? key : len - 1) * ks.ksl + hi * 8;
       f32x16 sc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) sc[r] = 0.f;
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) sc = Tr::mfma(qf[ks], *(const v8*)(kp + ks * 16), sc);
+      for (int d = 0; d < 4; ++d) sc = Tr::mfma(qf[d], *(const v8*)(kp + d * 16), sc);
       // sc[r] = <Q[q0+crow(r,hi)], K[key]> ; column = lane & 31 = key
       if (kok) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          if (rok[r]) probs[orow[r] + col0 + key] = (T)fast_exp2(__builtin_fmaf(sc[r], p.scale_log2, -lse2[r]));
+          if (rok[r]) probs[orow[r] + col0 + key] = (T)prob(sc[r], p.scale_log2, lse2[r]);
         }
       }
     }
     col0 += len;
   }
-}
-
-static int device_cus() {   // per device, looked up once (idempotent: a race between threads only repeats the query)
-  static int cached[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (cached[dev] == 0) {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    cached[dev] = cus;
-  }
-  return cached[dev];
 }
 
 // Cut of the key axis: the largest chunk (whole segments first) that still leaves >= 16 workgroups per CU; never below 256 keys.
@@ -306,7 +258,7 @@ static ProbsPlan make_plan(const AttnKParams& p, int rows_per_wg, int step, bool
   const int maxlen = (p.include_self && p.Ls > p.Lr) || p.N == 0 ? p.Ls : p.Lr;
   int kc = (maxlen + step - 1) / step * step;
   if (!whole_segments) {
-    const int64_t want = (int64_t)16 * device_cus();
+    const int64_t want = (int64_t)16 * ir_device_cus();
     for (;;) {
       const int64_t ns = p.include_self ? (p.Ls + kc - 1) / kc : 0;
       const int64_t nr = p.N > 0 ? (p.Lr + kc - 1) / kc : 0;
@@ -335,6 +287,18 @@ static bool lines_ok(const AttnKParams& p) {
 }  // namespace
 
 bool ir_attn_probs_uses_lines(const AttnKParams& p) { return lines_ok(p); }
+
+int ir_device_cus() {   // per device, looked up once (idempotent: a race between threads only repeats the query)
+  static int cached[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (cached[dev] == 0) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    cached[dev] = cus;
+  }
+  return cached[dev];
+}
 
 namespace {
 template <typename T, int NQ, int NK>

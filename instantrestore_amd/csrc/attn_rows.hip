@@ -9,8 +9,7 @@
 //
 //   p[b,h,r,j] = exp2(fma(<q[b, idx[b,r], h, :], k_ext[b, j, h, :]>, scale*log2(e), -lse[b,h,idx[b,r]]*log2(e)))
 //
-// the expression of attn_probs.hip on the same fp32 MFMA result (v_mfma_f32_32x32x16, the four 16-wide steps over d in
-// ascending order), so form 0 below is the dump's rows bit for bit.
+// the expression and the contraction of ir_readout.h, which attn_probs.hip shares: form 0 below is the dump's rows bit for bit.
 //
 //   IR_ROWS_NONE       `dtype` (B, H, R, Lkv)   attention_probs[:, :, idx, :]
 //   IR_ROWS_HEAD_MEAN  fp32    (B, R, Lkv)      attn.mean(dim=1)[b][idx]            (vis_utils.py:92, 104)
@@ -18,9 +17,8 @@
 //
 // Bound: K is read once (B * H * Lkv * 128 bytes) plus the output; the gathered Q rows (R * H * 128 bytes per batch entry)
 // come from L2.  Shape of the work:
-//   * the contraction is issued SWAPPED as in attn_probs.hip (keys on the MFMA rows through keymap, the gathered rows on its
-//     columns): a lane then holds 16 CONSECUTIVE keys of ONE row per 32 x 32 block and stores them 16 bytes at a time (32 B
-//     of a 16-bit row, 64 B of an fp32 row per lane, the two half-waves side by side);
+//   * the lane layout of ir_readout.h: a lane holds 16 CONSECUTIVE keys of ONE gathered row per 32 x 32 block and stores them
+//     16 bytes at a time (32 B of a 16-bit row, 64 B of an fp32 row per lane, the two half-waves side by side);
 //   * a wave owns a key range of one segment and up to 96 rows (NQ <= 3 blocks of 32; more rows are further row groups) whose
 //     Q fragments stay in registers for the walk of that range.  Waves never exchange data: no LDS, no barrier, no atomics;
 //   * form 0: a wave walks 256 keys of one head.  Forms 1 / 2: a wave owns 64 keys and walks the HEADS in ascending order
@@ -35,10 +33,10 @@
 //     zeros; rows of the padding to 32 are neither stored nor summed.  Duplicated indices are rows like any other;
 //   * 16-byte stores need every row segment 16-byte aligned (segment lengths multiples of 8 keys for 16-bit rows, of 4 for
 //     fp32 rows); other lengths take element stores in the same kernel (a wave-uniform branch).
-#include "ir_common.h"
-#include "ir_kernels.h"
+#include "ir_readout.h"
 
 namespace {
+using namespace ir_readout;
 
 constexpr int RW = 4;            // waves per workgroup (independent of each other)
 constexpr int KEYS_FORM0 = 256;  // keys a wave walks in form 0
@@ -79,23 +77,9 @@ struct RowsPlan {
   float inv_h;    // 1 / H
 };
 
-// MFMA row i of a swapped 32 x 32 block carries key keymap(i) of the block (attn_probs.hip): lane (lq, hi) then holds
-// keys 16*hi + r, r = 0..15, of row lq
-static __device__ __forceinline__ int keymap(int i) { return (i & 3) + 4 * (i >> 3) + 16 * ((i >> 2) & 1); }
-
-template <typename T>
-static __device__ __forceinline__ unsigned pack2(float a, float b) {
-  typedef T T2 __attribute__((ext_vector_type(2)));
-  T2 v;
-  v[0] = (T)a;
-  v[1] = (T)b;
-  return __builtin_bit_cast(unsigned, v);
-}
-
 template <typename T, int NQ, int RED>
 __global__ void __launch_bounds__(RW * 64) attn_rows_kernel(const AttnKParams p, const RowsPlan pl) {
-  using Tr = ElemTraits<T>;
-  using v8 = typename Tr::v8;
+  using v8 = typename ElemTraits<T>::v8;
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int hi = lane >> 5, lq = lane & 31;
@@ -109,81 +93,34 @@ __global__ void __launch_bounds__(RW * 64) attn_rows_kernel(const AttnKParams p,
   if constexpr (RED == kRowsNone) { h0 = id % p.H; id /= p.H; }
   const int b = id;
 
-  const T* kb;   // head 0 of the segment's keys
-  int64_t ksl, ksh;
-  int len, col0, chunk;
-  if (c < pl.nch_self) {
-    kb = (const T*)p.k_self + (int64_t)b * p.ks_sb; ksl = p.ks_sl; ksh = p.ks_sh; len = p.Ls; col0 = 0; chunk = c;
-  } else {
-    const int cr = c - pl.nch_self;
-    const int n = cr / pl.nch_ref;
-    chunk = cr - n * pl.nch_ref;
-    kb = ir_ref_entry((const T*)p.k_ref + (int64_t)b * p.kr_sb + (int64_t)n * p.kr_sn, p.ref_tables); ksl = p.kr_sl; ksh = p.kr_sh; len = p.Lr;
-    col0 = p.include_self * p.Ls + n * p.Lr;
-  }
-  const int j_begin = (chunk * RW + wid) * pl.kpw;
+  const KeyChunk<T> kc = key_chunk<T>(p, b, c, pl.nch_self, pl.nch_ref);
+  const KeySeg<T> ks = kc.ks;   // keys past its end are clamped as addresses; their columns are not stored
+  const int len = ks.len, col0 = kc.col0;
+  const int j_begin = (kc.chunk * RW + wid) * pl.kpw;
   if (j_begin >= len) return;
   const int j_end = (j_begin + pl.kpw < len) ? j_begin + pl.kpw : len;
 
-  const float LOG2E = 1.4426950408889634f;
   const int km = keymap(lq);
   const int32_t* idx = pl.idx + (int64_t)b * pl.R;
-
-  // rows of group g held by this lane: r = (g * NQ + qi) * 32 + lq; their token index (row 0 for padding and indices out of range)
-  auto load_idx = [&](int g, int (&qrow)[NQ], bool (&ok)[NQ]) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi) {
-      const int r = (g * NQ + qi) * 32 + lq;
-      const int ix = r < pl.R ? idx[r] : -1;
-      ok[qi] = (unsigned)ix < (unsigned)p.Lq;
-      qrow[qi] = ok[qi] ? ix : 0;
-    }
-  };
-  // B operand: Q[row][d = 16ks + 8hi ..] of head h; the LSE of that row in the exp2 domain
-  auto load_q = [&](int h, const int (&qrow)[NQ], v8 (&qf)[NQ][4], float (&lse2)[NQ]) {
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi) {
-      const T* qp = (const T*)p.q + (int64_t)b * p.q_sb + (int64_t)qrow[qi] * p.q_sl + (int64_t)h * p.q_sh + hi * 8;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) qf[qi][ks] = *(const v8*)(qp + ks * 16);
-      lse2[qi] = p.lse[((int64_t)b * p.H + h) * p.Lq + qrow[qi]] * LOG2E;
-    }
-  };
-  // A operand: K[key j + keymap(lq)][d = 16ks + 8hi ..] of head h, keys past the segment clamped (their columns are not stored)
-  auto load_k = [&](int h, int j, v8 (&kf)[4]) {
-    const int key = j + km;
-    const T* kp = kb + (int64_t)h * ksh + (int64_t)(key < len ? key : len - 1) * ksl + hi * 8;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) kf[ks] = *(const v8*)(kp + ks * 16);
-  };
-  // sc[r] = <K[j + 16 hi + r], Q[row of qi]>
-  auto scores = [&](const v8 (&kf)[4], const v8 (&qf)[4]) {
-    f32x16 sc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) sc[r] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) sc = Tr::mfma(kf[ks], qf[ks], sc);
-    return sc;
-  };
 
   if constexpr (RED == kRowsNone) {
     int qrow[NQ];
     bool ok[NQ];
     v8 qf[NQ][4];
     float lse2[NQ];
-    load_idx(g0, qrow, ok);
-    load_q(h0, qrow, qf, lse2);
+    gather_rows<NQ>(idx, pl.R, p.Lq, g0, lq, qrow, ok);
+    load_q<T, NQ>(p, b, h0, hi, qrow, qf, lse2);
     v8 kf[2][4];
-    load_k(h0, j_begin, kf[0]);
-    load_k(h0, j_begin + 32, kf[1]);
+    load_k(ks, h0, j_begin + km, hi, kf[0]);
+    load_k(ks, h0, j_begin + 32 + km, hi, kf[1]);
     T* const obase = (T*)pl.out + (((int64_t)b * p.H + h0) * pl.R) * (int64_t)p.lkv + col0;
     for (int j = j_begin; j < j_end; j += 64) {
 #pragma unroll
       for (int kblk = 0; kblk < 2; ++kblk) {
         f32x16 sc[NQ];
 #pragma unroll
-        for (int qi = 0; qi < NQ; ++qi) sc[qi] = scores(kf[kblk], qf[qi]);
-        load_k(h0, j + 64 + 32 * kblk, kf[kblk]);   // the next step's fragments arrive while this step's exponentials run (clamped: a valid address)
+        for (int qi = 0; qi < NQ; ++qi) sc[qi] = scores<T>(kf[kblk], qf[qi]);
+        load_k(ks, h0, j + 64 + 32 * kblk + km, hi, kf[kblk]);   // the next step's fragments arrive while this step's exponentials run (clamped: a valid address)
         const int key0 = j + 32 * kblk + 16 * hi;
 #pragma unroll
         for (int qi = 0; qi < NQ; ++qi) {
@@ -191,7 +128,7 @@ __global__ void __launch_bounds__(RW * 64) attn_rows_kernel(const AttnKParams p,
           float e[16];
 #pragma unroll
           for (int t = 0; t < 16; ++t) {
-            const float x = fast_exp2(__builtin_fmaf(sc[qi][t], p.scale_log2, -lse2[qi]));
+            const float x = prob(sc[qi][t], p.scale_log2, lse2[qi]);
             e[t] = ok[qi] ? x : 0.f;
           }
           if (r < pl.R) {
@@ -222,7 +159,7 @@ __global__ void __launch_bounds__(RW * 64) attn_rows_kernel(const AttnKParams p,
     for (int g = g_first; g < g_last; ++g) {
       int qrow[NQ];
       bool ok[NQ];
-      load_idx(g, qrow, ok);
+      gather_rows<NQ>(idx, pl.R, p.Lq, g, lq, qrow, ok);
       f32x16 acc[KB][NQ];
 #pragma unroll
       for (int kblk = 0; kblk < KB; ++kblk)
@@ -235,16 +172,16 @@ __global__ void __launch_bounds__(RW * 64) attn_rows_kernel(const AttnKParams p,
         float lse2[NQ];
         v8 kf[KB][4];
 #pragma unroll
-        for (int kblk = 0; kblk < KB; ++kblk) load_k(h, j_begin + 32 * kblk, kf[kblk]);
-        load_q(h, qrow, qf, lse2);
+        for (int kblk = 0; kblk < KB; ++kblk) load_k(ks, h, j_begin + 32 * kblk + km, hi, kf[kblk]);
+        load_q<T, NQ>(p, b, h, hi, qrow, qf, lse2);
 #pragma unroll
         for (int kblk = 0; kblk < KB; ++kblk) {
 #pragma unroll
           for (int qi = 0; qi < NQ; ++qi) {
-            const f32x16 sc = scores(kf[kblk], qf[qi]);
+            const f32x16 sc = scores<T>(kf[kblk], qf[qi]);
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
-              const float x = fast_exp2(__builtin_fmaf(sc[t], p.scale_log2, -lse2[qi]));
+              const float x = prob(sc[t], p.scale_log2, lse2[qi]);
               acc[kblk][qi][t] += ok[qi] ? x : 0.f;
             }
           }
@@ -307,27 +244,6 @@ __global__ void __launch_bounds__(RW * 64) attn_rows_kernel(const AttnKParams p,
   }
 }
 
-template <typename T, int NQ>
-hipError_t launch_nq(const AttnKParams& p, const RowsPlan& pl, int reduce, int items, hipStream_t s) {
-  const dim3 grid(items), block(RW * 64);
-  switch (reduce) {
-    case kRowsNone: hipLaunchKernelGGL((attn_rows_kernel<T, NQ, kRowsNone>), grid, block, 0, s, p, pl); break;
-    case kRowsHeadMean: hipLaunchKernelGGL((attn_rows_kernel<T, NQ, kRowsHeadMean>), grid, block, 0, s, p, pl); break;
-    case kRowsMap: hipLaunchKernelGGL((attn_rows_kernel<T, NQ, kRowsMap>), grid, block, 0, s, p, pl); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_t(const AttnKParams& p, const RowsPlan& pl, int nq, int reduce, int items, hipStream_t s) {
-  switch (nq) {
-    case 1: return launch_nq<T, 1>(p, pl, reduce, items, s);
-    case 2: return launch_nq<T, 2>(p, pl, reduce, items, s);
-    default: return launch_nq<T, 3>(p, pl, reduce, items, s);
-  }
-}
-
 }  // namespace
 
 hipError_t ir_launch_attn_rows(const AttnKParams& p, int dtype, const int32_t* row_index, int n_rows, int reduce, void* out, hipStream_t s) {
@@ -335,9 +251,7 @@ hipError_t ir_launch_attn_rows(const AttnKParams& p, int dtype, const int32_t* r
   pl.idx = row_index;
   pl.out = out;
   pl.R = n_rows;
-  const int nblk = (n_rows + 31) / 32;
-  const int nq = nblk < 3 ? nblk : 3;   // 32-row blocks a wave holds: the padded row count up to 96, three beyond
-  pl.ngroups = (nblk + nq - 1) / nq;
+  pl.ngroups = rows_ngroups(n_rows);
   pl.kpw = reduce == kRowsNone ? KEYS_FORM0 : KEYS_SUM;
   const int kc = RW * pl.kpw;
   pl.nch_self = p.include_self ? (p.Ls + kc - 1) / kc : 0;
@@ -348,5 +262,16 @@ hipError_t ir_launch_attn_rows(const AttnKParams& p, int dtype, const int32_t* r
   pl.inv_h = 1.0f / (float)p.H;
   const int64_t items = (int64_t)p.B * (reduce == kRowsNone ? p.H : 1) * pl.nch_total * (reduce == kRowsMap ? 1 : pl.ngroups);
   if (items <= 0 || items > 0x7fffffffLL) return hipErrorInvalidValue;
-  return dtype == 1 ? launch_t<__bf16>(p, pl, nq, reduce, (int)items, s) : launch_t<_Float16>(p, pl, nq, reduce, (int)items, s);
+  return dispatch_rows(dtype, n_rows, [&](auto t, auto nq) {
+    using T = typename decltype(t)::type;
+    constexpr int NQ = decltype(nq)::value;
+    const dim3 grid((int)items), block(RW * 64);
+    switch (reduce) {
+      case kRowsNone: hipLaunchKernelGGL((attn_rows_kernel<T, NQ, kRowsNone>), grid, block, 0, s, p, pl); break;
+      case kRowsHeadMean: hipLaunchKernelGGL((attn_rows_kernel<T, NQ, kRowsHeadMean>), grid, block, 0, s, p, pl); break;
+      case kRowsMap: hipLaunchKernelGGL((attn_rows_kernel<T, NQ, kRowsMap>), grid, block, 0, s, p, pl); break;
+      default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+  });
 }

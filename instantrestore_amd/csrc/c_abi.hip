@@ -35,7 +35,7 @@ int64_t seg_stride_limit(int32_t len, int64_t sl) {
 }
 
 // `fwd`: the call is (or describes) a launch of the attention forward, whose segment-span limit applies; the read-out entry points
-// (ir_attn_probs*, ir_attn_segment_mass, ir_attn_rows) address K through 64-bit pointers and take any stride
+// (ir_attn_probs*, ir_attn_segment_mass, ir_attn_rows, ir_attn_match) address K through 64-bit pointers and take any stride
 bool attn_block_size_ok(uint32_t n) {
   return n == sizeof(ir_shared_attn_args) || n == sizeof(ir_shared_attn_table_args) || n == sizeof(ir_shared_attn_bias_args) ||
          n == sizeof(ir_shared_attn_ragged_args);
@@ -86,7 +86,7 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
   if (a->seg_mass != nullptr && (reinterpret_cast<uintptr_t>(a->seg_mass) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "seg_mass must be 4-byte aligned");
   if (kbias != nullptr) {
     if (!fwd)
-      return fail(IR_ERR_UNSUPPORTED, "key_bias: ir_attn_probs[_ex], ir_attn_segment_mass and ir_attn_rows do not take a key bias yet (their exp(s - lse) would "
+      return fail(IR_ERR_UNSUPPORTED, "key_bias: ir_attn_probs[_ex], ir_attn_segment_mass, ir_attn_rows and ir_attn_match do not take a key bias yet (their exp(s - lse) would "
                   "leave it out); the forward's seg_mass by-product does");
     if ((reinterpret_cast<uintptr_t>(kbias) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "key_bias must be 4-byte aligned");
     if (ba->kb_sb < 0 || ba->kb_sh < 0) return fail(IR_ERR_INVALID_ARG, "key_bias strides kb_sb %lld, kb_sh %lld must be >= 0", (long long)ba->kb_sb, (long long)ba->kb_sh);
@@ -99,7 +99,7 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
   }
   if (rlens != nullptr) {
     if (!fwd)
-      return fail(IR_ERR_UNSUPPORTED, "ref_lens: ir_attn_probs[_ex], ir_attn_segment_mass and ir_attn_rows do not take per-reference counts yet (they would "
+      return fail(IR_ERR_UNSUPPORTED, "ref_lens: ir_attn_probs[_ex], ir_attn_segment_mass, ir_attn_rows and ir_attn_match do not take per-reference counts yet (they would "
                   "walk the tails behind the counts); the forward's seg_mass by-product does");
     if ((reinterpret_cast<uintptr_t>(rlens) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "ref_lens must be 4-byte aligned");
     if (a->n_refs == 0) return fail(IR_ERR_UNSUPPORTED, "ref_lens with n_refs == 0: there is no reference to count");
@@ -238,6 +238,39 @@ int launch_fwd(const ir_shared_attn_args* a, const AttnKParams& p, hipStream_t s
   return IR_OK;
 }
 
+// The parameter block of a read-out of the forward's LSE (ir_attn_probs_ex, ir_attn_segment_mass, ir_attn_rows, ir_attn_match).
+// `single_kernel`: the name of an entry point that has one kernel and refuses a tuning value, or nullptr.  A key bias and
+// per-reference counts are refused for the whole family in build_attn_params (!fwd)
+int build_readout_params(const ir_shared_attn_args* args, AttnKParams* p, const char* single_kernel) {
+  if (single_kernel != nullptr) {
+    if (args == nullptr) return fail(IR_ERR_INVALID_ARG, "args is NULL");
+    if (attn_block_size_ok(args->struct_size) && args->tuning != IR_TUNE_DEFAULT)
+      return fail(IR_ERR_UNSUPPORTED, "%s has one kernel: tuning must be 0 (got %d)", single_kernel, args->tuning);
+  }
+  const int rc = build_attn_params(args, p, false, false);
+  if (rc != IR_OK) return rc;
+  if (p->q_prescaled) p->scale_log2 = 1.0f;   // IR_FLAG_Q_PRESCALED: the products of q and k ARE the exponents (`scale` is the LSE's unit only)
+  return IR_OK;
+}
+
+// What ir_attn_rows and ir_attn_match check of their own arguments, in the order both make the checks: every NULL, n_rows, the
+// form (0 .. n_forms - 1, `forms` names them), every alignment
+struct OutArg { const char* name; const void* ptr; unsigned align; };
+template <size_t N>
+int check_row_readout(const ir_shared_attn_args* args, const int32_t* row_index, int32_t n_rows, int32_t reduce, int32_t n_forms, const char* forms,
+                      const OutArg (&outs)[N]) {
+  if (row_index == nullptr) return fail(IR_ERR_INVALID_ARG, "row_index is NULL");
+  for (const OutArg& o : outs)
+    if (o.ptr == nullptr) return fail(IR_ERR_INVALID_ARG, "%s is NULL", o.name);
+  if (args->lse == nullptr) return fail(IR_ERR_INVALID_ARG, "lse is NULL");
+  if (n_rows < 1 || n_rows > args->len_q) return fail(IR_ERR_INVALID_ARG, "n_rows %d outside [1, len_q = %d]", n_rows, args->len_q);
+  if (reduce < 0 || reduce >= n_forms) return fail(IR_ERR_UNSUPPORTED, "reduce %d: %s", reduce, forms);
+  if ((reinterpret_cast<uintptr_t>(row_index) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "row_index must be 4-byte aligned");
+  for (const OutArg& o : outs)
+    if ((reinterpret_cast<uintptr_t>(o.ptr) & (o.align - 1)) != 0) return fail(IR_ERR_UNSUPPORTED, "%s must be %u-byte aligned", o.name, o.align);
+  return IR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -363,19 +396,13 @@ int ir_time_shared_attn_fwd(const ir_shared_attn_args* args, int32_t iters, void
   return IR_OK;
 }
 
-static int bench_blocks() {   // one 8-wave workgroup per CU = two waves per SIMD
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  return cus;
-}
-
 size_t ir_bench_mfma_stream_scratch_bytes(void) { return (size_t)1024 * 512 * sizeof(float); }   // up to 1024 CUs
 
 int ir_bench_mfma_stream(int32_t dtype, int32_t zero_operands, int32_t iters, int32_t launches, void* scratch, size_t scratch_bytes,
                          void* stream, float* tflops) {
   if (dtype != IR_DTYPE_F16 && dtype != IR_DTYPE_BF16) return fail(IR_ERR_UNSUPPORTED, "dtype %d: fp16 (0) / bf16 (1)", dtype);
   if (iters <= 0 || launches <= 0 || tflops == nullptr || scratch == nullptr) return fail(IR_ERR_INVALID_ARG, "iters/launches/scratch/tflops");
-  const int blocks = bench_blocks();
+  const int blocks = ir_device_cus();   // one 8-wave workgroup per CU = two waves per SIMD
   if (blocks > 1024 || scratch_bytes < (size_t)blocks * 512 * sizeof(float)) return fail(IR_ERR_WORKSPACE, "scratch %zu < %zu bytes", scratch_bytes, (size_t)blocks * 512 * sizeof(float));
   hipStream_t s = (hipStream_t)stream;
   hipEvent_t e0, e1;
@@ -398,12 +425,11 @@ int ir_bench_mfma_stream(int32_t dtype, int32_t zero_operands, int32_t iters, in
 
 int ir_attn_probs_ex(const ir_shared_attn_args* args, void* probs, int32_t kernel, void* stream) {
   AttnKParams p;
-  const int rc = build_attn_params(args, &p, false, false);
+  const int rc = build_readout_params(args, &p, nullptr);
   if (rc != IR_OK) return rc;
   if (probs == nullptr || args->lse == nullptr) return fail(IR_ERR_INVALID_ARG, "probs/lse is NULL");
   if (kernel < IR_PROBS_AUTO || kernel > IR_PROBS_LINES32_K256) return fail(IR_ERR_UNSUPPORTED, "attn_probs kernel %d", kernel);
   p.probs = probs;
-  if (p.q_prescaled) p.scale_log2 = 1.0f;   // IR_FLAG_Q_PRESCALED: the products of q and k ARE the exponents (`scale` is the LSE's unit only)
   if (kernel >= IR_PROBS_LINES64 && !ir_attn_probs_uses_lines(p))
     return fail(IR_ERR_UNSUPPORTED, "the line kernel needs len_self, len_ref (and so Lkv) to be multiples of 8 and probs 16-byte aligned");
   const hipError_t e = ir_launch_attn_probs(p, args->dtype, kernel, (hipStream_t)stream);
@@ -415,31 +441,21 @@ int ir_attn_probs(const ir_shared_attn_args* args, void* probs, void* stream) { 
 
 int ir_attn_segment_mass(const ir_shared_attn_args* args, float* mass, void* stream) {
   AttnKParams p;
-  const int rc = build_attn_params(args, &p, false, false);
+  const int rc = build_readout_params(args, &p, nullptr);
   if (rc != IR_OK) return rc;
   if (mass == nullptr || args->lse == nullptr) return fail(IR_ERR_INVALID_ARG, "mass/lse is NULL");
-  if (p.q_prescaled) p.scale_log2 = 1.0f;
   const hipError_t e = ir_launch_attn_segment_mass(p, args->dtype, mass, (hipStream_t)stream);
   if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "attn_segment_mass launch: %s", hipGetErrorString(e));
   return IR_OK;
 }
 
 int ir_attn_rows(const ir_shared_attn_args* args, const int32_t* row_index, int32_t n_rows, int32_t reduce, void* out, void* stream) {
-  if (args == nullptr) return fail(IR_ERR_INVALID_ARG, "args is NULL");
-  if (attn_block_size_ok(args->struct_size) && args->tuning != IR_TUNE_DEFAULT)
-    return fail(IR_ERR_UNSUPPORTED, "ir_attn_rows has one kernel: tuning must be 0 (got %d)", args->tuning);
   AttnKParams p;
-  const int rc = build_attn_params(args, &p, false, false);
+  int rc = build_readout_params(args, &p, "ir_attn_rows");
   if (rc != IR_OK) return rc;
-  if (row_index == nullptr) return fail(IR_ERR_INVALID_ARG, "row_index is NULL");
-  if (out == nullptr) return fail(IR_ERR_INVALID_ARG, "out is NULL");
-  if (args->lse == nullptr) return fail(IR_ERR_INVALID_ARG, "lse is NULL");
-  if (n_rows < 1 || n_rows > args->len_q) return fail(IR_ERR_INVALID_ARG, "n_rows %d outside [1, len_q = %d]", n_rows, args->len_q);
-  if (reduce != IR_ROWS_NONE && reduce != IR_ROWS_HEAD_MEAN && reduce != IR_ROWS_MAP)
-    return fail(IR_ERR_UNSUPPORTED, "reduce %d: IR_ROWS_NONE (0), IR_ROWS_HEAD_MEAN (1) or IR_ROWS_MAP (2)", reduce);
-  if ((reinterpret_cast<uintptr_t>(row_index) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "row_index must be 4-byte aligned");
-  if (!aligned16(out)) return fail(IR_ERR_UNSUPPORTED, "out must be 16-byte aligned");
-  if (p.q_prescaled) p.scale_log2 = 1.0f;   // as in ir_attn_probs: the products of a pre-scaled q and k ARE the exponents
+  const OutArg outs[] = {{"out", out, 16}};
+  rc = check_row_readout(args, row_index, n_rows, reduce, 3, "IR_ROWS_NONE (0), IR_ROWS_HEAD_MEAN (1) or IR_ROWS_MAP (2)", outs);
+  if (rc != IR_OK) return rc;
   const hipError_t e = ir_launch_attn_rows(p, args->dtype, row_index, n_rows, reduce, out, (hipStream_t)stream);
   if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "attn_rows launch: %s", hipGetErrorString(e));
   return IR_OK;
@@ -447,24 +463,13 @@ int ir_attn_rows(const ir_shared_attn_args* args, const int32_t* row_index, int3
 
 int ir_attn_match(const ir_shared_attn_args* args, const int32_t* row_index, int32_t n_rows, int32_t reduce, int32_t* index, float* prob,
                   void* stream) {
-  if (args == nullptr) return fail(IR_ERR_INVALID_ARG, "args is NULL");
-  if (attn_block_size_ok(args->struct_size) && args->tuning != IR_TUNE_DEFAULT)
-    return fail(IR_ERR_UNSUPPORTED, "ir_attn_match has one kernel: tuning must be 0 (got %d)", args->tuning);
   AttnKParams p;
-  const int rc = build_attn_params(args, &p, false, false);
+  int rc = build_readout_params(args, &p, "ir_attn_match");
   if (rc != IR_OK) return rc;
-  if (row_index == nullptr) return fail(IR_ERR_INVALID_ARG, "row_index is NULL");
-  if (index == nullptr) return fail(IR_ERR_INVALID_ARG, "index is NULL");
-  if (prob == nullptr) return fail(IR_ERR_INVALID_ARG, "prob is NULL");
-  if (args->lse == nullptr) return fail(IR_ERR_INVALID_ARG, "lse is NULL");
-  if (n_rows < 1 || n_rows > args->len_q) return fail(IR_ERR_INVALID_ARG, "n_rows %d outside [1, len_q = %d]", n_rows, args->len_q);
-  if (reduce != IR_MATCH_PER_HEAD && reduce != IR_MATCH_HEAD_MEAN)
-    return fail(IR_ERR_UNSUPPORTED, "reduce %d: IR_MATCH_PER_HEAD (0) or IR_MATCH_HEAD_MEAN (1)", reduce);
-  if ((reinterpret_cast<uintptr_t>(row_index) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "row_index must be 4-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(index) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "index must be 4-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(prob) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "prob must be 4-byte aligned");
+  const OutArg outs[] = {{"index", index, 4}, {"prob", prob, 4}};
+  rc = check_row_readout(args, row_index, n_rows, reduce, 2, "IR_MATCH_PER_HEAD (0) or IR_MATCH_HEAD_MEAN (1)", outs);
+  if (rc != IR_OK) return rc;
   if (ir_attn_match_items(p, n_rows, reduce) > kMatchMaxItems) return fail(IR_ERR_UNSUPPORTED, "grid too large");
-  if (p.q_prescaled) p.scale_log2 = 1.0f;   // as in ir_attn_probs: the products of a pre-scaled q and k ARE the exponents
   const hipError_t e = ir_launch_attn_match(p, args->dtype, row_index, n_rows, reduce, index, prob, (hipStream_t)stream);
   if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "attn_match launch: %s", hipGetErrorString(e));
   return IR_OK;

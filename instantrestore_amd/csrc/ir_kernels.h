@@ -205,6 +205,7 @@ bool ir_attn_variant_available(int variant);
 // variant: 0 = automatic (line kernel when every segment length is a multiple of 8), 1 = round 1's 2-byte-store kernel,
 // 2 / 3 = the line kernel with 64 / 32 query rows per wave
 hipError_t ir_launch_attn_probs(const AttnKParams& p, int dtype, int variant, hipStream_t s);
+int ir_device_cus();   // compute units of the current device (256 when the query fails); attn_probs.hip
 bool ir_attn_probs_uses_lines(const AttnKParams& p);
 hipError_t ir_launch_attn_segment_mass(const AttnKParams& p, int dtype, float* mass, hipStream_t s);
 // attn_rows.hip: the probability rows of `n_rows` chosen query tokens per batch entry (row_index: int32 (B, n_rows) on the device),
