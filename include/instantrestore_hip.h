@@ -265,8 +265,9 @@ typedef struct ir_shared_attn_ragged_args {
                                       seg_mass (the default dispatch still keeps calls that carry either on the kernel it chose
                                       before: IR_ATTN_W128=1 in the environment sends them to this one) */
 #define IR_TUNE_W64_ABL_FIRST 20 /* 20 ... : development builds (-DIR_ABLATIONS) only - energy / timing ablations of the 64-row kernel
-                                    (WRONG results: one class of work removed per bit; tools/gpu_energy_probe.py).  Value 17
-                                    (rounds 2-3: a three-stage experiment) is retired. */
+                                    (WRONG results: one class of work removed per bit; tools/gpu_energy_probe.py).  Values 3, 4,
+                                    6, 9 (round 1: experiments inside the 32-row kernel) and 17 (rounds 2-3: a three-stage
+                                    experiment) are retired: every build refuses them. */
 #define IR_TUNE_PIPE32_POSTCHECK 18   /* 32-row kernel, pre-scaled Q, reference checked after the exponentials (needs
                                          IR_FLAG_Q_PRESCALED; parity-green, same speed as PIPE32_PRESCALE_Q: opt-in) */
 

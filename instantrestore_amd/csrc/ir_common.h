@@ -85,13 +85,6 @@ static __device__ __forceinline__ float max3(float a, float b, float c) {
   return r;
 }
 
-// LDS-DMA: 16 bytes per lane straight from a buffer resource into LDS at (wave-uniform base +
-// lane*16).  Kept in a __device__ helper: the host pass must not see the address-space cast.
-static __device__ __forceinline__ void buffer_load_lds16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_base,
-                                                         unsigned voffset) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (IR_LDS void*)lds_base, 16, voffset, 0, 0, 0);
-}
-
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 
 // Raw buffer descriptor words (base, stride 0, num_records, flags) for hand-issued buffer ops.
@@ -105,7 +98,8 @@ static __device__ __forceinline__ i32x4 make_rsrc_words(const void* base, unsign
   return r;
 }
 
-// LDS-DMA issued from inline asm: invisible to hipcc's waitcnt bookkeeping, so the transfer stays
+// LDS-DMA: 16 bytes per lane straight from a buffer resource into LDS at (wave-uniform base + lane*16).
+// Issued from inline asm: invisible to hipcc's waitcnt bookkeeping, so the transfer stays
 // in flight across LDS reads until OUR s_waitcnt vmcnt(0) (placed before the step's barrier).
 // M0 (the LDS destination base) is written in the same statement that consumes it.
 static __device__ __forceinline__ void buffer_load_lds16_async(i32x4 rsrc, unsigned char* lds_base, unsigned voffset) {

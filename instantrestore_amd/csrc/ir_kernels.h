@@ -104,17 +104,16 @@ enum IrAttnFamily {
   IR_FAM_W64X8,         // 64 rows per wave, 8-wave (512-row) workgroups (shared_attn_fwd_w64.hip) ...
   IR_FAM_W64X4,         // ... 4 waves
   IR_FAM_PIPE32,        // software-pipelined 32-row kernel (shared_attn_fwd_pipe.hip), in one of its forms
-  IR_FAM_DEV            // -DIR_ABLATIONS builds: the straight-line kernel, the 64-row kernel's ablations, the `>> 5` ablation bits
+  IR_FAM_DEV            // -DIR_ABLATIONS builds: the straight-line kernel with its `>> 5` ablation bits, the 64-row kernel's ablations
 };
-enum IrPipeForm {   // template forms of the 32-row kernel (shared_attn_fwd_pipe.hip's launch_t has the template arguments)
+enum IrPipeForm {   // the product forms of the 32-row kernel (shared_attn_fwd_pipe.hip: one Form... struct each; launch_t maps these to them)
   IR_PIPE_NONE = 0,
-  IR_PIPE_EXACT,        // asm-issued LDS-DMA staging, exact (every-change) rescale
+  IR_PIPE_EXACT,        // exact (every-change) rescale
   IR_PIPE_LAZY,         // + lazy max
   IR_PIPE_PRESC,        // + pre-scaled Q, reference through the MFMA C operand
   IR_PIPE_EARLYQK,      // LAZY with the next tile's QK^T issued before the row max
-  IR_PIPE_POSTCHECK,    // PRESC with the reference checked after the exponentials (no row max on ordinary tiles; K ring of 3)
-  IR_PIPE_DEV_REG4, IR_PIPE_DEV_REG8, IR_PIPE_DEV_DMA, IR_PIPE_DEV_STRAIGHT3   // development builds: register staging with 4 / 8 waves,
-};                                                                             // builtin LDS-DMA, straight schedule at 3 waves/SIMD
+  IR_PIPE_POSTCHECK     // PRESC with the reference checked after the exponentials (no row max on ordinary tiles; K ring of 3)
+};
 struct IrAttnVariant {   // one tuning value (IR_TUNE_*)
   int id;
   IrAttnFamily family;   // (IR_TUNE_DEFAULT: what the default rules fall back to)
@@ -184,7 +183,6 @@ hipError_t ir_launch_shared_attn_fwd(const AttnKParams& p, int dtype, int varian
 hipError_t ir_launch_shared_attn_fwd_pipe(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s);
 hipError_t ir_launch_shared_attn_fwd_pipe_bias(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s);   // key_bias: PRESC / EARLYQK (shared_attn_fwd_pipe_bias.hip)
 hipError_t ir_launch_shared_attn_fwd_pipe_ragged(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s);   // ref_lens: PRESC / EARLYQK (shared_attn_fwd_pipe_ragged.hip)
-hipError_t ir_launch_shared_attn_fwd_pipe_abl(const AttnKParams& p, int abl, hipStream_t s);
 hipError_t ir_launch_shared_attn_combine(const AttnKParams& p, int dtype, int qb, int rem, hipStream_t s);
 hipError_t ir_launch_shared_attn_fwd_w64(const AttnKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_shared_attn_fwd_w64x8(const AttnKParams& p, int dtype, hipStream_t s);

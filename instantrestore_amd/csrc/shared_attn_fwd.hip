@@ -416,13 +416,14 @@ hipError_t launch_t(const AttnKParams& p, int nw, hipStream_t s) {
 // variant & 31 selects the kernel (per-call tuning field of ir_shared_attn_args; 0 = default dispatch, see
 // ir_attn_default_is_w64).  One row per tuning value: everything that asks "which values ..." reads this table.
 // Development builds only (tools/experiments/build.sh, -DIR_ABLATIONS; documented experiments, NOTES.md): 1/2 this file's
-// straight-line kernel with 8 / 4 waves, 3/4 pipelined with register staging, 6 pipelined + builtin LDS-DMA, 9 straight
-// schedule at 3 waves/SIMD; 20-28 the energy / timing ablations of the 64-row QS kernel (shared_attn_fwd_w64.hip, WRONG
-// results); variant >> 5: ablation bits of the 32-row kernels (timing experiments, WRONG results).  Those variants write
-// 16-bit results only: they are rejected together with IR_FLAG_OUT_F32.  (Rounds 1-3 also carried 8 ping-pong wave groups,
+// straight-line kernel with 8 / 4 waves; 20-28 the energy / timing ablations of the 64-row QS kernel (shared_attn_fwd_w64.hip,
+// WRONG results); variant >> 5: ablation bits of the straight-line kernel (timing experiments, WRONG results).  Those variants
+// write 16-bit results only: they are rejected together with IR_FLAG_OUT_F32.  (Rounds 1-3 also carried 8 ping-pong wave groups,
 // 15 the 64-row kernel with rotated phases, 16 one wave per SIMD, 17 a three-stage 32-row pipeline: measured negative
 // results - NOTES.md 4.1b, 4.1b', profiles/r1_pp_phase_trace.txt, r2_sp_ablation.txt - whose sources were second copies of
-// product kernel bodies and left the tree in round 5.)
+// product kernel bodies and left the tree in round 5.  The 32-row kernel's own experiments - 3/4 register staging with 4 / 8
+// waves, 6 builtin LDS-DMA, 9 the straight schedule at 3 waves/SIMD, and its ablation bits - were branches inside the product
+// kernel's body and left it the same way: NOTES.md 4.1 has their numbers, git history their code.)
 static const IrAttnVariant kAttnVariants[] = {
     // id                         family          32-row form           presc. Q  seg_mass  product
     {IR_TUNE_DEFAULT,             IR_FAM_PIPE32,  IR_PIPE_EARLYQK,      true,     true,     true},   // the rules of ir_attn_choose; this row where none takes a larger kernel
@@ -437,10 +438,6 @@ static const IrAttnVariant kAttnVariants[] = {
 #ifdef IR_ABLATIONS
     {1,                           IR_FAM_DEV,     IR_PIPE_NONE,         false,    false,    false},
     {2,                           IR_FAM_DEV,     IR_PIPE_NONE,         false,    false,    false},
-    {3,                           IR_FAM_PIPE32,  IR_PIPE_DEV_REG4,     false,    false,    false},
-    {4,                           IR_FAM_PIPE32,  IR_PIPE_DEV_REG8,     false,    false,    false},
-    {6,                           IR_FAM_PIPE32,  IR_PIPE_DEV_DMA,      false,    false,    false},
-    {9,                           IR_FAM_PIPE32,  IR_PIPE_DEV_STRAIGHT3, false,   false,    false},
 #endif
 };
 #ifdef IR_ABLATIONS
@@ -615,7 +612,6 @@ hipError_t ir_launch_shared_attn_fwd_bi(const AttnKParams& p, int dtype, const I
 #ifdef IR_ABLATIONS
 static hipError_t launch_dev(const AttnKParams& p, int dtype, int variant, hipStream_t s) {
   const int abl = variant >> 5, base = variant & 31;
-  if (abl != 0 && base == 3) return ir_launch_shared_attn_fwd_pipe_abl(p, abl, s);
   if (abl != 0) {
     switch (abl & 7) {
       case 1: return launch<__bf16, 4, false, 1>(p, s);

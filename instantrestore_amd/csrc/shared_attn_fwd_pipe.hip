@@ -13,7 +13,13 @@
 //
 // so the matrix pipe works on tile t+1's scores while the VALU exponentiates tile t's.  K is
 // staged one tile further ahead than V: K ring of 2, V ring of 3 (one prefetch stream, tiles
-// arrive as (K[j], V[j]) pairs two iterations ahead of their PV).
+// arrive as (K[j], V[j]) pairs two iterations ahead of their PV, by LDS-DMA issued from asm).
+//
+// One kernel body, nine product forms: how the running reference of the softmax is kept (exact,
+// lazy max, pre-scaled Q with the reference through the MFMA C operand, that with the reference
+// checked after the exponentials), whether the next tile's QK^T is issued before the row max, and
+// the two extensions - an additive key bias, per-reference key counts - of the two default forms.
+// The Form... structs below name them; the body reads those names and nothing else.
 //
 // VALU diet (D = 64 is VALU-issue bound): row sums as packed v_pk_add_f32 into two 2-wide
 // accumulators; scale-and-subtract as v_pk_fma_f32; AdaIN folded per SEGMENT with a lazily
@@ -32,37 +38,67 @@ namespace {
 constexpr int KVB = IR_KV_TILE;
 constexpr int TILE_BYTES = KVB * 64 * 2;  // 8 KiB
 
-// ABL (timing experiments only, WRONG results): 1 = no barrier, 2 = no LDS staging writes,
-// 4 = no global loads, 8 = no exp/pack VALU, 16 = no LDS fragment reads
+constexpr int NW = 4;                     // waves per workgroup
+constexpr int NT = NW * 64;
+constexpr int QB = NW * 32;               // query rows per work item
+
+// ---- the forms of the kernel: what each one is, by name (the kernel and the launcher read nothing else) -------------------
+// One struct per product form (IrPipeForm of ir_kernels.h), each the one it derives from plus one thing.
+struct FormExact {                               // rescale whenever some row's max moved
+  static constexpr bool lazy_max = false;        // keep the reference while no row's max grew by more than 2^6 (exp2 domain)
+  static constexpr bool presc_q = false;         // Q carries scale*log2(e); the reference enters through the C operand of the first QK^T MFMA
+  static constexpr bool early_qk = false;        // the next tile's QK^T is issued before this tile's row max
+  static constexpr bool post_check = false;      // no row max on ordinary tiles: the reference is checked after the exponentials
+  static constexpr bool key_bias = false;        // ir_shared_attn_bias_args.key_bias
+  static constexpr bool ref_counts = false;      // ir_shared_attn_ragged_args.ref_lens
+};
+struct FormLazy : FormExact { static constexpr bool lazy_max = true; };
+struct FormPresc : FormLazy { static constexpr bool presc_q = true; };
+struct FormEarlyQK : FormLazy { static constexpr bool early_qk = true; };
+struct FormPostCheck : FormPresc { static constexpr bool post_check = true; };
+// the two extensions, each instantiated in a translation unit of its own
+template <typename F> struct WithKeyBias : F { static constexpr bool key_bias = true; };       // shared_attn_fwd_pipe_bias.hip
+template <typename F> struct WithRefCounts : F { static constexpr bool ref_counts = true; };   // shared_attn_fwd_pipe_ragged.hip
+template <typename F> using NoExtension = F;
+
+template <typename F>
+constexpr bool form_is_legal() {
+  static_assert(!F::post_check || F::presc_q, "the check after the exponentials needs scores that already carry the reference");
+  static_assert(!(F::key_bias || F::ref_counts) || (F::lazy_max && !F::post_check && F::presc_q != F::early_qk),
+                "the key bias and the per-reference counts are built into the PRESC and EARLYQK forms only");
+  static_assert(!(F::key_bias && F::ref_counts), "counts together with a bias: not built (the public header names it as a follow-up)");
+  return true;
+}
+// a row may have no key at all (key bias: every key masked; counts: no self block and every count 0): exact zeros, lse = -inf,
+// in the kernel's epilogue and in the combine kernel that merges its pieces
+template <typename F> constexpr bool kRowMayHaveNoKey = F::key_bias || F::ref_counts;
+
+// F: the form (above).  FOLD: the AdaIN affine is folded in per segment.
 // MASS (ABI v9 seg_mass): also store the cumulative log-sum-exp at every segment boundary - a separate instantiation of the two
 // default forms, launched only when the caller asks for the masses
-template <typename T, int NW, bool FOLD, int ABL = 0, bool MASS = false>
-__global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) shared_attn_fwd_pipe_kernel(const AttnKParams p) {
+template <typename T, typename F, bool FOLD, bool MASS = false>
+__global__ void __launch_bounds__(NT, 2) shared_attn_fwd_pipe_kernel(const AttnKParams p) {
+  static_assert(form_is_legal<F>(), "");
   using Tr = ElemTraits<T>;
   using v8 = typename Tr::v8;
   using v4 = typename Tr::v4;
-  constexpr int NT = NW * 64;
-  constexpr int QB = NW * 32;
   constexpr int CH = (KVB * 8) / NT;
   // CHK (pre-scaled Q only): no row max on ordinary tiles - the reference is checked AFTER the exponentials (below) and a
   // tile that outgrew it is formed again from its K tile, which therefore stays in LDS one step longer: K ring of 3
-  constexpr bool CHK = (ABL & 8192) != 0;
-  static_assert(!CHK || (ABL & 2048), "the check after the exponentials needs scores that already carry the reference");
+  constexpr bool CHK = F::post_check;
   // BIAS (ir_shared_attn_bias_args.key_bias; the PRESC and EARLYQK forms, instantiated in shared_attn_fwd_pipe_bias.hip): an additive
   // fp32 term per key, in the exp2 domain, enters every tile's scores through the C operand of its first QK^T MFMA.  The S
   // registers of a tile are free between its P.V and the QK^T that refills them, so the 32 bias values a lane needs of tile t+2 are
   // fetched INTO them at the end of step t (one tile ahead of their use, no registers of their own) and turned into the C operand in
   // place.  A masked key (-inf or <= IR_KEY_BIAS_MASKED) is -inf in the C operand: -inf leaves the matrix pipe, before any row max.
-  constexpr bool BIAS = (ABL & 16384) != 0;
-  static_assert(!BIAS || (!CHK && (ABL & 256) == 0 && (ABL & 128) != 0 && ((ABL & 2048) != 0) != ((ABL & 4096) != 0)), "the key bias is built into the PRESC and EARLYQK forms only");
+  constexpr bool BIAS = F::key_bias;
   // RAGGED (ir_shared_attn_ragged_args.ref_lens; the PRESC and EARLYQK forms, instantiated in shared_attn_fwd_pipe_ragged.hip): reference
   // n of this batch entry has c_n = clamp(ref_lens[b, n], 0, Lr) keys and ceil(c_n / 64) tiles; Lr is the capacity of its segment.
   // Only what is wave-uniform and outside the tile loop changes: the item's tile count, where a piece's first tile lies, the length
   // and tile count a segment is set up with (its descriptors end at the count: the bounds check zero-fills the last tile's rows
   // behind it and the ragged-tail -inf of step (1) masks them), and the step to the next segment, which passes over c_n == 0
   // without a descriptor, a load or a fold.  The counts come through the constant address space, as table entries do.
-  constexpr bool RAGGED = (ABL & 32768) != 0;
-  static_assert(!RAGGED || (!BIAS && !CHK && (ABL & 256) == 0 && (ABL & 128) != 0 && ((ABL & 2048) != 0) != ((ABL & 4096) != 0)), "per-reference counts are built into the PRESC and EARLYQK forms only");
+  constexpr bool RAGGED = F::ref_counts;
   constexpr int KRING = CHK ? 3 : 2;
   constexpr int K_OFF = 0;                       // K ring: 2 tiles (3 with CHK)
   constexpr int V_OFF = KRING * TILE_BYTES;      // V ring: 3 tiles
@@ -134,7 +170,7 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
   // PRESC: Q carries scale*log2(e) (one more rounding of Q to the 16-bit type), so the scores leave the
   // matrix pipe already in the exp2 domain and - with the running reference fed through the C operand
   // of the first QK^T MFMA - already shifted: no per-score scale-and-subtract on the VALU.
-  constexpr bool PRESC = (ABL & 2048) != 0;
+  constexpr bool PRESC = F::presc_q;
   if (PRESC && !p.q_prescaled) {   // IR_FLAG_Q_PRESCALED: the projection already applied the factor (one rounding in all)
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
@@ -143,14 +179,9 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
 
   // ---- staging coordinates -------------------------------------------------------------------
   const int slot = tid & 7;
-  int srow[CH], koff[CH], voff[CH];
+  int srow[CH];
 #pragma unroll
-  for (int c = 0; c < CH; ++c) {
-    const int row = (tid >> 3) + c * (NT / 8);
-    srow[c] = row;
-    koff[c] = row * 128 + ((slot ^ ((row >> 1) & 7)) << 4);
-    voff[c] = row * 128 + ((slot ^ (((row >> 1) & 1) << 2)) << 4);
-  }
+  for (int c = 0; c < CH; ++c) srow[c] = (tid >> 3) + c * (NT / 8);
   int kread[4];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) kread[ks] = lq * 128 + (((2 * ks + hi) ^ ((lq >> 1) & 7)) << 4);
@@ -169,11 +200,9 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
   }
 
   // ---- prefetch stream (tile pairs j = 0, 1, 2, ...) ---------------------------------------------
-  constexpr bool DMA_FLAG = (ABL & (64 | 128 | 256)) != 0;
-  constexpr bool DMA_ASM = (ABL & (128 | 256)) != 0;  // DMA issued from inline asm, waited for by hand
+  // Global -> LDS by LDS-DMA (buffer_load ... lds, no staging registers), issued from inline asm and waited for by hand
   i32x4 krw = {0, 0, 0, 0}, vrw = {0, 0, 0, 0};
   const int nseg = p.include_self + nref;
-  __amdgpu_buffer_rsrc_t krs, vrs;
   int kstep = 0, vstep = 0, sntile = 0;
   unsigned kvo[CH], vvo[CH];
   auto seg_setup = [&](int s) {
@@ -191,59 +220,31 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
       ksl_b = (int)p.kr_sl * 2; vsl_b = (int)p.vr_sl * 2; slen = p.Lr; sntile = p.tiles_ref;
       if (RAGGED) { slen = seg_keys(s); sntile = (slen + KVB - 1) / KVB; }   // (never 0: the walk steps over an empty reference)
     }
-    krs = __builtin_amdgcn_make_buffer_rsrc((void*)sk, 0, (slen - 1) * ksl_b + 128, 0x00020000);
-    vrs = __builtin_amdgcn_make_buffer_rsrc((void*)sv, 0, (slen - 1) * vsl_b + 128, 0x00020000);
-    if (DMA_ASM) {
-      krw = make_rsrc_words(sk, (unsigned)((slen - 1) * ksl_b + 128));
-      vrw = make_rsrc_words(sv, (unsigned)((slen - 1) * vsl_b + 128));
-    }
+    krw = make_rsrc_words(sk, (unsigned)((slen - 1) * ksl_b + 128));
+    vrw = make_rsrc_words(sv, (unsigned)((slen - 1) * vsl_b + 128));
     kstep = KVB * ksl_b;
     vstep = KVB * vsl_b;
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
-      // register staging: thread fetches logical slot `slot` and writes it to the swizzled LDS
-      // position; LDS-DMA: the LDS position is lane-linear (physical slot = tid & 7), so the thread
-      // fetches the logical slot that belongs there (the XOR swizzles are involutions)
-      const int ks_ = DMA_FLAG ? (slot ^ ((srow[c] >> 1) & 7)) : slot;
-      const int vs_ = DMA_FLAG ? (slot ^ (((srow[c] >> 1) & 1) << 2)) : slot;
+      // the LDS position of a transfer is lane-linear (physical 16-byte slot = tid & 7), so the thread fetches the logical
+      // slot that belongs there under the tile's swizzle (K: slot ^ ((row >> 1) & 7), V: slot ^ (((row >> 1) & 1) << 2); the
+      // XORs are involutions)
+      const int ks_ = slot ^ ((srow[c] >> 1) & 7);
+      const int vs_ = slot ^ (((srow[c] >> 1) & 1) << 2);
       kvo[c] = (unsigned)(srow[c] * ksl_b + ks_ * 16);
       vvo[c] = (unsigned)(srow[c] * vsl_b + vs_ * 16);
     }
   };
-  u32x4 kreg[CH], vreg[CH];
   auto issue_dma = [&](int kslot, int vslot) {  // tile pair straight into its ring slots
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
-      if (DMA_ASM) {
-        buffer_load_lds16_async(krw, smem + K_OFF + kslot * TILE_BYTES + (c * NW + wid) * 1024, kvo[c]);
-        buffer_load_lds16_async(vrw, smem + V_OFF + vslot * TILE_BYTES + (c * NW + wid) * 1024, vvo[c]);
-      } else {
-        buffer_load_lds16(krs, smem + K_OFF + kslot * TILE_BYTES + (c * NW + wid) * 1024, kvo[c]);
-        buffer_load_lds16(vrs, smem + V_OFF + vslot * TILE_BYTES + (c * NW + wid) * 1024, vvo[c]);
-      }
+      buffer_load_lds16_async(krw, smem + K_OFF + kslot * TILE_BYTES + (c * NW + wid) * 1024, kvo[c]);
+      buffer_load_lds16_async(vrw, smem + V_OFF + vslot * TILE_BYTES + (c * NW + wid) * 1024, vvo[c]);
       kvo[c] += kstep;
       vvo[c] += vstep;
     }
   };
   int seg = 0, t0 = 0;
-  auto issue_loads = [&]() {
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      kreg[c] = __builtin_amdgcn_raw_buffer_load_b128(krs, kvo[c], 0, 0);
-      vreg[c] = __builtin_amdgcn_raw_buffer_load_b128(vrs, vvo[c], 0, 0);
-      kvo[c] += kstep;
-      vvo[c] += vstep;
-    }
-  };
-  auto stage_write = [&](int kslot, int vslot) {
-    unsigned char* Kb = smem + K_OFF + kslot * TILE_BYTES;
-    unsigned char* Vb = smem + V_OFF + vslot * TILE_BYTES;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      *(u32x4*)(Kb + koff[c]) = kreg[c];
-      *(u32x4*)(Vb + voff[c]) = vreg[c];
-    }
-  };
   auto advance = [&]() {
     if (++t0 == sntile) {
       t0 = 0;
@@ -288,7 +289,7 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
   float cum_last = -INFINITY;               // RAGGED + MASS: the cumulative value stored last - an absent reference repeats it
   bool started = false;                     // BIAS + PRESC: a tile with an unmasked key has set the reference (wave-uniform: the bias has no query axis)
   // BIAS: loaded bias -> exponent units of the scores as they leave the matrix pipe (PRESC: exp2 domain; else raw scores, scaled by c2 later)
-  const float kb_mul = (ABL & 2048) != 0 ? 1.4426950408889634f : 1.4426950408889634f / c2;
+  const float kb_mul = PRESC ? 1.4426950408889634f : 1.4426950408889634f / c2;
   f32x16 mneg;                              // PRESC: -m_run in every register: C operand of the first QK^T MFMA
 #pragma unroll
   for (int r = 0; r < 16; ++r) mneg[r] = 0.f;
@@ -321,14 +322,12 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
     c_ntile = (c_len + KVB - 1) / KVB;
   }
 
-  constexpr bool NOPIPE = (ABL & 256) != 0;  // no S double buffer: fewer VGPRs, three waves per SIMD (implies asm DMA)
-  constexpr bool DMA = (ABL & (64 | 128 | 256)) != 0;    // global->LDS staging by LDS-DMA (buffer_load ... lds), no registers (real variant)
   auto load_kf = [&](v8 (&kf0)[4], v8 (&kf1)[4], int kslot) {
     const unsigned char* Kb = smem + K_OFF + kslot * TILE_BYTES;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      kf0[ks] = (ABL & 16) ? qf[(ks + 1) & 3] : *(const IR_LDS v8*)(IR_LDS unsigned char*)(Kb + kread[ks]);
-      kf1[ks] = (ABL & 16) ? qf[(ks + 2) & 3] : *(const IR_LDS v8*)(IR_LDS unsigned char*)(Kb + 32 * 128 + kread[ks]);
+      kf0[ks] = *(const IR_LDS v8*)(IR_LDS unsigned char*)(Kb + kread[ks]);
+      kf1[ks] = *(const IR_LDS v8*)(IR_LDS unsigned char*)(Kb + 32 * 128 + kread[ks]);
     }
   };
   auto qk_mfma = [&](f32x16& s0, f32x16& s1, const v8 (&kf0)[4], const v8 (&kf1)[4]) {
@@ -443,23 +442,17 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
     // K ring slots: tile t lives in slot t & 1 (ring of 2) or in the V ring's slot (ring of 3: both rings turn together)
     const int v_next = vcur == 2 ? 0 : vcur + 1, v_prev = (vcur >= 1) ? vcur - 1 : 2;
     const int ks_cur = CHK ? vcur : (t & 1), ks_next = CHK ? v_next : ((t + 1) & 1), ks_free = CHK ? v_prev : (t & 1);
-    if (NOPIPE) {  // straight schedule: prefetch pair t+1, S(t) now
-      if (has1) {
-        issue_dma((t + 1) & 1, vcur == 2 ? 0 : vcur + 1);
-        advance();
-      }
-      qk(c0, c1, t & 1);
-      asm volatile("s_nop 7\n\ts_nop 4" : "+v"(c0), "+v"(c1));  // MFMA -> asm v_max3 hazard pad
-    }
+    // `step` captures by reference.  Its closure is laid out in the order in which the body first names what it captures, and
+    // hipcc's inlining bonus for a pointer to a stack object depends on that object's size: both reach the generated code (the
+    // scalar register allocation of the FOLD kernels, the schedule of the forms with counts).  The seven names here and at (6)
+    // hold the layout that the measured code was built with; profiles/pipe32_forms_refactor.txt, section 2, has the comparison
+    (void)issue_dma; (void)advance; (void)qk; (void)kvo;
     // EARLYQK: the prefetch issue and S(t+1) = K[t+1] Q^T go FIRST, so the row-max chain and the rescale
     // test of S(t) - 40-odd dependent VALU operations that used to run with the matrix pipe idle - execute
     // beside the eight QK^T MFMAs (S is double-buffered: n0/n1 are not the registers read below)
-    constexpr bool EARLYQK = (ABL & 4096) != 0 && !PRESC && !NOPIPE;
+    constexpr bool EARLYQK = F::early_qk && !PRESC;
     if (EARLYQK) {
-      if (has2) {
-        if (DMA) issue_dma(ks_free, v_prev);
-        else issue_loads();
-      }
+      if (has2) issue_dma(ks_free, v_prev);
       if (has1) qk(n0, n1, ks_next);
     }
     // (1) ragged tail of a segment: mask keys past its end (wave-uniform branch, rare)
@@ -511,9 +504,9 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
       }
     }
     const float m_new = max3(m_run, mx, mx);
-    // (3) rescale only when some row's max moved (exact).  LAZYMAX (experiment): keep the old
+    // (3) rescale only when some row's max moved (exact).  LAZYMAX: keep the old
     // reference while no row's max grew by more than 2^6 in the exp2 domain, so P <= 64.
-    constexpr bool LAZYMAX = (ABL & 1024) != 0;
+    constexpr bool LAZYMAX = F::lazy_max;
     if (PRESC) {   // (CHK: nothing here - the check comes after the exponentials)
     } else if (LAZYMAX ? __any(mx > m_run + lazy_thr) : __any(m_new != m_run)) {
       const float alpha = fast_exp2((m_run - m_new) * c2);
@@ -528,11 +521,8 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
     const float mc = (BIAS && !(m_sub > -INFINITY)) ? 0.f : m_sub * c2;
     // (4) the overlapped block: prefetch issue, S(t+1) on the matrix pipe, exp/pack on the VALU,
     //     PV(t) on the matrix pipe
-    if (!EARLYQK && !NOPIPE && has2 && !(ABL & 4)) {
-      if (DMA) issue_dma(ks_free, v_prev);  // K slot of tile t+2 (ring of 2: (t+2)&1; of 3: (vcur+2)%3), V slot (vcur+2)%3: free since the last barrier
-      else issue_loads();
-    }
-    if (!EARLYQK && !NOPIPE && has1) qk(n0, n1, ks_next);
+    if (!EARLYQK && has2) issue_dma(ks_free, v_prev);  // K slot of tile t+2 (ring of 2: (t+2)&1; of 3: (vcur+2)%3), V slot (vcur+2)%3: free since the last barrier
+    if (!EARLYQK && has1) qk(n0, n1, ks_next);
     const f32x2 cc = {c2, c2};
     const f32x2 nm = {-mc, -mc};
     f32x2 ta = {0.f, 0.f}, tb = {0.f, 0.f};   // CHK: this tile's own row sums (four 8-element partial sums per lane)
@@ -553,7 +543,7 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
         c1[r] = t1v[0]; c1[r + 1] = t1v[1];
       }
     };
-    if (!CHK && !(ABL & 8)) exps();
+    if (!CHK) exps();
     if (CHK) {
       // Reference checked AFTER the exponentials (the 64-row kernel's rule, shared_attn_fwd_w64.hip): the scores left the
       // matrix pipe as exponents relative to the running reference, so P = exp2(S) needs no row max; what must be caught
@@ -565,7 +555,7 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
       // and in the fp32 accumulators.
       bool redo = (t == 0);
       if (!redo) {
-        if (!(ABL & 8)) exps();
+        exps();
         const float worst = max3(fmaxf(ta[0], ta[1]), tb[0], tb[1]);
         redo = __any(!(worst <= 2048.f));
         if (redo) {
@@ -610,17 +600,12 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         const int off = (32 * kb + 16 * ks) * 128;
-        if (ABL & 16) {
-          o0 = Tr::mfma(qf[kb + ks], pk[kb][ks], o0);
-          o1 = Tr::mfma(qf[3 - kb - ks], pk[kb][ks], o1);
-        } else {
-          const s16x4 a00 = lds_read_tr16(Vb + vread[0] + off);
-          const s16x4 a01 = lds_read_tr16(Vb + vread[0] + off + 8 * 128);
-          const s16x4 a10 = lds_read_tr16(Vb + vread[1] + off);
-          const s16x4 a11 = lds_read_tr16(Vb + vread[1] + off + 8 * 128);
-          o0 = Tr::mfma(join_tr<v8>(a00, a01), pk[kb][ks], o0);
-          o1 = Tr::mfma(join_tr<v8>(a10, a11), pk[kb][ks], o1);
-        }
+        const s16x4 a00 = lds_read_tr16(Vb + vread[0] + off);
+        const s16x4 a01 = lds_read_tr16(Vb + vread[0] + off + 8 * 128);
+        const s16x4 a10 = lds_read_tr16(Vb + vread[1] + off);
+        const s16x4 a11 = lds_read_tr16(Vb + vread[1] + off + 8 * 128);
+        o0 = Tr::mfma(join_tr<v8>(a00, a01), pk[kb][ks], o0);
+        o1 = Tr::mfma(join_tr<v8>(a10, a11), pk[kb][ks], o1);
       }
     }
     // (5) segment boundary of this stream: fold the AdaIN affine into the LDS total
@@ -641,18 +626,11 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
         c_ntile = (c_len + KVB - 1) / KVB;
       }
     }
-    // (6) land pair t+2 in LDS
-    if (!NOPIPE && has2) {
-      if (DMA) {}
-      else if (!(ABL & 2)) stage_write(t & 1, (vcur >= 1) ? vcur - 1 : 2);  // K slot (t+2)&1, V slot (vcur+2)%3
-      else if (!(ABL & 4)) {
-#pragma unroll
-        for (int c = 0; c < CH; ++c) asm volatile("" ::"v"(kreg[c]), "v"(vreg[c]));  // keep the loads alive
-      }
-      advance();
-    }
-    if (DMA_ASM) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // our DMA of pair t+2 has landed
-    if (!(ABL & 1)) __syncthreads();
+    // (6) the prefetch stream moves on to pair t+3; pair t+2 lands in LDS
+    (void)vvo; (void)krw; (void)vrw;   // (closure layout: see the top of `step`)
+    if (has2) advance();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // our DMA of pair t+2 has landed
+    __syncthreads();
   };
 
   // ---- prologue: pairs 0 and 1 into LDS, S(0) ---------------------------------------------------
@@ -665,46 +643,29 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
   if (RAGGED && NTILES == 0) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) { sa0[r] = 0.f; sa1[r] = 0.f; sb0[r] = 0.f; sb1[r] = 0.f; }
-  } else if (DMA) {
+  } else {
     if (BIAS) bias_load(sa0, sa1);
     issue_dma(0, 0);
     advance();
-    if (!NOPIPE && NTILES > 1) {
+    if (NTILES > 1) {
       if (BIAS) bias_load(sb0, sb1);
       issue_dma(1, 1);
       advance();
     }
-    if (DMA_ASM) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  } else {
-    issue_loads();
-    stage_write(0, 0);
-    advance();
-    if (NTILES > 1) {
-      issue_loads();
-      stage_write(1, 1);
-      advance();
-    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) asm volatile("" ::"v"(qf[ks]));  // retire the Q loads before the loop
   __syncthreads();
 
-  if (!NOPIPE) {
-    qk(sa0, sa1, 0);
-    // S(0) is read by inline-asm v_max3 right away in the first step: pad the MFMA->VALU hazard
-    asm volatile("s_nop 7\n\ts_nop 4" : "+v"(sa0), "+v"(sa1));
-  }
+  qk(sa0, sa1, 0);
+  // S(0) is read by inline-asm v_max3 right away in the first step: pad the MFMA->VALU hazard
+  asm volatile("s_nop 7\n\ts_nop 4" : "+v"(sa0), "+v"(sa1));
 
   int t = 0, vcur = 0;  // vcur = V ring slot of tile t
   auto next3 = [](int v) { return v == 2 ? 0 : v + 1; };
   const std::integral_constant<bool, true> fast{};
   const std::integral_constant<bool, false> slow{};
-  if (NOPIPE) {
-    for (; t < NTILES; ++t) {
-      step(slow, t, sa0, sa1, sa0, sa1, vcur);
-      vcur = next3(vcur);
-    }
-  }
   for (; t + 3 < NTILES; t += 2) {  // steady state: both tiles of the pair have t+2 < NTILES
     step(fast, t, sa0, sa1, sb0, sb1, vcur);
     vcur = next3(vcur);
@@ -836,7 +797,7 @@ __global__ void __launch_bounds__(NW * 64, ((ABL & 256) && !FOLD) ? 3 : 2) share
     }
     return;
   }
-  constexpr bool NOKEY = BIAS || RAGGED;   // a row may have no key at all (BIAS: every key masked; RAGGED: no self block, every count 0)
+  constexpr bool NOKEY = kRowMayHaveNoKey<F>;
   const float inv = (NOKEY && !(l_fin > 0.f)) ? 0.f : 1.0f / l_fin;   // then exact zeros, lse = -inf
   if (qrow < p.Lq) {
     const int64_t ooff = (int64_t)b * p.o_sb + (int64_t)qrow * p.o_sl + (int64_t)h * p.o_sh;
@@ -928,122 +889,57 @@ int force_split() {
 }
 
 // (the work plan: ir_attn_plan.h)
-template <typename T, int NW, bool FOLD, int ABL = 0, bool MASS = false>
+template <typename T, typename F, bool FOLD, bool MASS = false>
 hipError_t launch(const AttnKParams& p0, hipStream_t s) {
   if (!MASS && p0.seg_cum != nullptr) return hipErrorInvalidValue;   // seg_mass: the two default forms carry the MASS instantiation
-  constexpr int QB = NW * 32;
-  const int slots_x = 32 * (NW == 8 ? 1 : (((ABL & 256) && !FOLD) ? 3 : 2));   // CUs per XCD x workgroups per CU
+  const int slots_x = 32 * 2;   // CUs per XCD x workgroups per CU (the kernel's launch bounds)
   const IrAttnPlan pl = ir_attn_plan(ir_attn_plan_in(p0, QB, slots_x, force_split()));
   AttnKParams p = p0;
   ir_attn_plan_apply(pl, p);
-  hipLaunchKernelGGL((shared_attn_fwd_pipe_kernel<T, NW, FOLD, ABL, MASS>), dim3(pl.grid), dim3(NW * 64), 0, s, p);
+  hipLaunchKernelGGL((shared_attn_fwd_pipe_kernel<T, F, FOLD, MASS>), dim3(pl.grid), dim3(NT), 0, s, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || pl.k <= 1) return e;
-  if ((ABL & (16384 | 32768)) != 0) {   // BIAS, RAGGED
+  if (kRowMayHaveNoKey<F>) {
     hipLaunchKernelGGL((shared_attn_combine_bias_kernel<T, QB>), dim3(kIrXcds * pl.rem, QB / 16), dim3(256), 0, s, p);
     return hipGetLastError();
   }
   return ir_launch_shared_attn_combine(p, std::is_same<T, __bf16>::value ? 1 : 0, QB, pl.rem, s);
 }
 
-// template arguments (ABL bits) of the forms, IrPipeForm of ir_kernels.h
-constexpr int kAsmDma = 128, kLazyMax = 1024, kPrescQ = 2048, kEarlyQK = 4096, kPostCheck = 8192;
-#ifdef IR_ABLATIONS
-constexpr int kDma = 64, kStraight3 = 256;   // builtin LDS-DMA staging; straight schedule at 3 waves/SIMD (0: register staging)
-#endif
-constexpr int kFormExact = kAsmDma;                                   // LDS-DMA from asm
-constexpr int kFormLazy = kAsmDma | kLazyMax;                         // asm DMA + lazy max
-constexpr int kFormPresc = kFormLazy | kPrescQ;                       // + pre-scaled Q, reference through the C operand
-constexpr int kFormEarlyQK = kFormLazy | kEarlyQK;                    // + QK^T of the next tile first
-constexpr int kFormPostCheck = kFormPresc | kPostCheck;               // PRESC + reference checked after the exponentials
-
-template <typename T, int ABL, bool MASS = false, int NW = 4>
+template <typename T, typename F, bool MASS = false>
 hipError_t launch_f(const AttnKParams& p, hipStream_t s) {
-  return p.aa != nullptr ? launch<T, NW, true, ABL, MASS>(p, s) : launch<T, NW, false, ABL, MASS>(p, s);
+  return p.aa != nullptr ? launch<T, F, true, MASS>(p, s) : launch<T, F, false, MASS>(p, s);
 }
 
-#ifdef IR_PIPE_BIAS_TU   // shared_attn_fwd_pipe_bias.hip: the BIAS instantiations and nothing else of this file
-constexpr int kBias = 16384;
-template <typename T>
-hipError_t launch_bias_t(const AttnKParams& p, IrPipeForm form, hipStream_t s) {
+// The one instantiation table: (IrPipeForm, seg_mass asked for?) -> form, under the extension EXT that this translation unit holds.
+// PRESC and EARLYQK - what the default dispatch takes - carry seg_mass and the extensions; the other forms neither.
+template <typename T, template <typename> class EXT>
+hipError_t launch_t(const AttnKParams& p, IrPipeForm form, hipStream_t s) {
   const bool mass = p.seg_cum != nullptr;
-  if (form == IR_PIPE_PRESC) return mass ? launch_f<T, kFormPresc | kBias, true>(p, s) : launch_f<T, kFormPresc | kBias>(p, s);
-  if (form == IR_PIPE_EARLYQK) return mass ? launch_f<T, kFormEarlyQK | kBias, true>(p, s) : launch_f<T, kFormEarlyQK | kBias>(p, s);
+  if (form == IR_PIPE_PRESC) return mass ? launch_f<T, EXT<FormPresc>, true>(p, s) : launch_f<T, EXT<FormPresc>>(p, s);
+  if (form == IR_PIPE_EARLYQK) return mass ? launch_f<T, EXT<FormEarlyQK>, true>(p, s) : launch_f<T, EXT<FormEarlyQK>>(p, s);
+  if constexpr (std::is_same<EXT<FormExact>, FormExact>::value) {
+    if (mass) return hipErrorInvalidValue;
+    if (form == IR_PIPE_EXACT) return launch_f<T, FormExact>(p, s);
+    if (form == IR_PIPE_LAZY) return launch_f<T, FormLazy>(p, s);
+    if (form == IR_PIPE_POSTCHECK) return launch_f<T, FormPostCheck>(p, s);
+  }
   return hipErrorInvalidValue;
 }
 
 }  // namespace
 
+#ifdef IR_PIPE_BIAS_TU   // shared_attn_fwd_pipe_bias.hip: the key-bias instantiations and nothing else of this file
 hipError_t ir_launch_shared_attn_fwd_pipe_bias(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s) {
   if (p.key_bias == nullptr || p.valid != nullptr) return hipErrorInvalidValue;
-  return dtype == 1 ? launch_bias_t<__bf16>(p, form, s) : launch_bias_t<_Float16>(p, form, s);
+  return dtype == 1 ? launch_t<__bf16, WithKeyBias>(p, form, s) : launch_t<_Float16, WithKeyBias>(p, form, s);
 }
-#elif defined(IR_PIPE_RAGGED_TU)   // shared_attn_fwd_pipe_ragged.hip: the RAGGED instantiations and nothing else of this file
-constexpr int kRagged = 32768;
-template <typename T>
-hipError_t launch_ragged_t(const AttnKParams& p, IrPipeForm form, hipStream_t s) {
-  const bool mass = p.seg_cum != nullptr;
-  if (form == IR_PIPE_PRESC) return mass ? launch_f<T, kFormPresc | kRagged, true>(p, s) : launch_f<T, kFormPresc | kRagged>(p, s);
-  if (form == IR_PIPE_EARLYQK) return mass ? launch_f<T, kFormEarlyQK | kRagged, true>(p, s) : launch_f<T, kFormEarlyQK | kRagged>(p, s);
-  return hipErrorInvalidValue;
-}
-
-}  // namespace
-
+#elif defined(IR_PIPE_RAGGED_TU)   // shared_attn_fwd_pipe_ragged.hip: the per-reference-count instantiations and nothing else of this file
 hipError_t ir_launch_shared_attn_fwd_pipe_ragged(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s) {
   if (p.ref_lens == nullptr || p.valid != nullptr || p.key_bias != nullptr || p.N <= 0) return hipErrorInvalidValue;
-  return dtype == 1 ? launch_ragged_t<__bf16>(p, form, s) : launch_ragged_t<_Float16>(p, form, s);
+  return dtype == 1 ? launch_t<__bf16, WithRefCounts>(p, form, s) : launch_t<_Float16, WithRefCounts>(p, form, s);
 }
 #else
-template <typename T>
-hipError_t launch_t(const AttnKParams& p, IrPipeForm form, hipStream_t s) {
-  if (p.seg_cum != nullptr) {   // ABI v9 seg_mass: the two forms the default dispatch takes
-    if (form == IR_PIPE_PRESC) return launch_f<T, kFormPresc, true>(p, s);
-    if (form == IR_PIPE_EARLYQK) return launch_f<T, kFormEarlyQK, true>(p, s);
-    return hipErrorInvalidValue;
-  }
-  switch (form) {
-#ifdef IR_ABLATIONS
-    case IR_PIPE_DEV_REG8: return launch_f<T, 0, false, 8>(p, s);
-    case IR_PIPE_DEV_DMA: return launch_f<T, kDma>(p, s);
-    case IR_PIPE_DEV_STRAIGHT3: return launch_f<T, kStraight3>(p, s);
-    case IR_PIPE_DEV_REG4: return launch_f<T, 0>(p, s);
-#endif
-    case IR_PIPE_EXACT: return launch_f<T, kFormExact>(p, s);
-    case IR_PIPE_LAZY: return launch_f<T, kFormLazy>(p, s);
-    case IR_PIPE_PRESC: return launch_f<T, kFormPresc>(p, s);
-    case IR_PIPE_EARLYQK: return launch_f<T, kFormEarlyQK>(p, s);
-    case IR_PIPE_POSTCHECK: return launch_f<T, kFormPostCheck>(p, s);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-}  // namespace
-
-// Ablation builds (timing experiments, WRONG results) exist only with -DIR_ABLATIONS
-// (`build.sh -DIR_ABLATIONS`, used by tools/gpu_ablate.py); the shipped library has none.
-hipError_t ir_launch_shared_attn_fwd_pipe_abl(const AttnKParams& p, int abl, hipStream_t s) {
-#ifndef IR_ABLATIONS
-  (void)abl;
-  return launch<__bf16, 4, false, 0>(p, s);
-#else
-  switch (abl) {
-    case 1: return launch<__bf16, 4, false, 1>(p, s);
-    case 2: return launch<__bf16, 4, false, 2>(p, s);
-    case 3: return launch<__bf16, 4, false, 3>(p, s);
-    case 4: return launch<__bf16, 4, false, 4>(p, s);
-    case 6: return launch<__bf16, 4, false, 6>(p, s);
-    case 7: return launch<__bf16, 4, false, 7>(p, s);
-    case 8: return launch<__bf16, 4, false, 8>(p, s);
-    case 15: return launch<__bf16, 4, false, 15>(p, s);
-    case 16: return launch<__bf16, 4, false, 16>(p, s);
-    case 23: return launch<__bf16, 4, false, 23>(p, s);
-    case 31: return launch<__bf16, 4, false, 31>(p, s);
-    default: return launch<__bf16, 4, false, 0>(p, s);
-  }
-#endif
-}
-
 // the combine of every kernel family (p must carry the final sk_* / ws_* fields)
 template <typename T, int QB>
 static hipError_t combine(const AttnKParams& p, int rem, hipStream_t s) {
@@ -1061,6 +957,6 @@ hipError_t ir_launch_shared_attn_combine(const AttnKParams& p, int dtype, int qb
 }
 
 hipError_t ir_launch_shared_attn_fwd_pipe(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s) {
-  return dtype == 1 ? launch_t<__bf16>(p, form, s) : launch_t<_Float16>(p, form, s);
+  return dtype == 1 ? launch_t<__bf16, NoExtension>(p, form, s) : launch_t<_Float16, NoExtension>(p, form, s);
 }
 #endif  // IR_PIPE_BIAS_TU / IR_PIPE_RAGGED_TU

@@ -1,4 +1,4 @@
-// shared_attn_fwd_pipe_bias.hip - the key-bias instantiations of the software-pipelined 32-row kernel (BIAS = true, the PRESC and
+// shared_attn_fwd_pipe_bias.hip - the key-bias instantiations of the software-pipelined 32-row kernel (WithKeyBias of the PRESC and
 // EARLYQK forms x fold x seg_mass; shared_attn_fwd_pipe.hip has the kernel and says what the form does) and the combine of their
 // K/V-range pieces.  An object of their own: the instantiations of shared_attn_fwd_pipe.o stay the ones they were, compiled from
 // the code they were compiled from.

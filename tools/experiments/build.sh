@@ -1,8 +1,8 @@
 #!/usr/bin/env bash
 # Development build of the library: the PRODUCT sources of instantrestore_amd/csrc compiled with -DIR_ABLATIONS - nothing
 # else.  That switch turns on, inside those same files,
-#   shared_attn_fwd.hip        tuning values 1-4, 6, 9 (round 1's straight-line / register-staged kernels) and the `>> 5`
-#                              timing-ablation bits of the 32-row kernels (tools/gpu_ablate.py)
+#   shared_attn_fwd.hip        tuning values 1 and 2 (round 1's straight-line kernel) and its `>> 5` timing-ablation bits
+#                              (tools/gpu_ablate.py)
 #   shared_attn_fwd_w64.hip    tuning values 20-28: the ENERGY / timing ablations of the 64-row QS kernel (template parameter
 #                              ABL: no DMA, no barrier, Q fragments read once, no exponentials, no row sums, no conversions;
 #                              tools/gpu_energy_probe.py, profiles/r5_energy_budget.txt)
