@@ -54,6 +54,10 @@ def main(argv=None):
     ap.add_argument("--matches", action="store_true",
                     help="one more frame that leaves the best-matching token of every reference behind for every query token "
                          "(attention_match): prints, per shared layer, the mean best probability per reference and where the best matches lie")
+    ap.add_argument("--transfer", action="store_true",
+                    help="one more frame that leaves the attention-weighted mean position inside every reference behind for every query "
+                         "token (attention_transfer with the coordinate payload): prints, per shared layer and reference, the mean soft "
+                         "displacement, the mean mass and how often the rounded expected position is attention_match's hard match")
     ap.add_argument("--ref-weights", default=None,
                     help="comma-separated weight per reference, e.g. 1,1,0.25,0 (0 masks a reference): prints the top shared layer's "
                          "per-reference attention masses with and without")
@@ -255,6 +259,35 @@ def main(argv=None):
                       f"share of tokens whose best match lies in each reference {fmt(share)}")
                 assert int(ri.min()) >= 0 and int(ri.max()) < tokens and int(y.max()) < side_len and 0 <= int(xq.min()) and int(xq.max()) < side_len
                 assert float(prob.min()) > 0 and float(prob.sum(-1).max()) <= 1.0 + 8e-3 and abs(float(share.sum()) - 1) < 1e-5
+        # Where in each reference does every token of the degraded face look, to a fraction of a token?  The payload holds the
+        # (y, x) of every key; each shared layer leaves (sums, mass) of the head-mean attention behind - fp32 (B, L, [self?] + N, 2)
+        # and (B, L, [self?] + N) - and soft_match_field divides: the expected position inside every segment, its displacement
+        # from the token's own place and the segment's mass as the confidence.  attention_match of the same frame is the hard form.
+        if args.transfer:
+            from instantrestore_amd.attn_maps import coordinate_payload, match_coordinates, soft_match_field
+            shared = sorted((p for p in unet.attn_processors.values() if getattr(p, "self_attn_idx", None) is not None),
+                            key=lambda p: p.self_attn_idx)
+            for p in shared:
+                tokens = ck[p.self_attn_idx].shape[2]
+                p.attention_transfer_payload = coordinate_payload(tokens, N, tokens, bool(p.train_input), device=dev)
+                p.attention_match_index = "all"
+            unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1),
+                 cross_attention_kwargs={"ref_keys": ck, "ref_values": cv, "ref_stats": cs})
+            fmt = lambda m: " ".join(f"{v:.4f}" for v in m.tolist())
+            for p in shared:
+                (sums, mass), p.attention_transfer_payload = p.attention_transfer, None
+                (index, _), p.attention_match_index = p.attention_match, None
+                first = int(p.train_input)                                       # column of reference 0
+                side_len = int(round(ck[p.self_attn_idx].shape[2] ** 0.5))
+                pos, disp, conf = soft_match_field(sums, mass, "all", side_len)
+                pos, disp, conf = pos[:, :, first:], disp[:, :, first:], conf[:, :, first:]      # (B, L, N, 2), (B, L, N)
+                hy, hx = match_coordinates(index[..., first:], side_len)
+                agree = ((pos[..., 0].round().long() == hy) & (pos[..., 1].round().long() == hx)).float().mean(dim=(0, 1))
+                print(f"shared layer {p.self_attn_idx}: transfer {tuple(sums.shape)}; mean soft displacement per reference "
+                      f"{fmt(disp.norm(dim=-1).mean(dim=(0, 1)))}; mean mass per reference {fmt(conf.mean(dim=(0, 1)))}; "
+                      f"share of tokens whose rounded expected position is the hard match {fmt(agree)}")
+                assert float(pos.min()) >= 0 and float(pos.max()) <= side_len - 1 + 1e-3 and float(mass.min()) > 0
+                assert float((mass.sum(-1) - 1).abs().max()) < 8e-3
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     assert out_u8.shape == (B, S, S, 3) and out_u8.dtype == torch.uint8

@@ -412,6 +412,53 @@ int ir_attn_match(const ir_shared_attn_args* args, const int32_t* row_index, int
                   void* stream);
 
 /*
+ * ir_attn_transfer (opt-in) - attention-weighted sums of a per-key payload for a caller-chosen set of query tokens, per K/V
+ * segment, without the probability matrix.
+ *
+ * Replaces `einsum('bhij,bjc->bhic', attention_probs[..., segment], y[:, segment])` per segment s of the column order above
+ * ([self (iff INCLUDE_SELF)] ++ ref 0 ++ ... ++ ref N-1, S = include_self + N): the soft form of ir_attn_match.  With y = the
+ * (y, x) of every key it is the expected position inside each reference at sub-token precision (soft-argmax correspondences,
+ * the segment mass as confidence); with y = the reference pixels pooled to the token grid, the attention-warped reference;
+ * with y = a parsing map or landmark heat map, label transfer - at resolutions where the dump cannot be formed.  Same args as
+ * ir_attn_rows / ir_attn_match (q, the K pointers or the K table, lse; v_*, adain_*, out, valid_refs, seg_mass and workspace are
+ * ignored - every reference is walked - and `tuning` must be 0; IR_FLAG_Q_PRESCALED and IR_FLAG_BATCH_INVARIANT: same rules) plus
+ *   payload    fp32 on the device, 4-byte aligned, over the PACKED extended key axis (the axis of key_bias):
+ *              y[b, j, c] = payload[b * pay_sb + j * pay_sj + c], strides in floats, every offset formed in 64 bits.
+ *              pay_sb >= 0 (0: one payload for every batch entry), pay_sj >= channels; nothing outside the `channels` floats of
+ *              a key is read.  Read by the kernel when it runs: a replayed hipGraph follows in-place updates of it (and of
+ *              row_index and the pointer tables).
+ *   channels   1 ... IR_TRANSFER_MAX_CHANNELS (call again for more)
+ *   row_index, n_rows   exactly as for ir_attn_match
+ *   reduce     IR_TRANSFER_PER_HEAD   sums fp32 (B, H, n_rows, S, channels), mass fp32 (B, H, n_rows, S)
+ *              IR_TRANSFER_HEAD_MEAN  sums fp32 (B, n_rows, S, channels), mass fp32 (B, n_rows, S)
+ *   sums       contiguous, 4-byte aligned: sums[.., s, c] = sum over the keys j of segment s of p_j * y[b, j, c], UNNORMALISED, with
+ *              the fp32 p = exp2(fma(<q[idx[b,r]], k_j>, scale*log2(e), -lse[b,h,idx[b,r]]*log2(e))) of ir_attn_probs / ir_attn_rows
+ *   mass       contiguous, 4-byte aligned, or NULL (not written): mass[.., s] = sum of p_j over the segment.  sums / mass is the
+ *              expectation inside a segment, sums summed over s the expectation over all keys.
+ * Bit for bit (part of the interface):
+ *   - the mass and every channel of a (row, segment, head) are accumulated over the same keys in the same order, one fp32 fused
+ *     multiply-add per term with the payload value as multiplicand (the mass: multiplicand 1).  A channel that is 1.0f on every key
+ *     equals the mass; a channel that is 1 at a single key and 0 elsewhere equals that key's fp32 p - the value ir_attn_rows
+ *     rounds to `dtype` - and is exactly 0 in every other segment;
+ *   - IR_TRANSFER_HEAD_MEAN == ((S_0 + S_1) + ... + S_{H-1}) * (1.0f / (float)H) of the IR_TRANSFER_PER_HEAD outputs S_h, sums and
+ *     mass alike; with a one-hot channel that is the element of ir_attn_rows' IR_ROWS_HEAD_MEAN row;
+ *   - an index outside [0, len_q) gives sums 0 and mass 0 and is never used as an address.
+ * Bound: K read once per group of 96 rows (ceil(n_rows / 96) * B * H * Lkv * 128 bytes) and the payload once per work item
+ * (Lkv * channels * 4 bytes per row group, head and batch entry); channels + 1 numbers per (row, segment) written; no workspace,
+ * no atomics, one launch; asynchronous and capturable.  One wave walks a whole segment for up to 96 rows, so every output element
+ * has one writer and one order; the cut follows len_self, len_ref, n_refs, n_rows, channels and reduce only: the call is batch
+ * invariant with or without IR_FLAG_BATCH_INVARIANT.  Any segment length.
+ * Refused: a key_bias or ref_lens block (IR_ERR_UNSUPPORTED, as for the other read-outs), tuning != 0; IR_ERR_INVALID_ARG: NULL
+ * payload / row_index / sums / lse, n_rows outside 1 ... len_q, pay_sb < 0, pay_sj < channels; IR_ERR_UNSUPPORTED: channels
+ * outside its range, a misaligned payload / row_index / sums / mass, another reduce, more than 2^31 - 4 work items.
+ */
+#define IR_TRANSFER_PER_HEAD 0
+#define IR_TRANSFER_HEAD_MEAN 1
+#define IR_TRANSFER_MAX_CHANNELS 8
+int ir_attn_transfer(const ir_shared_attn_args* args, const float* payload, int64_t pay_sb, int64_t pay_sj, int32_t channels,
+                     const int32_t* row_index, int32_t n_rows, int32_t reduce, float* sums, float* mass, void* stream);
+
+/*
  * ir_adain_stats - per-(b, n, channel) AdaIN affine from token statistics.
  *
  * Replaces the statistics half of adain() (attn_processors.py:9-10) and of its call site

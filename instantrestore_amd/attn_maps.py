@@ -4,7 +4,9 @@ landmarks fall on, and the heat-map picture of a summed row.
 The reference does both inside ``get_visualization_image`` (face_replace/training/utils/vis_utils.py:97-108) on the head
 mean of the whole ``attention_probs``; here the index list goes IN (``attention_rows_index``) and only the chosen rows are
 ever computed.  ``match_coordinates`` / ``match_field`` turn the key indices of ``ops.attn_match`` /
-``SharedAttnProcessor.attention_match`` into grid coordinates and displacements."""
+``SharedAttnProcessor.attention_match`` into grid coordinates and displacements.  ``coordinate_payload`` / ``image_payload`` build
+the per-key payloads of ``ops.attn_transfer`` / ``SharedAttnProcessor.attention_transfer_payload`` and ``soft_match_field`` reads
+its sums back as expected positions: the soft form of ``match_field``."""
 import numpy as np
 
 
@@ -78,3 +80,82 @@ def match_field(index, rows, side: int):
         import torch
         return torch.where(bad, zero, y - qy), torch.where(bad, zero, x - qx)
     return np.where(bad, zero, y - qy), np.where(bad, zero, x - qx)
+
+
+def _square_side(length: int, what: str) -> int:
+    side = int(round(int(length) ** 0.5))
+    if side * side != int(length):
+        raise ValueError(f"{what} = {length} is not a square token grid")
+    return side
+
+
+def coordinate_payload(len_self: int, n_refs: int, len_ref: int, include_self: bool, device=None):
+    """fp32 ``(1, Lkv, 2)``: the ``(y, x)`` of every key of ``[self (iff include_self)] ++ ref 0 ++ ... ++ ref N-1`` on its OWN
+    segment's square grid, row-major - the convention of :func:`match_coordinates`.  As the payload of ``ops.attn_transfer`` it
+    gives, per segment, ``sum_j p_j * (y_j, x_j)``: divided by the mass, the expected position inside the segment
+    (:func:`soft_match_field`).  One payload serves every batch entry.  A length that is no square: ``ValueError``."""
+    import torch
+    parts = []
+    for length, what, count in ((len_self, "len_self", 1 if include_self else 0), (len_ref, "len_ref", int(n_refs))):
+        if count == 0:
+            continue
+        side = _square_side(length, what)
+        idx = torch.arange(int(length), device=device)
+        yx = torch.stack([torch.div(idx, side, rounding_mode="floor"), idx % side], dim=-1).to(torch.float32)
+        parts += [yx] * count
+    if not parts:
+        raise ValueError("empty key axis: include_self is False and n_refs is 0")
+    return torch.cat(parts, dim=0).unsqueeze(0)
+
+
+def image_payload(self_image, ref_images, len_self: int, len_ref: int, include_self: bool):
+    """fp32 ``(B, Lkv, Cimg)``: pictures laid on the key axis, one token per grid cell.  ``self_image`` ``(B, Cimg, Hp, Wp)`` (ignored
+    unless ``include_self``; may then be ``None`` only without it) and ``ref_images`` ``(B, N, Cimg, Hp, Wp)`` (or ``None``: no
+    references) are pooled by area to the ``side x side`` token grids of their segments (``side = sqrt(len)``; adaptive average
+    pooling, as ``ops.key_bias`` pools a keep map) and flattened row-major.  As the payload of ``ops.attn_transfer`` the sums
+    over the reference segments are the attention-warped reference picture.  ``Cimg <= 8`` per call."""
+    import torch
+    pool = torch.nn.functional.adaptive_avg_pool2d
+    parts = []
+    if include_self:
+        if self_image is None or self_image.dim() != 4:
+            raise ValueError("image_payload: include_self needs self_image (B, Cimg, Hp, Wp)")
+        side = _square_side(len_self, "len_self")
+        parts.append(pool(self_image.to(torch.float32), side).flatten(2).transpose(1, 2))                    # (B, len_self, Cimg)
+    if ref_images is not None:
+        if ref_images.dim() != 5:
+            raise ValueError(f"image_payload: ref_images must be (B, N, Cimg, Hp, Wp), got {tuple(ref_images.shape)}")
+        B, N, Ci = ref_images.shape[:3]
+        side = _square_side(len_ref, "len_ref")
+        r = pool(ref_images.to(torch.float32).flatten(0, 1), side).reshape(B, N, Ci, side * side)
+        parts.append(r.permute(0, 1, 3, 2).reshape(B, N * side * side, Ci))                                      # (B, N * len_ref, Cimg)
+    if not parts:
+        raise ValueError("empty key axis: include_self is False and ref_images is None")
+    if len(parts) == 2 and (parts[0].shape[0] != parts[1].shape[0] or parts[0].shape[2] != parts[1].shape[2]):
+        raise ValueError(f"image_payload: self_image and ref_images disagree on batch or channels: {tuple(self_image.shape)} vs {tuple(ref_images.shape)}")
+    return torch.cat(parts, dim=1).contiguous()
+
+
+def soft_match_field(sums, mass, rows, side: int):
+    """``(sums, mass)`` of ``ops.attn_transfer`` with :func:`coordinate_payload` - ``sums`` ``(..., R, S, 2)``, ``mass`` ``(..., R, S)``,
+    torch tensors - -> ``(pos, disp, conf)``: the expected ``(y, x)`` of every (row, segment), ``sums / mass``, fp32
+    ``(..., R, S, 2)``; its displacement from the query token's own place on the ``side x side`` grid; and the mass as the
+    confidence.  ``rows``: the query tokens the call was given - ``(R,)``, ``(B, R)`` or ``None`` / ``"all"`` for ``arange(R)``.  Where
+    the mass is 0 or the row is out of range, position and displacement are 0.  With a one-hot distribution ``pos`` is the key
+    of :func:`match_coordinates` and ``disp`` the field of :func:`match_field`."""
+    import torch
+    R = sums.shape[-3]
+    if rows is None or isinstance(rows, str):
+        rows = torch.arange(R, device=sums.device)
+    else:
+        rows = torch.as_tensor(rows).to(sums.device)
+    qy, qx = _divmod_side(rows, side)
+    if qy.ndim == 2 and sums.ndim == 5:          # (B, R) against (B, H, R, S, 2)
+        qy, qx = qy[:, None], qx[:, None]
+    own = torch.stack([qy, qx], dim=-1)[..., None, :]                       # (..., R, 1, 2): over the segments
+    m = mass.unsqueeze(-1)
+    ok = (m > 0) & (own[..., :1] >= 0)
+    zero = torch.zeros_like(sums)
+    pos = torch.where(ok, sums / torch.where(m > 0, m, torch.ones_like(m)), zero)
+    disp = torch.where(ok, pos - own.to(sums.dtype), zero)
+    return pos, disp, mass

@@ -542,6 +542,18 @@ class SharedAttnProcessor(nn.Module):
         self.attention_match_index = None
         self.attention_match_reduce = "head_mean"
         self.attention_match = None
+        # opt-in (plain attributes like ``attention_match_index``): ``attention_transfer_payload`` - an fp32 device tensor ``(Lkv, C)``,
+        # ``(1, Lkv, C)`` or ``(B, Lkv, C)`` over the key axis, C <= 8 (``attn_maps.coordinate_payload`` / ``image_payload``) - makes every
+        # call of a shared layer leave ``attention_transfer = (sums, mass)``: per K/V segment the attention-weighted sum of the payload
+        # and the segment's mass (``ir_attn_transfer``) - ``einsum('bhij,bjc->bhic')`` over a segment's columns of ``attention_probs``
+        # without the (B, H, L, Lkv) tensor.  ``attention_transfer_index``: ``None`` / ``"all"`` (every query token) or an integer tensor
+        # ``(R,)`` / ``(B, R)``.  ``attention_transfer_reduce``: "head_mean" - fp32 (B, R, S, C) / (B, R, S); "none" - (B, H, R, S, C) /
+        # (B, H, R, S).  ``attn_maps.soft_match_field`` turns the sums of a coordinate payload into expected positions.  Uses the LSE of
+        # the same attention call.  ``None`` payload: off, nothing changes.
+        self.attention_transfer_payload = None
+        self.attention_transfer_index = None
+        self.attention_transfer_reduce = "head_mean"
+        self.attention_transfer = None
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                 ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None, ref_weights=None, ref_token_keep=None,
@@ -609,6 +621,9 @@ class SharedAttnProcessor(nn.Module):
                 if getattr(self, "attention_match_index", None) is not None:
                     raise NotImplementedError("ref_lens together with attention_match_index: ir_attn_match would walk the tails behind the "
                                               "counts (follow-up)")
+                if getattr(self, "attention_transfer_payload", None) is not None:
+                    raise NotImplementedError("ref_lens together with attention_transfer_payload: ir_attn_transfer would walk the tails "
+                                              "behind the counts (follow-up)")
                 if self.use_adain and cstats is None:
                     raise ValueError("ref_lens with use_adain needs ref_stats: the AdaIN content statistics are those of the full reference, "
                                      "taken before compaction - computing them here would read the packed rows and whatever lies behind them")
@@ -654,7 +669,8 @@ class SharedAttnProcessor(nn.Module):
         want_mass = bool(getattr(self, "save_attention_mass", False))
         rows_index = getattr(self, "attention_rows_index", None) if shared else None
         match_index = getattr(self, "attention_match_index", None) if shared else None
-        want_lse = want_probs or rows_index is not None or match_index is not None
+        transfer_payload = getattr(self, "attention_transfer_payload", None) if shared else None
+        want_lse = want_probs or rows_index is not None or match_index is not None or transfer_payload is not None
         kw = {"q_prescaled": True} if presc else {}
         kw.update(_bi_kw(bi))
         if shared and ref_valid is not None:
@@ -676,6 +692,9 @@ class SharedAttnProcessor(nn.Module):
             if match_index is not None:
                 raise NotImplementedError("attention_match_index together with an attention mask, ref_weights or ref_token_keep: "
                                           "ir_attn_match does not take the key bias yet (follow-up)")
+            if transfer_payload is not None:
+                raise NotImplementedError("attention_transfer_payload together with an attention mask, ref_weights or ref_token_keep: "
+                                          "ir_attn_transfer does not take the key bias yet (follow-up)")
             kw["key_bias"] = bias
         # the masses are a by-product of the attention launch itself (ABI v9 ``seg_mass``: the kernels hold the row sums at every
         # segment boundary): no second pass over Q and K
@@ -701,6 +720,16 @@ class SharedAttnProcessor(nn.Module):
                                                    heads=attn.heads, scale=0.6931471805599453 if presc else attn.scale,
                                                    include_self=include_self,
                                                    reduce=getattr(self, "attention_match_reduce", "head_mean"), **_bi_kw(bi))
+        if transfer_payload is not None:
+            # the attention-weighted sums of the payload per segment for the chosen tokens (None / "all": every token), same LSE
+            transfer_index = getattr(self, "attention_transfer_index", None)
+            if isinstance(transfer_index, str) and transfer_index != "all":
+                raise ValueError(f"attention_transfer_index must be None, \"all\" or an integer tensor, got {transfer_index!r}")
+            self.attention_transfer = _ops.attn_transfer(query, key, ref_k, lse, transfer_payload,
+                                                         None if isinstance(transfer_index, str) else transfer_index,
+                                                         heads=attn.heads, scale=0.6931471805599453 if presc else attn.scale,
+                                                         include_self=include_self,
+                                                         reduce=getattr(self, "attention_transfer_reduce", "head_mean"), **_bi_kw(bi))
         if want_probs:
             # (B, H, L, Lkv), columns [self?] ++ ref0 ++ ... ++ refN-1, in the compute dtype.  A pre-scaled query
             # already carries scale * log2(e): its scores are exponents, ln 2 turns them into the logits of the LSE

@@ -35,7 +35,7 @@ int64_t seg_stride_limit(int32_t len, int64_t sl) {
 }
 
 // `fwd`: the call is (or describes) a launch of the attention forward, whose segment-span limit applies; the read-out entry points
-// (ir_attn_probs*, ir_attn_segment_mass, ir_attn_rows, ir_attn_match) address K through 64-bit pointers and take any stride
+// (ir_attn_probs*, ir_attn_segment_mass, ir_attn_rows, ir_attn_match, ir_attn_transfer) address K through 64-bit pointers and take any stride
 bool attn_block_size_ok(uint32_t n) {
   return n == sizeof(ir_shared_attn_args) || n == sizeof(ir_shared_attn_table_args) || n == sizeof(ir_shared_attn_bias_args) ||
          n == sizeof(ir_shared_attn_ragged_args);
@@ -86,7 +86,7 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
   if (a->seg_mass != nullptr && (reinterpret_cast<uintptr_t>(a->seg_mass) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "seg_mass must be 4-byte aligned");
   if (kbias != nullptr) {
     if (!fwd)
-      return fail(IR_ERR_UNSUPPORTED, "key_bias: ir_attn_probs[_ex], ir_attn_segment_mass, ir_attn_rows and ir_attn_match do not take a key bias yet (their exp(s - lse) would "
+      return fail(IR_ERR_UNSUPPORTED, "key_bias: ir_attn_probs[_ex], ir_attn_segment_mass, ir_attn_rows, ir_attn_match and ir_attn_transfer do not take a key bias yet (their exp(s - lse) would "
                   "leave it out); the forward's seg_mass by-product does");
     if ((reinterpret_cast<uintptr_t>(kbias) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "key_bias must be 4-byte aligned");
     if (ba->kb_sb < 0 || ba->kb_sh < 0) return fail(IR_ERR_INVALID_ARG, "key_bias strides kb_sb %lld, kb_sh %lld must be >= 0", (long long)ba->kb_sb, (long long)ba->kb_sh);
@@ -99,7 +99,7 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
   }
   if (rlens != nullptr) {
     if (!fwd)
-      return fail(IR_ERR_UNSUPPORTED, "ref_lens: ir_attn_probs[_ex], ir_attn_segment_mass, ir_attn_rows and ir_attn_match do not take per-reference counts yet (they would "
+      return fail(IR_ERR_UNSUPPORTED, "ref_lens: ir_attn_probs[_ex], ir_attn_segment_mass, ir_attn_rows, ir_attn_match and ir_attn_transfer do not take per-reference counts yet (they would "
                   "walk the tails behind the counts); the forward's seg_mass by-product does");
     if ((reinterpret_cast<uintptr_t>(rlens) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "ref_lens must be 4-byte aligned");
     if (a->n_refs == 0) return fail(IR_ERR_UNSUPPORTED, "ref_lens with n_refs == 0: there is no reference to count");
@@ -238,7 +238,8 @@ int launch_fwd(const ir_shared_attn_args* a, const AttnKParams& p, hipStream_t s
   return IR_OK;
 }
 
-// The parameter block of a read-out of the forward's LSE (ir_attn_probs_ex, ir_attn_segment_mass, ir_attn_rows, ir_attn_match).
+// The parameter block of a read-out of the forward's LSE (ir_attn_probs_ex, ir_attn_segment_mass, ir_attn_rows, ir_attn_match,
+// ir_attn_transfer).
 // `single_kernel`: the name of an entry point that has one kernel and refuses a tuning value, or nullptr.  A key bias and
 // per-reference counts are refused for the whole family in build_attn_params (!fwd)
 int build_readout_params(const ir_shared_attn_args* args, AttnKParams* p, const char* single_kernel) {
@@ -253,7 +254,7 @@ int build_readout_params(const ir_shared_attn_args* args, AttnKParams* p, const 
   return IR_OK;
 }
 
-// What ir_attn_rows and ir_attn_match check of their own arguments, in the order both make the checks: every NULL, n_rows, the
+// What ir_attn_rows, ir_attn_match and ir_attn_transfer check of their own arguments, in the order all of them make the checks: every NULL, n_rows, the
 // form (0 .. n_forms - 1, `forms` names them), every alignment
 struct OutArg { const char* name; const void* ptr; unsigned align; };
 template <size_t N>
@@ -472,6 +473,25 @@ int ir_attn_match(const ir_shared_attn_args* args, const int32_t* row_index, int
   if (ir_attn_match_items(p, n_rows, reduce) > kMatchMaxItems) return fail(IR_ERR_UNSUPPORTED, "grid too large");
   const hipError_t e = ir_launch_attn_match(p, args->dtype, row_index, n_rows, reduce, index, prob, (hipStream_t)stream);
   if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "attn_match launch: %s", hipGetErrorString(e));
+  return IR_OK;
+}
+
+int ir_attn_transfer(const ir_shared_attn_args* args, const float* payload, int64_t pay_sb, int64_t pay_sj, int32_t channels,
+                     const int32_t* row_index, int32_t n_rows, int32_t reduce, float* sums, float* mass, void* stream) {
+  AttnKParams p;
+  int rc = build_readout_params(args, &p, "ir_attn_transfer");
+  if (rc != IR_OK) return rc;
+  const OutArg outs[] = {{"payload", payload, 4}, {"sums", sums, 4}};
+  rc = check_row_readout(args, row_index, n_rows, reduce, 2, "IR_TRANSFER_PER_HEAD (0) or IR_TRANSFER_HEAD_MEAN (1)", outs);
+  if (rc != IR_OK) return rc;
+  if (mass != nullptr && (reinterpret_cast<uintptr_t>(mass) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "mass must be 4-byte aligned");
+  if (channels < 1 || channels > IR_TRANSFER_MAX_CHANNELS)
+    return fail(IR_ERR_UNSUPPORTED, "channels %d outside [1, IR_TRANSFER_MAX_CHANNELS = %d] (call again for more)", channels, IR_TRANSFER_MAX_CHANNELS);
+  if (pay_sb < 0) return fail(IR_ERR_INVALID_ARG, "pay_sb %lld must be >= 0 (0: one payload for every batch entry)", (long long)pay_sb);
+  if (pay_sj < channels) return fail(IR_ERR_INVALID_ARG, "pay_sj %lld must be >= channels %d", (long long)pay_sj, channels);
+  if (ir_attn_transfer_items(p, n_rows, reduce) > kTransferMaxItems) return fail(IR_ERR_UNSUPPORTED, "grid too large");
+  const hipError_t e = ir_launch_attn_transfer(p, args->dtype, payload, pay_sb, pay_sj, channels, row_index, n_rows, reduce, sums, mass, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "attn_transfer launch: %s", hipGetErrorString(e));
   return IR_OK;
 }
 

@@ -218,6 +218,16 @@ constexpr int64_t kMatchMaxItems = 0x7fffffffLL - 3;
 int64_t ir_attn_match_items(const AttnKParams& p, int n_rows, int reduce);
 hipError_t ir_launch_attn_match(const AttnKParams& p, int dtype, const int32_t* row_index, int n_rows, int reduce, int32_t* index, float* prob,
                                 hipStream_t s);
+// attn_transfer.hip: per K/V segment, the attention-weighted sums of a per-key fp32 payload (`channels` floats per key of the packed
+// extended key axis, batch / key strides pay_sb / pay_sj in floats) and the segment's mass for `n_rows` chosen query tokens
+// (sums fp32 (B, H, n_rows, S, channels) / (B, n_rows, S, channels), mass fp32 without the last axis, or nullptr); `reduce` is
+// IR_TRANSFER_* of the public header.  The items of ir_attn_match: one wave each, at most kTransferMaxItems
+constexpr int kTransferPerHead = 0, kTransferHeadMean = 1;
+constexpr int kTransferMaxChannels = 8;
+constexpr int64_t kTransferMaxItems = 0x7fffffffLL - 3;
+int64_t ir_attn_transfer_items(const AttnKParams& p, int n_rows, int reduce);
+hipError_t ir_launch_attn_transfer(const AttnKParams& p, int dtype, const float* payload, int64_t pay_sb, int64_t pay_sj, int channels,
+                                   const int32_t* row_index, int n_rows, int reduce, float* sums, float* mass, hipStream_t s);
 hipError_t ir_launch_adain_stats(const AdainKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_token_stats(const AdainKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_adain_stats_cached(const AdainKParams& p, int dtype, hipStream_t s);

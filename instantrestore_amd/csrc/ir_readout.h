@@ -1,8 +1,8 @@
-// ir_readout.h - the QK block that the read-out kernels share (attn_probs.hip, attn_rows.hip, attn_match.hip; gfx950).
+// ir_readout.h - the QK block that the read-out kernels share (attn_probs.hip, attn_rows.hip, attn_match.hip, attn_transfer.hip; gfx950).
 // For this family only: the forward kernels have their own operand paths and never include it.
 //
 // Every read-out recomputes P = exp2(fma(<q, k>, scale*log2(e), -lse*log2(e))) from the LSE of the fused forward, and the tests
-// hold the results of the three files to each other bit for bit.  What that rests on is here, once:
+// hold the results of these files to each other bit for bit.  What that rests on is here, once:
 //   * the contraction of a 32 x 32 block is issued SWAPPED (S^T = K Q^T: keys on the MFMA rows, query rows on its columns), and
 //     the key a lane supplies for MFMA row i is keymap(i).  Lane (lq, hi) - lq = lane & 31, hi = lane >> 5 - then holds C rows
 //     (r&3) + 8(r>>2) + 4hi, r = 0..15  ==  the 16 CONSECUTIVE keys 16*hi + r of ONE query row lq: whole 16-byte pieces of a
@@ -119,7 +119,7 @@ static __device__ __forceinline__ void gather_rows(const int32_t* idx, int R, in
   }
 }
 
-// ---- host side: the row groups of ir_attn_rows / ir_attn_match ----
+// ---- host side: the row groups of ir_attn_rows / ir_attn_match / ir_attn_transfer ----
 // 32-row blocks a wave holds: the padded row count up to 96, three beyond; further rows are further groups
 static inline int rows_nq(int n_rows) {
   const int nblk = (n_rows + 31) / 32;

@@ -813,6 +813,73 @@ def attn_match(q, k_self, ref_k, lse, rows=None, *, heads: int, scale: float, in
     return index, prob
 
 
+TRANSFER_REDUCE = {"none": _lib.IR_TRANSFER_PER_HEAD, "head_mean": _lib.IR_TRANSFER_HEAD_MEAN}
+
+
+def _transfer_payload(payload, batch: int, lkv: int, device: torch.device):
+    """``payload`` checked against the call: the tensor as it is (never copied) and its batch / key strides in floats"""
+    if not isinstance(payload, torch.Tensor) or payload.dtype != torch.float32:
+        raise ValueError(f"payload must be an fp32 tensor, got {getattr(payload, 'dtype', type(payload))}")
+    if payload.dim() not in (2, 3):
+        raise ValueError(f"payload must be (Lkv, C), (1, Lkv, C) or (B, Lkv, C), got {tuple(payload.shape)}")
+    if payload.device != device:
+        raise ValueError(f"payload is on {payload.device}, the call on {device}")
+    if payload.dim() == 3 and payload.shape[0] not in (1, batch):
+        raise ValueError(f"payload: {payload.shape[0]} batch entries for a batch of {batch} (1 or {batch})")
+    if payload.shape[-2] != lkv:
+        raise ValueError(f"payload: {payload.shape[-2]} keys, the call has Lkv = {lkv}")
+    nch = payload.shape[-1]
+    if nch < 1 or nch > _lib.IR_TRANSFER_MAX_CHANNELS:
+        raise ValueError(f"payload: {nch} channels, expected 1 ... {_lib.IR_TRANSFER_MAX_CHANNELS} (call again for more)")
+    if payload.stride(-1) != 1:
+        raise ValueError(f"payload: last-axis stride {payload.stride(-1)}, expected 1")
+    sj = payload.stride(-2) if lkv > 1 else nch
+    sb = payload.stride(0) if payload.dim() == 3 and payload.shape[0] == batch and batch > 1 else 0
+    if sj < nch or sb < 0:
+        raise ValueError(f"payload: key stride {sj} must be >= {nch} channels and the batch stride {sb} >= 0")
+    return payload, sb, sj, nch
+
+
+@_on_tensor_device
+def attn_transfer(q, k_self, ref_k, lse, payload, rows=None, *, heads: int, scale: float, include_self: bool = True,
+                  reduce: str = "none", normalize: bool = False, q_prescaled: bool = False, batch_invariant: bool = False):
+    """Attention-weighted sums of a per-key payload for the query tokens ``rows`` from the LSE of the fused forward, without the
+    ``(B, H, Lq, Lkv)`` tensor (``ir_attn_transfer``): ``einsum('bhij,bjc->bhic', attention_probs[..., segment], payload[:, segment])``
+    per segment of ``[self (iff include_self)] ++ ref 0 ++ ... ++ ref N-1`` - the soft form of :func:`attn_match`.
+
+    ``payload``: fp32 device tensor ``(Lkv, C)``, ``(1, Lkv, C)`` (one payload for the whole batch) or ``(B, Lkv, C)``, ``C <= 8``,
+    last-axis stride 1; its key and batch strides are passed through, never copied
+    (:func:`instantrestore_amd.attn_maps.coordinate_payload` / ``image_payload`` build the usual ones).  ``rows``: ``None`` - every
+    query token, in order - or an integer tensor ``(R,)`` / ``(B, R)`` as for :func:`attn_match` (a device index outside ``[0, Lq)``
+    gives sums 0, mass 0).  Returns ``(values, mass)``, fp32: ``(B, H, R, S, C)`` and ``(B, H, R, S)`` with ``reduce="none"``,
+    ``(B, R, S, C)`` and ``(B, R, S)`` with ``"head_mean"`` - bit for bit ``((S_0 + S_1) + ...) * (1/H)`` of the per-head result.
+    ``values`` are the UNNORMALISED sums (``values.sum(-2)`` is the expectation over all keys); ``normalize=True`` returns
+    ``sums / mass`` - the expectation inside each segment - where ``mass > 0`` and 0 elsewhere.  The mass and every channel are
+    summed over the same keys in the same order: a channel of ones IS the mass, a one-hot channel IS that key's fp32 probability
+    (what :func:`attn_rows` rounds to q's dtype).  ``q_prescaled`` as in :func:`attn_probs`.  Batch invariant by construction;
+    ``batch_invariant`` is accepted and changes nothing."""
+    if reduce not in TRANSFER_REDUCE:
+        raise ValueError(f"reduce must be one of {sorted(TRANSFER_REDUCE)}, got {reduce!r}")
+    args, q, B, Lq, lkv, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant)
+    args.tuning = 0   # one kernel: the A/B hook of the forward does not apply
+    payload, sb, sj, nch = _transfer_payload(payload, B, lkv, q.device)
+    if rows is None:
+        idx = torch.arange(Lq, dtype=torch.int32, device=q.device).unsqueeze(0).expand(B, -1).contiguous()
+    else:
+        idx = _row_index(rows, B, Lq, q.device)
+    R = idx.shape[1]
+    nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
+    shape = (B, heads, R, nseg) if reduce == "none" else (B, R, nseg)
+    sums = torch.empty(shape + (nch,), dtype=torch.float32, device=q.device)
+    mass = torch.empty(shape, dtype=torch.float32, device=q.device)
+    _lib.check(_lib.lib().ir_attn_transfer(C.byref(args), payload.data_ptr(), sb, sj, nch, idx.data_ptr(), R, TRANSFER_REDUCE[reduce],
+                                           sums.data_ptr(), mass.data_ptr(), _stream()), "ir_attn_transfer")
+    if normalize:
+        m = mass.unsqueeze(-1)
+        sums = torch.where(m > 0, sums / m, torch.zeros_like(sums))
+    return sums, mass
+
+
 @_on_tensor_device
 def adain_stats(v_self: torch.Tensor, ref_v: torch.Tensor, *, heads: int, eps: float = ADAIN_EPS):
     """AdaIN as a per-(b, n, head, channel) affine ``x*a + b`` (``ir_adain_stats``).

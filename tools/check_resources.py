@@ -9,8 +9,9 @@ import re
 import subprocess
 import sys
 
-NO_SCRATCH = ("linear_tiled", "shared_attn_fwd_w128", "attn_rows_kernel", "attn_match_kernel")     # mangled-name substrings: scratch / spills are a build error for these kernels
-# (attn_rows_kernel / attn_match_kernel hold up to 96 / 192 fp32 sums per lane across their head walk: a spill would put them in scratch memory)
+NO_SCRATCH = ("linear_tiled", "shared_attn_fwd_w128", "attn_rows_kernel", "attn_match_kernel", "attn_transfer_kernel")     # mangled-name substrings: scratch / spills are a build error for these kernels
+# (attn_rows_kernel / attn_match_kernel hold up to 96 / 192 fp32 sums per lane across their head walk: a spill would put them in scratch memory;
+# attn_transfer_kernel keeps up to 27 running sums, 27 head totals and 48 probabilities beside its operands)
 
 
 def demangle(name):
