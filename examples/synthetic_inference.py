@@ -58,6 +58,13 @@ def main(argv=None):
                     help="one more frame that leaves the attention-weighted mean position inside every reference behind for every query "
                          "token (attention_transfer with the coordinate payload): prints, per shared layer and reference, the mean soft "
                          "displacement, the mean mass and how often the rounded expected position is attention_match's hard match")
+    ap.add_argument("--received", action="store_true",
+                    help="one more frame that leaves, for every token of every reference, the attention it receives from the whole "
+                         "degraded face behind (attention_received, unweighted): prints, per shared layer, the received mass per reference")
+    ap.add_argument("--prune", type=float, default=None, metavar="FRACTION",
+                    help="with --received: keep that fraction of every reference's tokens, the ones the top shared layer looked at most on "
+                         "the warm-up frame (attn_maps.keep_from_received -> ops.compact_refs -> ref_lens); prints the top layer's masses "
+                         "and the kept counts with and without")
     ap.add_argument("--ref-weights", default=None,
                     help="comma-separated weight per reference, e.g. 1,1,0.25,0 (0 masks a reference): prints the top shared layer's "
                          "per-reference attention masses with and without")
@@ -68,6 +75,8 @@ def main(argv=None):
     ap.add_argument("--kv-tables", action="store_true",
                     help="one more cached frame whose reference K/V are pointer tables into the cache entries (assemble_tables: no copy)")
     args = ap.parse_args(argv)
+    if args.prune is not None and not args.received:
+        ap.error("--prune chooses its tokens from the attention they received: give --received with it")
 
     import __graft_entry__ as ge
     from face_replace.models.attn_processors import register_attention_processor, register_attention_processor_kv_unet
@@ -288,6 +297,55 @@ def main(argv=None):
                       f"share of tokens whose rounded expected position is the hard match {fmt(agree)}")
                 assert float(pos.min()) >= 0 and float(pos.max()) <= side_len - 1 + 1e-3 and float(mass.min()) > 0
                 assert float((mass.sum(-1) - 1).abs().max()) < 8e-3
+        # Which tokens of each reference does the restored face USE, and how much?  The column sums of the attention: each shared
+        # layer leaves fp32 (B, Lkv, 1) behind - per key, the head-mean attention summed over every query token - instead of the
+        # (B, H, L, Lkv) tensor.  A reference's received mass is its share of the L units the query tokens hand out.  With --prune
+        # that warm-up frame decides which tokens every later frame of the identity keeps: data-driven, where --compact-refs
+        # keeps a centred ellipse.
+        if args.received:
+            from instantrestore_amd.attn_maps import keep_from_received, received_maps
+            shared = sorted((p for p in unet.attn_processors.values() if getattr(p, "self_attn_idx", None) is not None),
+                            key=lambda p: p.self_attn_idx)
+            for p in shared:
+                p.attention_received_weights = "ones"
+            unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1),
+                 cross_attention_kwargs={"ref_keys": ck, "ref_values": cv, "ref_stats": cs})
+            fmt = lambda m: " ".join(f"{v:.4f}" for v in m.tolist())
+            recv_top = None
+            for p in shared:
+                recv, p.attention_received_weights = p.attention_received, None
+                tokens = ck[p.self_attn_idx].shape[2]
+                maps = received_maps(recv, tokens, N, tokens, bool(p.train_input))         # (B, S, side, side, 1)
+                per_seg = maps.sum(dim=(2, 3, 4)) / tokens                                  # (B, S): shares of the query tokens' attention
+                print(f"shared layer {p.self_attn_idx}: received {tuple(recv.shape)}; received mass [self?] ++ references "
+                      f"{fmt(per_seg.mean(dim=0))}; largest share of one token {float(recv.max()) / tokens:.4f}")
+                assert float(recv.min()) >= 0 and float((per_seg.sum(-1) - 1).abs().max()) < 8e-3
+                if p.self_attn_idx == 8:
+                    recv_top = recv
+            if args.prune is not None:
+                frac = float(args.prune)
+                assert 0.0 < frac <= 1.0, "--prune needs a fraction in (0, 1]"
+                top = [p for p in shared if p.self_attn_idx == 8][0]
+                tokens = ck[8].shape[2]
+                side_len = int(round(tokens ** 0.5))
+                keep = keep_from_received(recv_top, tokens, N, tokens, bool(top.train_input), frac)       # (B, N, tokens) bool
+                packed = [ops.compact_refs(k, v, keep.view(B, N, side_len, side_len), heads=k.shape[-1] // 64)
+                          for k, v in zip(ck, cv)]                                                    # pooled to every layer's side
+                top.save_attention_mass = True
+                unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1),
+                     cross_attention_kwargs={"ref_keys": ck, "ref_values": cv, "ref_stats": cs})
+                m0 = top.attention_mass.mean(dim=(1, 2))
+                zp = unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1),
+                          cross_attention_kwargs={"ref_keys": [t[0] for t in packed], "ref_values": [t[1] for t in packed], "ref_stats": cs,
+                                                  "ref_lens": [t[2] for t in packed]}).sample
+                m1 = top.attention_mass.mean(dim=(1, 2))
+                top.save_attention_mass = False
+                fmt3 = lambda m: " ".join(f"{v:.3f}" for v in m.tolist())
+                for b in range(B):
+                    print(f"identity {b}: mass [self?] ++ references  full {fmt3(m0[b])}  |  pruned to {packed[8][2][b].tolist()} of {tokens} "
+                          f"tokens by received attention: {fmt3(m1[b])}")
+                assert bool(torch.isfinite(zp).all()) and float((m1.sum(-1) - 1).abs().max()) < 2e-3
+                assert packed[8][2].tolist() == [[int(keep[b, n].sum()) for n in range(N)] for b in range(B)]
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     assert out_u8.shape == (B, S, S, 3) and out_u8.dtype == torch.uint8

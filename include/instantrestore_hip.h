@@ -459,6 +459,56 @@ int ir_attn_transfer(const ir_shared_attn_args* args, const float* payload, int6
                      const int32_t* row_index, int32_t n_rows, int32_t reduce, float* sums, float* mass, void* stream);
 
 /*
+ * ir_attn_received (opt-in) - per-key sums of the attention over ALL query rows, weighted by a per-row payload, without the
+ * probability matrix: the column sums of P.
+ *
+ * Replaces `einsum('bhij,bic->bhjc', attention_probs, w)` (w = 1: `attention_probs.sum(dim=-2)`): how much every key - every
+ * token of every reference - is looked at by the whole degraded face (w = 1), by a region of it (w = a mask) or per label (w = a
+ * parsing map).  Every other read-out reduces along the key axis; this one reduces along the query axis, and it is the adjoint of
+ * ir_attn_transfer: <w, P y> = <P^T w, y>.  Same args as ir_attn_rows / ir_attn_match / ir_attn_transfer (q, the K pointers or the
+ * K table, lse; v_*, adain_*, out, valid_refs, seg_mass and workspace are ignored - every reference is walked - and `tuning` must
+ * be 0; IR_FLAG_Q_PRESCALED: same rule; IR_FLAG_BATCH_INVARIANT: accepted, inert) plus
+ *   weights    fp32 on the device, 4-byte aligned, over the query axis: w[b, i, c] = weights[b * w_sb + i * w_si + c], strides in
+ *              floats, every offset formed in 64 bits.  w_sb >= 0 (0: one payload for every batch entry), w_si >= channels;
+ *              nothing outside the `channels` floats of a row is read.  NULL: one channel of ones (channels must be 1).  Read by
+ *              the kernel when it runs: a replayed hipGraph follows in-place updates of it (and of the pointer tables).
+ *   channels   1 ... IR_RECEIVED_MAX_CHANNELS (call again for more)
+ *   reduce     IR_RECEIVED_PER_HEAD   recv fp32 (B, H, Lkv, channels)
+ *              IR_RECEIVED_HEAD_MEAN  recv fp32 (B, Lkv, channels)
+ *   recv       contiguous, 4-byte aligned: recv[b, h, j, c] = sum over i = 0 .. len_q - 1 of p[b,h,i,j] * w[b,i,c], j on the PACKED
+ *              extended key axis [self (iff INCLUDE_SELF)] ++ ref 0 ++ ... ++ ref N-1 (the axis of ir_attn_transfer's payload and of
+ *              key_bias), with the fp32 p = exp2(fma(<q_i, k_j>, scale*log2(e), -lse[b,h,i]*log2(e))) of ir_attn_probs / ir_attn_rows
+ * Bit for bit (part of the interface):
+ *   - every (row, key, channel) term is one fp32 fused multiply-add with the weight as multiplicand (no weights: multiplicand
+ *     1.0f); all channels of a key are accumulated over the same rows in the same order.  weights == NULL equals a channel of ones;
+ *     two equal channels give equal outputs; a channel that is 1 at one row i and 0 elsewhere equals that row's fp32 p[i, j] at every
+ *     key j - the value ir_attn_rows rounds to `dtype`;
+ *   - the order is a function of len_q and reduce only - not of batch, the grid, the stream or the device's CU count.  With
+ *     l = i mod 32: the partial sum s_l starts at 0 and takes the rows l, l + 32, l + 64, ... in ascending order (lane l of a
+ *     half-wave, one row per 32-row block).  The 32 partial sums then meet in a butterfly over the lane bits 1, 2, 4, 8, 16 in that
+ *     order - at step m lane l replaces its value by (its own + lane l ^ m's) - which is the balanced tree
+ *       ((((s0+s1) + (s2+s3)) + ((s4+s5) + (s6+s7))) + (the same over s8..s15)) + (the same over s16..s31);
+ *   - IR_RECEIVED_HEAD_MEAN == ((R_0 + R_1) + ... + R_{H-1}) * (1.0f / (float)H) of the IR_RECEIVED_PER_HEAD outputs R_h (the fold
+ *     starts at 0 + R_0); with a one-hot channel that is the element of ir_attn_rows' IR_ROWS_HEAD_MEAN row;
+ *   - rows of the padding to a whole 32-row block contribute exactly nothing (probability and weight replaced by 0; a padded
+ *     row's own weight is never addressed - nothing behind row len_q - 1 of `weights` is read); keys past the end of a segment
+ *     are never written.
+ * Bound: Q, lse and the weights read once per group of 96 / 96 / 64 / 32 keys (channels padded to 1 / 2 / 4 / 8), K once;
+ * Lkv * channels floats written per (head,) batch entry; no workspace, no atomics, one launch; asynchronous and capturable.  One
+ * wave walks the whole query axis for its keys, so every output element has one writer; the cut follows len_self, len_ref,
+ * n_refs, channels and reduce only.  Any segment length, any len_q.
+ * Checked in this order, after the checks of the args block: IR_ERR_INVALID_ARG: NULL recv, NULL lse; IR_ERR_UNSUPPORTED: channels
+ * outside its range; IR_ERR_INVALID_ARG: NULL weights with channels != 1, w_sb < 0, w_si < channels; IR_ERR_UNSUPPORTED: another
+ * reduce, a misaligned weights / recv, more than 2^31 - 4 work items.  Refused with the args block: a key_bias or ref_lens block
+ * (IR_ERR_UNSUPPORTED, as for the other read-outs), tuning != 0.
+ */
+#define IR_RECEIVED_PER_HEAD 0
+#define IR_RECEIVED_HEAD_MEAN 1
+#define IR_RECEIVED_MAX_CHANNELS 8
+int ir_attn_received(const ir_shared_attn_args* args, const float* weights, int64_t w_sb, int64_t w_si, int32_t channels,
+                     int32_t reduce, float* recv, void* stream);
+
+/*
  * ir_adain_stats - per-(b, n, channel) AdaIN affine from token statistics.
  *
  * Replaces the statistics half of adain() (attn_processors.py:9-10) and of its call site

@@ -6,7 +6,9 @@ mean of the whole ``attention_probs``; here the index list goes IN (``attention_
 ever computed.  ``match_coordinates`` / ``match_field`` turn the key indices of ``ops.attn_match`` /
 ``SharedAttnProcessor.attention_match`` into grid coordinates and displacements.  ``coordinate_payload`` / ``image_payload`` build
 the per-key payloads of ``ops.attn_transfer`` / ``SharedAttnProcessor.attention_transfer_payload`` and ``soft_match_field`` reads
-its sums back as expected positions: the soft form of ``match_field``."""
+its sums back as expected positions: the soft form of ``match_field``.  ``received_maps`` / ``keep_from_received`` read the per-key
+sums of ``ops.attn_received`` / ``SharedAttnProcessor.attention_received``: pictures per segment, and a ``keep`` mask for
+``ops.compact_refs``."""
 import numpy as np
 
 
@@ -159,3 +161,58 @@ def soft_match_field(sums, mass, rows, side: int):
     pos = torch.where(ok, sums / torch.where(m > 0, m, torch.ones_like(m)), zero)
     disp = torch.where(ok, pos - own.to(sums.dtype), zero)
     return pos, disp, mass
+
+
+def _received_axes(recv, len_self: int, n_refs: int, len_ref: int, include_self: bool):
+    """the packed key axis of ``recv`` ``(..., Lkv, C)`` checked against the call: ``(offset of reference 0, Lkv)``"""
+    off = int(len_self) if include_self else 0
+    lkv = off + int(n_refs) * int(len_ref)
+    if lkv == 0:
+        raise ValueError("empty key axis: include_self is False and n_refs is 0")
+    if recv.dim() not in (3, 4) or recv.shape[-2] != lkv:
+        raise ValueError(f"recv must be (B, Lkv, C) or (B, H, Lkv, C) with Lkv = {lkv}, got {tuple(recv.shape)}")
+    return off, lkv
+
+
+def received_maps(recv, len_self: int, n_refs: int, len_ref: int, include_self: bool):
+    """``recv`` of ``ops.attn_received`` / ``SharedAttnProcessor.attention_received`` - ``(B, Lkv, C)`` or ``(B, H, Lkv, C)`` over
+    the packed key axis ``[self (iff include_self)] ++ ref 0 ++ ... ++ ref N-1`` - as per-segment pictures ``(..., S, side, side, C)``,
+    ``S = include_self + n_refs``: how much every token of every segment is looked at, on the segment's own square grid, row-major
+    (the convention of :func:`match_coordinates`).  A view where the layout allows it.  A segment length that is no square, or a
+    self segment and references of different lengths (no common ``side``): ``ValueError``."""
+    off, _ = _received_axes(recv, len_self, n_refs, len_ref, include_self)
+    lens = ([int(len_self)] if include_self else []) + ([int(len_ref)] if n_refs else [])
+    sides = [_square_side(n, what) for n, what in zip(lens, (["len_self"] if include_self else []) + ["len_ref"])]
+    if len(set(sides)) != 1:
+        raise ValueError(f"len_self = {len_self} and len_ref = {len_ref} are square grids of different sides {sides}: cut recv at "
+                         f"{off} and call once per part")
+    side, S = sides[0], (1 if include_self else 0) + int(n_refs)
+    return recv.reshape(tuple(recv.shape[:-2]) + (S, side, side, recv.shape[-1]))
+
+
+def keep_from_received(recv, len_self: int, n_refs: int, len_ref: int, include_self: bool, keep_fraction: float):
+    """a ``keep`` mask for ``ops.compact_refs`` from the attention the reference tokens received on a warm-up frame: bool
+    ``(B, N, len_ref)``, per reference ``True`` on the ``ceil(keep_fraction * len_ref)`` tokens that received most.  The count
+    is ``ceil(keep_fraction * len_ref - 1e-9)``, at least 1 and at most ``len_ref``: the ``1e-9`` takes a product that binary
+    floating point puts a hair above a whole number back to it (``0.3 * 10`` keeps 3 tokens, not 4).
+
+    ``recv`` as for :func:`received_maps`.  Channel 0 is the score when there are several; a per-head ``recv`` is averaged over its
+    heads first.  Ties go to the LOWER token index (a stable descending sort).  Everything stays on ``recv``'s device: no host
+    sync beyond what ``torch`` itself does."""
+    import math
+
+    import torch
+    off, lkv = _received_axes(recv, len_self, n_refs, len_ref, include_self)
+    if int(n_refs) < 1:
+        raise ValueError("keep_from_received needs n_refs >= 1")
+    if not 0.0 < float(keep_fraction) <= 1.0:
+        raise ValueError(f"keep_fraction must lie in (0, 1], got {keep_fraction}")
+    count = min(int(len_ref), max(1, math.ceil(float(keep_fraction) * int(len_ref) - 1e-9)))
+    score = recv[..., 0]
+    if score.dim() == 3:
+        score = score.mean(dim=1)
+    score = score[:, off:lkv].reshape(score.shape[0], int(n_refs), int(len_ref))
+    order = torch.sort(-score, dim=-1, stable=True).indices                 # descending, equal scores in ascending token order
+    keep = torch.zeros(score.shape, dtype=torch.bool, device=score.device)
+    keep.scatter_(-1, order[..., :count], True)
+    return keep

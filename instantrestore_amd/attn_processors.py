@@ -554,6 +554,16 @@ class SharedAttnProcessor(nn.Module):
         self.attention_transfer_index = None
         self.attention_transfer_reduce = "head_mean"
         self.attention_transfer = None
+        # opt-in (plain attributes like ``attention_transfer_payload``): ``attention_received_weights`` - ``"ones"`` or an fp32 device
+        # tensor over the QUERY axis, ``(L, C)``, ``(1, L, C)`` or ``(B, L, C)``, C <= 8 (``(L,)`` / ``(B, L)``: one channel) - makes every
+        # call of a shared layer leave ``attention_received``: per key of the packed key axis the sum over ALL query tokens of the
+        # attention times the weights (``ir_attn_received``) - ``einsum('bhij,bic->bhjc', attention_probs, w)``, with "ones"
+        # ``attention_probs.sum(-2)``, without the (B, H, L, Lkv) tensor.  ``attention_received_reduce``: "head_mean" - fp32
+        # (B, Lkv, C); "none" - (B, H, Lkv, C).  ``attn_maps.received_maps`` cuts it into pictures, ``keep_from_received`` into a
+        # ``keep`` mask for ``ops.compact_refs``.  Uses the LSE of the same attention call.  ``None``: off, nothing changes.
+        self.attention_received_weights = None
+        self.attention_received_reduce = "head_mean"
+        self.attention_received = None
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                 ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None, ref_weights=None, ref_token_keep=None,
@@ -624,6 +634,9 @@ class SharedAttnProcessor(nn.Module):
                 if getattr(self, "attention_transfer_payload", None) is not None:
                     raise NotImplementedError("ref_lens together with attention_transfer_payload: ir_attn_transfer would walk the tails "
                                               "behind the counts (follow-up)")
+                if getattr(self, "attention_received_weights", None) is not None:
+                    raise NotImplementedError("ref_lens together with attention_received_weights: ir_attn_received would walk the tails "
+                                              "behind the counts (follow-up)")
                 if self.use_adain and cstats is None:
                     raise ValueError("ref_lens with use_adain needs ref_stats: the AdaIN content statistics are those of the full reference, "
                                      "taken before compaction - computing them here would read the packed rows and whatever lies behind them")
@@ -670,7 +683,11 @@ class SharedAttnProcessor(nn.Module):
         rows_index = getattr(self, "attention_rows_index", None) if shared else None
         match_index = getattr(self, "attention_match_index", None) if shared else None
         transfer_payload = getattr(self, "attention_transfer_payload", None) if shared else None
-        want_lse = want_probs or rows_index is not None or match_index is not None or transfer_payload is not None
+        received_weights = getattr(self, "attention_received_weights", None) if shared else None
+        if isinstance(received_weights, str) and received_weights != "ones":          # before anything is launched
+            raise ValueError(f"attention_received_weights must be None, \"ones\" or an fp32 tensor, got {received_weights!r}")
+        want_lse = want_probs or rows_index is not None or match_index is not None or transfer_payload is not None or \
+            received_weights is not None
         kw = {"q_prescaled": True} if presc else {}
         kw.update(_bi_kw(bi))
         if shared and ref_valid is not None:
@@ -695,6 +712,9 @@ class SharedAttnProcessor(nn.Module):
             if transfer_payload is not None:
                 raise NotImplementedError("attention_transfer_payload together with an attention mask, ref_weights or ref_token_keep: "
                                           "ir_attn_transfer does not take the key bias yet (follow-up)")
+            if received_weights is not None:
+                raise NotImplementedError("attention_received_weights together with an attention mask, ref_weights or ref_token_keep: "
+                                          "ir_attn_received does not take the key bias yet (follow-up)")
             kw["key_bias"] = bias
         # the masses are a by-product of the attention launch itself (ABI v9 ``seg_mass``: the kernels hold the row sums at every
         # segment boundary): no second pass over Q and K
@@ -730,6 +750,12 @@ class SharedAttnProcessor(nn.Module):
                                                          heads=attn.heads, scale=0.6931471805599453 if presc else attn.scale,
                                                          include_self=include_self,
                                                          reduce=getattr(self, "attention_transfer_reduce", "head_mean"), **_bi_kw(bi))
+        if received_weights is not None:
+            # what every key receives from all query tokens ("ones": unweighted), same LSE
+            self.attention_received = _ops.attn_received(query, key, ref_k, lse, None if isinstance(received_weights, str) else received_weights,
+                                                         heads=attn.heads, scale=0.6931471805599453 if presc else attn.scale,
+                                                         include_self=include_self,
+                                                         reduce=getattr(self, "attention_received_reduce", "head_mean"), **_bi_kw(bi))
         if want_probs:
             # (B, H, L, Lkv), columns [self?] ++ ref0 ++ ... ++ refN-1, in the compute dtype.  A pre-scaled query
             # already carries scale * log2(e): its scores are exponents, ln 2 turns them into the logits of the LSE

@@ -35,7 +35,7 @@ int64_t seg_stride_limit(int32_t len, int64_t sl) {
 }
 
 // `fwd`: the call is (or describes) a launch of the attention forward, whose segment-span limit applies; the read-out entry points
-// (ir_attn_probs*, ir_attn_segment_mass, ir_attn_rows, ir_attn_match, ir_attn_transfer) address K through 64-bit pointers and take any stride
+// (ir_attn_probs*, ir_attn_segment_mass, ir_attn_rows, ir_attn_match, ir_attn_transfer, ir_attn_received) address K through 64-bit pointers and take any stride
 bool attn_block_size_ok(uint32_t n) {
   return n == sizeof(ir_shared_attn_args) || n == sizeof(ir_shared_attn_table_args) || n == sizeof(ir_shared_attn_bias_args) ||
          n == sizeof(ir_shared_attn_ragged_args);
@@ -86,7 +86,7 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
   if (a->seg_mass != nullptr && (reinterpret_cast<uintptr_t>(a->seg_mass) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "seg_mass must be 4-byte aligned");
   if (kbias != nullptr) {
     if (!fwd)
-      return fail(IR_ERR_UNSUPPORTED, "key_bias: ir_attn_probs[_ex], ir_attn_segment_mass, ir_attn_rows, ir_attn_match and ir_attn_transfer do not take a key bias yet (their exp(s - lse) would "
+      return fail(IR_ERR_UNSUPPORTED, "key_bias: ir_attn_probs[_ex], ir_attn_segment_mass, ir_attn_rows, ir_attn_match, ir_attn_transfer and ir_attn_received do not take a key bias yet (their exp(s - lse) would "
                   "leave it out); the forward's seg_mass by-product does");
     if ((reinterpret_cast<uintptr_t>(kbias) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "key_bias must be 4-byte aligned");
     if (ba->kb_sb < 0 || ba->kb_sh < 0) return fail(IR_ERR_INVALID_ARG, "key_bias strides kb_sb %lld, kb_sh %lld must be >= 0", (long long)ba->kb_sb, (long long)ba->kb_sh);
@@ -99,7 +99,7 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
   }
   if (rlens != nullptr) {
     if (!fwd)
-      return fail(IR_ERR_UNSUPPORTED, "ref_lens: ir_attn_probs[_ex], ir_attn_segment_mass, ir_attn_rows, ir_attn_match and ir_attn_transfer do not take per-reference counts yet (they would "
+      return fail(IR_ERR_UNSUPPORTED, "ref_lens: ir_attn_probs[_ex], ir_attn_segment_mass, ir_attn_rows, ir_attn_match, ir_attn_transfer and ir_attn_received do not take per-reference counts yet (they would "
                   "walk the tails behind the counts); the forward's seg_mass by-product does");
     if ((reinterpret_cast<uintptr_t>(rlens) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "ref_lens must be 4-byte aligned");
     if (a->n_refs == 0) return fail(IR_ERR_UNSUPPORTED, "ref_lens with n_refs == 0: there is no reference to count");
@@ -239,7 +239,7 @@ int launch_fwd(const ir_shared_attn_args* a, const AttnKParams& p, hipStream_t s
 }
 
 // The parameter block of a read-out of the forward's LSE (ir_attn_probs_ex, ir_attn_segment_mass, ir_attn_rows, ir_attn_match,
-// ir_attn_transfer).
+// ir_attn_transfer, ir_attn_received).
 // `single_kernel`: the name of an entry point that has one kernel and refuses a tuning value, or nullptr.  A key bias and
 // per-reference counts are refused for the whole family in build_attn_params (!fwd)
 int build_readout_params(const ir_shared_attn_args* args, AttnKParams* p, const char* single_kernel) {
@@ -492,6 +492,30 @@ int ir_attn_transfer(const ir_shared_attn_args* args, const float* payload, int6
   if (ir_attn_transfer_items(p, n_rows, reduce) > kTransferMaxItems) return fail(IR_ERR_UNSUPPORTED, "grid too large");
   const hipError_t e = ir_launch_attn_transfer(p, args->dtype, payload, pay_sb, pay_sj, channels, row_index, n_rows, reduce, sums, mass, (hipStream_t)stream);
   if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "attn_transfer launch: %s", hipGetErrorString(e));
+  return IR_OK;
+}
+
+// The checks of its own arguments, in this order (the header states it): NULL recv, NULL lse, channels, NULL weights with
+// channels != 1, the strides, the form, the alignments, the item count
+int ir_attn_received(const ir_shared_attn_args* args, const float* weights, int64_t w_sb, int64_t w_si, int32_t channels,
+                     int32_t reduce, float* recv, void* stream) {
+  AttnKParams p;
+  const int rc = build_readout_params(args, &p, "ir_attn_received");
+  if (rc != IR_OK) return rc;
+  if (recv == nullptr) return fail(IR_ERR_INVALID_ARG, "recv is NULL");
+  if (args->lse == nullptr) return fail(IR_ERR_INVALID_ARG, "lse is NULL");
+  if (channels < 1 || channels > IR_RECEIVED_MAX_CHANNELS)
+    return fail(IR_ERR_UNSUPPORTED, "channels %d outside [1, IR_RECEIVED_MAX_CHANNELS = %d] (call again for more)", channels, IR_RECEIVED_MAX_CHANNELS);
+  if (weights == nullptr && channels != 1) return fail(IR_ERR_INVALID_ARG, "weights is NULL (one channel of ones): channels must be 1 (got %d)", channels);
+  if (w_sb < 0) return fail(IR_ERR_INVALID_ARG, "w_sb %lld must be >= 0 (0: one payload for every batch entry)", (long long)w_sb);
+  if (w_si < (weights != nullptr ? channels : 0)) return fail(IR_ERR_INVALID_ARG, "w_si %lld must be >= channels %d", (long long)w_si, channels);
+  if (reduce != IR_RECEIVED_PER_HEAD && reduce != IR_RECEIVED_HEAD_MEAN)
+    return fail(IR_ERR_UNSUPPORTED, "reduce %d: IR_RECEIVED_PER_HEAD (0) or IR_RECEIVED_HEAD_MEAN (1)", reduce);
+  if ((reinterpret_cast<uintptr_t>(weights) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "weights must be 4-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(recv) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "recv must be 4-byte aligned");
+  if (ir_attn_received_items(p, channels, reduce) > kReceivedMaxItems) return fail(IR_ERR_UNSUPPORTED, "grid too large");
+  const hipError_t e = ir_launch_attn_received(p, args->dtype, weights, w_sb, w_si, channels, reduce, recv, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "attn_received launch: %s", hipGetErrorString(e));
   return IR_OK;
 }
 

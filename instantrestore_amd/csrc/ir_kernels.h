@@ -228,6 +228,16 @@ constexpr int64_t kTransferMaxItems = 0x7fffffffLL - 3;
 int64_t ir_attn_transfer_items(const AttnKParams& p, int n_rows, int reduce);
 hipError_t ir_launch_attn_transfer(const AttnKParams& p, int dtype, const float* payload, int64_t pay_sb, int64_t pay_sj, int channels,
                                    const int32_t* row_index, int n_rows, int reduce, float* sums, float* mass, hipStream_t s);
+// attn_received.hip: per key of the packed extended key axis, the sum over ALL query rows of p * w for a per-row fp32 payload
+// (`channels` floats per row, batch / row strides w_sb / w_si in floats; nullptr: one channel of ones), recv fp32
+// (B, H, Lkv, channels) / (B, Lkv, channels); `reduce` is IR_RECEIVED_* of the public header.  One wave per item (a group of keys
+// of one segment), at most kReceivedMaxItems
+constexpr int kReceivedPerHead = 0, kReceivedHeadMean = 1;
+constexpr int kReceivedMaxChannels = 8;
+constexpr int64_t kReceivedMaxItems = 0x7fffffffLL - 3;
+int64_t ir_attn_received_items(const AttnKParams& p, int channels, int reduce);
+hipError_t ir_launch_attn_received(const AttnKParams& p, int dtype, const float* weights, int64_t w_sb, int64_t w_si, int channels, int reduce,
+                                   float* recv, hipStream_t s);
 hipError_t ir_launch_adain_stats(const AdainKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_token_stats(const AdainKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_adain_stats_cached(const AdainKParams& p, int dtype, hipStream_t s);

@@ -880,6 +880,74 @@ def attn_transfer(q, k_self, ref_k, lse, payload, rows=None, *, heads: int, scal
     return sums, mass
 
 
+RECEIVED_REDUCE = {"none": _lib.IR_RECEIVED_PER_HEAD, "head_mean": _lib.IR_RECEIVED_HEAD_MEAN}
+
+
+def _received_weights(weights, batch: int, len_q: int, device: torch.device):
+    """``weights`` checked against the call: the tensor as it is (never copied), its batch / row strides in floats and its
+    channel count.  ``(L,)`` / ``(B, L)`` are one channel; ``(L, C)``, ``(1, L, C)``, ``(B, L, C)`` carry ``C``"""
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32:
+        raise ValueError(f"weights must be an fp32 tensor, got {getattr(weights, 'dtype', type(weights))}")
+    if weights.dim() not in (1, 2, 3):
+        raise ValueError(f"weights must be (L,), (B, L), (L, C), (1, L, C) or (B, L, C), got {tuple(weights.shape)}")
+    if weights.device != device:
+        raise ValueError(f"weights is on {weights.device}, the call on {device}")
+    # two axes: (L, C) when the first one is the query axis, else (B, L); a shape that reads both ways is refused
+    if weights.dim() == 2 and weights.shape[0] == len_q and tuple(weights.shape) == (batch, len_q):
+        raise ValueError(f"weights {tuple(weights.shape)} reads as (L, C) and as (B, L) for a batch of {batch} and len_q = {len_q}: "
+                         f"pass (1, L, C) or (B, L, 1)")
+    one_channel = weights.dim() == 1 or (weights.dim() == 2 and weights.shape[0] != len_q)
+    if one_channel:
+        weights = weights.unsqueeze(-1)          # a view: the row stride stays what it was
+    if weights.dim() == 3 and weights.shape[0] not in (1, batch):
+        raise ValueError(f"weights: {weights.shape[0]} batch entries for a batch of {batch} (1 or {batch})")
+    if weights.shape[-2] != len_q:
+        raise ValueError(f"weights: {weights.shape[-2]} rows, the call has len_q = {len_q}")
+    nch = weights.shape[-1]
+    if nch < 1 or nch > _lib.IR_RECEIVED_MAX_CHANNELS:
+        raise ValueError(f"weights: {nch} channels, expected 1 ... {_lib.IR_RECEIVED_MAX_CHANNELS} (call again for more)")
+    if not one_channel and weights.stride(-1) != 1:
+        raise ValueError(f"weights: last-axis stride {weights.stride(-1)}, expected 1")
+    si = weights.stride(-2) if len_q > 1 else nch
+    sb = weights.stride(0) if weights.dim() == 3 and weights.shape[0] == batch and batch > 1 else 0
+    if si < nch or sb < 0:
+        raise ValueError(f"weights: row stride {si} must be >= {nch} channels and the batch stride {sb} >= 0")
+    return weights, sb, si, nch
+
+
+@_on_tensor_device
+def attn_received(q, k_self, ref_k, lse, weights=None, *, heads: int, scale: float, include_self: bool = True, reduce: str = "none",
+                  q_prescaled: bool = False, batch_invariant: bool = False) -> torch.Tensor:
+    """The attention every key RECEIVES from the query rows, from the LSE of the fused forward, without the ``(B, H, Lq, Lkv)``
+    tensor (``ir_attn_received``): ``einsum('bhij,bic->bhjc', attention_probs, weights)`` - with ``weights=None`` one channel of
+    ones, ``attention_probs.sum(dim=-2)[..., None]``.  The adjoint of :func:`attn_transfer`.
+
+    ``weights``: ``None`` or an fp32 device tensor over the query axis - ``(L, C)``, ``(1, L, C)`` (one payload for the whole
+    batch) or ``(B, L, C)``, ``C <= 8``, last-axis stride 1; ``(L,)`` / ``(B, L)`` are one channel.  A tensor of two axes is
+    ``(L, C)`` when its first axis has ``len_q`` entries and ``(B, L)`` otherwise; one that reads both ways (``B == len_q``) is
+    refused: pass three axes.  Its row and batch strides are passed through, never copied (an expanded batch axis is stride 0).  Returns fp32 ``(B, H, Lkv, C)`` with
+    ``reduce="none"``, ``(B, Lkv, C)`` with ``"head_mean"`` - bit for bit ``((R_0 + R_1) + ...) * (1/H)`` of the per-head result -
+    over the packed key axis ``[self (iff include_self)] ++ ref 0 ++ ... ++ ref N-1``
+    (:func:`instantrestore_amd.attn_maps.received_maps` cuts it into pictures, ``keep_from_received`` into a ``keep`` mask for
+    :func:`compact_refs`).  Every term is one fused multiply-add in a fixed order that follows ``len_q`` and ``reduce`` only: a
+    one-hot channel at row ``i`` IS that row's fp32 probabilities (what :func:`attn_rows` rounds to q's dtype), ``None`` IS a
+    channel of ones.  ``q_prescaled`` as in :func:`attn_probs`.  Batch invariant by construction; ``batch_invariant`` is accepted
+    and changes nothing."""
+    if reduce not in RECEIVED_REDUCE:
+        raise ValueError(f"reduce must be one of {sorted(RECEIVED_REDUCE)}, got {reduce!r}")
+    args, q, B, Lq, lkv, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant)
+    args.tuning = 0   # one kernel: the A/B hook of the forward does not apply
+    if weights is None:
+        wptr, sb, si, nch = None, 0, 1, 1
+    else:
+        weights, sb, si, nch = _received_weights(weights, B, Lq, q.device)
+        wptr = weights.data_ptr()
+    recv = torch.empty((B, heads, lkv, nch) if reduce == "none" else (B, lkv, nch), dtype=torch.float32, device=q.device)
+    _lib.check(_lib.lib().ir_attn_received(C.byref(args), wptr, sb, si, nch, RECEIVED_REDUCE[reduce], recv.data_ptr(), _stream()),
+               "ir_attn_received")
+    return recv
+
+
 @_on_tensor_device
 def adain_stats(v_self: torch.Tensor, ref_v: torch.Tensor, *, heads: int, eps: float = ADAIN_EPS):
     """AdaIN as a per-(b, n, head, channel) affine ``x*a + b`` (``ir_adain_stats``).
