@@ -451,7 +451,10 @@ def _readout_case(ops, arena, key, dtype):
             elif entry == "segment_mass":
                 edges = [0, Lq] + [Lq + (n + 1) * Lr for n in range(N)]
                 m_ref = np.stack([p_ref[..., a:b].sum(-1) for a, b in zip(edges[:-1], edges[1:])], axis=-1)
-                assert np.abs(w - m_ref).max() <= 2e-3                     # the bound of test_gpu_probs.test_segment_mass
+                import lse_bounds as LB                                    # the bound of test_gpu_probs.test_segment_mass
+                keys = LB.pack_keys(data["ks"], data["kr"], True)
+                sc = LB.row_scale(data["q"], keys, SCALE, LB.oracle_lse_and_mass(_np64(data["q"]), keys, H, SCALE))
+                LB.check_mass(w, m_ref.reshape(w.shape), sc, f"{key} {entry} {dtype}")
             elif entry == "rows_none":
                 assert np.abs(w - picked).max() <= TR.TOL[dtype]
             elif entry == "rows_head_mean":

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN_MANIFEST
+from lse_bounds import check_lse, pack_keys, q_rounded_like_tuning_11, row_scale
 from parity_bounds import check_before_rounding, check_parity
 from oracle import shared_attn_oracle as O
 
@@ -116,13 +117,15 @@ def test_core_parity(ops, case, dtype, variant):
         ops.set_attn_variant(prev)
     # peaky cases (q, k x 2.5: logits of +-10 ... 30): the rounding of the exponent itself shows; 1.5 x the regression bound
     _check(out, ref, dtype, "shared_attention", TOL_FACTOR.get(variant, 1.0), reg_factor=1.5 if peaky else 1.0)
-    # LSE against the oracle's scores
-    qh = O.head_to_batch_dim_np(_np64(q), H)
+    # LSE against the oracle's scores, every element to tests/lse_bounds.py (variant 11 rounds Q * scale * log2(e) to 16 bit inside
+    # the kernel: its row sums are those of the equally rounded Q)
+    q_l = q_rounded_like_tuning_11(q, dtype, scale) if variant == 11 else (_np64(qs) / c2 if presc else _np64(q))
+    qh = O.head_to_batch_dim_np(q_l, H)
     ek, _ = O.extended_kv_np(_np64(k), _np64(v), _np64(rk), _np64(rv), H, False, inc)
     s = np.matmul(qh, ek.transpose(0, 2, 1)) * scale
     m = s.max(-1)
     lse_ref = (m + np.log(np.exp(s - m[..., None]).sum(-1))).reshape(B, H, Lq)
-    assert np.abs(lse.cpu().numpy() - lse_ref).max() <= 2e-3 * max(1.0, np.abs(lse_ref).max())
+    check_lse(lse, lse_ref, row_scale(q_l, pack_keys(k, rk, inc), scale, lse_ref), f"core parity {case} {dtype} variant {variant}")
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
@@ -631,7 +634,8 @@ def test_randomised_modes_every_product_kernel(ops):
         sc = np.matmul(qh, ek.transpose(0, 2, 1)) * (0.6931471805599453 if presc else 0.125)
         mx = sc.max(-1)
         lse_ref = (mx + np.log(np.exp(sc - mx[..., None]).sum(-1))).reshape(B, H, Lq)
-        assert np.abs(lse.cpu().numpy() - lse_ref).max() <= 2e-3 * max(1.0, np.abs(lse_ref).max()), what
+        sc_l = 0.6931471805599453 if presc else 0.125
+        check_lse(lse, lse_ref, row_scale(_np64(q), pack_keys(k, rk, inc), sc_l, lse_ref), what)
     print("modes sweep: kernels used", used)
 
 

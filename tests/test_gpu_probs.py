@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from lse_bounds import check_mass, oracle_lse_and_mass, pack_keys, row_scale
 from oracle import shared_attn_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -140,7 +141,8 @@ def test_rows_past_the_output_are_untouched(ops):
 @pytest.mark.parametrize("case", CASES + ODD_CASES, ids=_ids(CASES + ODD_CASES))
 def test_segment_mass(ops, case, dtype):
     """mass[b,h,i,s] = sum of row i's probabilities over segment s, fp32, summed before the 16-bit rounding: against the
-    oracle's float64 block sums (abs 2e-3: the only 16-bit quantity left is the input rounding) and rows summing to 1"""
+    oracle's float64 block sums (every element to tests/lse_bounds.py::check_mass - the LSE it reads is the forward kernel's, held
+    to the same scale: the only 16-bit quantity left is the input rounding) and rows summing to 1"""
     B, H, Lq, Ls, N, Lr, inc = case
     q, k, v, rk, rv = _case_inputs(case, dtype, seed=7)
     p_ref = _oracle_probs(q, k, v, rk, rv, H, inc)
@@ -152,7 +154,9 @@ def test_segment_mass(ops, case, dtype):
     mass = ops.attn_segment_mass(qd, kd, rkd, lse, heads=H, scale=0.125, include_self=inc)
     assert mass.shape == m_ref.shape and mass.dtype == torch.float32
     m = mass.cpu().numpy()
-    assert np.abs(m - m_ref).max() <= 2e-3, np.abs(m - m_ref).max()
+    keys = pack_keys(k, rk, inc)
+    sc = row_scale(_np64(q), keys, 0.125, oracle_lse_and_mass(_np64(q), keys, H, 0.125))
+    check_mass(m, m_ref, sc, f"segment mass {case} {dtype}")
     np.testing.assert_allclose(m.sum(-1), 1.0, atol=2e-3)
 
 
@@ -272,7 +276,10 @@ def test_segment_mass_with_prescaled_q(ops, dtype, shape):
     _, p_ref = O.shared_attention_np(_np64(qs), _np64(k), _np64(v), _np64(rk), _np64(rv), H, 0.6931471805599453, False, True, return_probs=True)
     edges = [0, L] + [L + (n + 1) * Lr for n in range(N)]
     m_ref = np.stack([p_ref[..., a:b].sum(-1) for a, b in zip(edges[:-1], edges[1:])], axis=-1)
-    assert np.abs(m_presc.cpu().numpy() - m_ref).max() <= 2e-3
+    keys = pack_keys(k, rk, True)
+    ln2 = 0.6931471805599453
+    sc = row_scale(_np64(qs), keys, ln2, oracle_lse_and_mass(_np64(qs), keys, H, ln2))
+    check_mass(m_presc, m_ref, sc, f"segment mass with pre-scaled Q {shape} {dtype}")
     # and the dump itself accepts the flag (same expression with the factor 1)
     p1 = ops.attn_probs(qs, k, rk, lse, heads=H, scale=0.125, include_self=True, q_prescaled=True)
     assert np.abs(p1.float().cpu().numpy() - p_ref).max() <= TOL[dtype]

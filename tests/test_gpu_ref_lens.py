@@ -2,8 +2,8 @@
 ``ops.compact_refs``): the RAGGED forms of the software-pipelined 32-row kernel against the float64 helper oracle
 (``key_bias_oracle.biased_attention_np`` with ``-inf`` on every key behind a count - tests/test_ref_lens_cpu.py shows that this IS the
 attention over the truncated references) on identical 16-bit-rounded inputs, held to ``parity_bounds.check_parity`` with its default
-factors; the LSE to 2e-3 * max(1, |lse|) and the masses to 2e-3 absolute, the bounds tests/test_gpu_key_bias.py holds the same
-kernel family to.
+factors; every element of the LSE and of the masses to tests/lse_bounds.py (fp32 accuracy at the row's own scale), the bounds
+tests/test_gpu_key_bias.py holds the same kernel family to.
 
 What can go wrong and is looked at: the item's tile count and where a K/V-range piece starts (inside a later reference, nowhere at
 all), the descriptor that must end at the count (NaN behind it), the step over an absent reference in both streams of the pipeline
@@ -21,6 +21,7 @@ import pytest
 import torch
 
 from key_bias_oracle import biased_attention_np
+from lse_bounds import check_lse, check_mass, pack_keys, row_scale
 from parity_bounds import check_parity
 
 pytestmark = pytest.mark.gpu
@@ -72,7 +73,7 @@ class Case:
         self.k, self.v, self.rk, self.rv = k.to(dtype), v.to(dtype), rk.to(dtype), rv.to(dtype)
         self.seg_lens = ([Ls] if inc else []) + [cap] * N
         self.lens = torch.tensor(counts, dtype=torch.int32)
-        self._dev = self._ref = None
+        self._dev = self._ref = self._scales = None
 
     def dev(self):
         if self._dev is None:
@@ -97,21 +98,30 @@ class Case:
                                             use_adain=self.adain, train_input=self.inc, seg_lens=self.seg_lens)
         return self._ref
 
+    def scales(self):
+        """tests/lse_bounds.py::row_scale of every (b, h, row) of the oracle's call, once per case"""
+        if self._scales is None:
+            bias = _tail_bias(self.B, self.Ls if self.inc else 0, self.cap, self.counts)
+            self._scales = row_scale(self.q_true, pack_keys(self.k, self.rk, self.inc), SCALE, self.oracle()[1], bias=bias)
+        return self._scales
 
-def _check(case, got, what, ref=None):
-    """out, lse [, mass] of a call against the oracle"""
+
+def _check(case, got, what, ref=None, bias=None):
+    """out, lse [, mass] of a call against the oracle (``ref`` with the ``bias`` it was computed with, or the case's own): the
+    output to parity_bounds, every element of the LSE and of the masses to lse_bounds"""
     ro, rl, rm = case.oracle() if ref is None else ref
     err = check_parity(got[0], ro, case.dtype, what)
-    gl = got[1].cpu().numpy().astype(np.float64)
     live = np.isfinite(rl)
-    assert np.array_equal(np.isneginf(gl), ~live), f"{what}: lse = -inf exactly on the rows without a key"
-    e = np.abs(gl[live] - rl[live]) / np.maximum(1.0, np.abs(rl[live]))
-    assert e.size == 0 or e.max() <= 2e-3, f"{what}: LSE off by {e.max():.2e} (relative to max(1, |lse|))"
+    if ref is None:
+        sc = case.scales()
+    else:
+        sc = row_scale(case.q_true, pack_keys(case.k, case.rk, case.inc), SCALE, rl, bias=bias)
+    check_lse(got[1], rl, sc, what)              # every element; -inf exactly on the rows without a key
     if len(got) > 2:
         m = got[2].cpu().numpy().astype(np.float64)
         assert np.isfinite(m).all(), what
         lives = live[..., None] & np.ones_like(m, dtype=bool)
-        assert np.abs(m - rm).max() <= 2e-3, f"{what}: masses off by {np.abs(m - rm).max():.2e}"
+        check_mass(m, rm, sc, what)
         assert np.abs(m.sum(-1)[live] - 1.0).max(initial=0.0) <= 1e-5, f"{what}: the masses of a row sum to 1"
         assert np.all(m[~lives] == 0.0), f"{what}: a row without keys has no mass"
         off = 1 if case.inc else 0
@@ -436,10 +446,10 @@ def test_compacted_call_and_bias_call_meet_the_same_oracle(ops, dtype, presc, ad
     assert torch.equal(lens.cpu(), keep.sum(-1).to(torch.int32))
     case.counts = lens.cpu().tolist()                    # (what _check reads for the absent references)
     got = case.run(ops, lens=lens, rk=ck, rv=cv, aff=aff, return_lse=True, return_mass=True)
-    _check(case, got, "compacted", ref=ref)
+    _check(case, got, "compacted", ref=ref, bias=bias.numpy().astype(np.float64))
     biased = ops.shared_attention(q, k, v, rk, rv, heads=case.H, scale=SCALE, include_self=True, adain=aff, q_prescaled=presc,
                                   key_bias=bias.cuda(), return_lse=True, return_mass=True)
-    _check(case, biased, "bias call with the same mask", ref=ref)
+    _check(case, biased, "bias call with the same mask", ref=ref, bias=bias.numpy().astype(np.float64))
 
 
 # ---- processor ----------------------------------------------------------------------------------------------------------------

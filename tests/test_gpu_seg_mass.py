@@ -4,8 +4,8 @@ to, without the tensor and without a second pass over Q and K.
 
 The forward kernels store the cumulative log-sum-exp at every segment boundary of their K/V walk and a row-sized kernel turns the
 differences into masses.  Checked here: against the float64 oracle's block sums of the probability matrix on identical
-16-bit-rounded inputs (abs 2e-3, the bound of tests/test_gpu_probs.py::test_segment_mass: the inputs' rounding is the only 16-bit
-quantity on the way), against the second-pass kernel ``ir_attn_segment_mass`` (abs 1e-4: same fp32 arithmetic, another summation
+16-bit-rounded inputs (every element to tests/lse_bounds.py::check_mass, fp32 accuracy at the row's own scale: the inputs' rounding
+is the only 16-bit quantity on the way and the oracle sees the same rounded inputs), against the second-pass kernel ``ir_attn_segment_mass`` (abs 1e-4: same fp32 arithmetic, another summation
 order), rows summing to 1, the attention output BIT-identical to the launch without the by-product, with and without the AdaIN
 fold, the self segment, pre-scaled Q, ragged segment lengths, zero-filled references closed analytically (``valid_refs``) and the
 K/V-range pieces of the remainder split (the cfg-2 shapes of both kernels)."""
@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from oracle import shared_attn_oracle as O
+from lse_bounds import check_mass, oracle_lse_and_mass, pack_keys, row_scale
 from parity_bounds import check_parity
 
 pytestmark = pytest.mark.gpu
@@ -113,7 +114,9 @@ def test_by_product_mass_against_the_oracle(ops, case, dtype, adain, presc):
     assert mass.dtype == torch.float32 and tuple(mass.shape) == m_ref.shape
     m = mass.cpu().numpy()
     assert np.isfinite(m).all()
-    assert np.abs(m - m_ref).max() <= 2e-3, np.abs(m - m_ref).max()
+    keys = pack_keys(k, rk, inc)
+    sc = row_scale(_np64(q), keys, oracle_scale, oracle_lse_and_mass(_np64(q), keys, H, oracle_scale))
+    check_mass(m, m_ref, sc, f"by-product masses {case} {dtype} adain {adain} presc {presc}")     # every element, tests/lse_bounds.py
     assert np.abs(m.sum(-1) - 1.0).max() <= 1e-5                       # the differences telescope
     assert m.min() >= -1e-6
     second = ops.attn_segment_mass(qd, kd, rkd, lse, heads=H, scale=scale, include_self=inc, q_prescaled=presc)
@@ -150,9 +153,11 @@ def test_mass_with_zero_filled_references_closed_analytically(ops, dtype, inc, a
     kw = dict(heads=H, scale=0.125, include_self=inc, adain=aff)
     walked = ops.shared_attention(qd, kd, vd, rkd, rvd, return_mass=True, **kw)
     closed = ops.shared_attention(qd, kd, vd, rkd, rvd, return_mass=True, valid_refs=vt, **kw)
+    keys = pack_keys(k, rk, inc)
+    sc = row_scale(_np64(q), keys, 0.125, oracle_lse_and_mass(_np64(q), keys, H, 0.125))
     for out, mass in (walked, closed):
         m = mass.cpu().numpy()
-        assert np.abs(m - m_ref).max() <= 2e-3, np.abs(m - m_ref).max()
+        check_mass(m, m_ref, sc, f"zero-filled references {dtype} inc {inc} adain {adain}")
         assert np.abs(m.sum(-1) - 1.0).max() <= 1e-5
         check_parity(out, out_ref, dtype, "seg_mass launch output")
     assert float((walked[1] - closed[1]).abs().max()) <= 1e-5

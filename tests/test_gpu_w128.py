@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle import shared_attn_oracle as O
+from lse_bounds import check_lse, check_lse_pair, oracle_lse_and_mass, pack_keys, row_scale
 from parity_bounds import check_before_rounding, check_parity
 
 pytestmark = pytest.mark.gpu
@@ -66,15 +67,21 @@ def test_w128_parity(case, dtype):
     rows = torch.unique(torch.tensor([r % Lq for r in (0, 1, 31, 32, 63, 64, 127, 128, 255, 511, 512, Lq // 2, Lq - 2, Lq - 1)]
                                      + np.random.default_rng(Lq).integers(0, Lq, 24).tolist()))
     f = lambda t: None if t is None else t.float().cpu()
+    keys = pack_keys(k, rk, inc)
     for b in sorted({0, B - 1}):
         ref = O.shared_attention_port(q_eff[b:b + 1, rows.cuda()].cpu(), f(k[b:b + 1]), f(v[b:b + 1]),
                                       None if rk is None else f(rk[b:b + 1]), None if rv is None else f(rv[b:b + 1]), H, 0.125,
                                       use_adain=ad, train_input=inc)
         check_parity(out[b:b + 1, rows.cuda()], ref.numpy(), dtype, f"w128 {case} identity {b}", reg_factor=1.5 if peaky else 1.0)
-    # the 64-row kernel on the same call: same result within both kernels' error, LSE equal
+        # its LSE against float64 on the same rows, every element to tests/lse_bounds.py
+        qr, kb = q_eff[b:b + 1, rows.cuda()].double(), keys[b:b + 1]
+        lse_ref = oracle_lse_and_mass(qr, kb, H, 0.125)
+        check_lse(lse[b:b + 1, :, rows.cuda()], lse_ref, row_scale(qr, kb, 0.125, lse_ref), f"w128 {case} identity {b}: LSE")
+    # the 64-row kernel on the same call: same result within both kernels' error, LSE equal to fp32 accuracy
     out64, lse64 = _run(ops, qs, k, v, rk, rv, H, inc, aff, variant=13, return_lse=True)
     assert float((out.float() - out64.float()).abs().max()) <= 2 * (8e-3 if dtype == torch.bfloat16 else 1e-3) * max(1.0, float(out64.float().abs().max()))
-    assert float((lse - lse64).abs().max()) <= 2e-3 * max(1.0, float(lse64.abs().max()))
+    # (every row: each side within its bound of the truth - the sum of the two bounds, at the row's own scale)
+    check_lse_pair(lse, lse64, row_scale(q_eff, keys, 0.125, lse64), f"w128 {case}: 128-row against 64-row LSE")
     # bit-identical from launch to launch
     out2 = _run(ops, qs, k, v, rk, rv, H, inc, aff)
     assert torch.equal(out, out2)
