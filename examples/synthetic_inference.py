@@ -54,6 +54,13 @@ def main(argv=None):
     ap.add_argument("--matches", action="store_true",
                     help="one more frame that leaves the best-matching token of every reference behind for every query token "
                          "(attention_match): prints, per shared layer, the mean best probability per reference and where the best matches lie")
+    ap.add_argument("--topk", type=int, default=None, metavar="K",
+                    help="one more frame that leaves the K best tokens of every reference behind for every query token (attention_topk, "
+                         "K = 1 ... 8): prints, per shared layer and reference, the mean ambiguity (runner-up / best, the ratio test) and the "
+                         "mean share of the reference's attention its K best keys carry")
+    ap.add_argument("--prune-topk", action="store_true",
+                    help="with --topk: prints the fraction of reference tokens that are among the K best of any query token "
+                         "(attn_maps.keep_from_topk, a keep mask for ops.compact_refs)")
     ap.add_argument("--transfer", action="store_true",
                     help="one more frame that leaves the attention-weighted mean position inside every reference behind for every query "
                          "token (attention_transfer with the coordinate payload): prints, per shared layer and reference, the mean soft "
@@ -77,6 +84,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.prune is not None and not args.received:
         ap.error("--prune chooses its tokens from the attention they received: give --received with it")
+    if args.prune_topk and args.topk is None:
+        ap.error("--prune-topk chooses its tokens from the K best keys: give --topk K with it")
 
     import __graft_entry__ as ge
     from face_replace.models.attn_processors import register_attention_processor, register_attention_processor_kv_unet
@@ -268,6 +277,36 @@ def main(argv=None):
                       f"share of tokens whose best match lies in each reference {fmt(share)}")
                 assert int(ri.min()) >= 0 and int(ri.max()) < tokens and int(y.max()) < side_len and 0 <= int(xq.min()) and int(xq.max()) < side_len
                 assert float(prob.min()) > 0 and float(prob.sum(-1).max()) <= 1.0 + 8e-3 and abs(float(share.sum()) - 1) < 1e-5
+        # One best key cannot tell one sharp peak from two equal ones (two eyes, two brows, rows of teeth).  Each shared layer leaves
+        # (index, prob) of the K best keys of every segment behind - int32 / fp32 (B, L, [self?] + N, K), rank 0 being the match
+        # above - and the segment masses of the same launch say how much of a reference's attention those K keys carry.
+        if args.topk is not None:
+            from instantrestore_amd.attn_maps import keep_from_topk, match_ambiguity, topk_coverage
+            K = int(args.topk)
+            shared = sorted((p for p in unet.attn_processors.values() if getattr(p, "self_attn_idx", None) is not None),
+                            key=lambda p: p.self_attn_idx)
+            for p in shared:
+                p.attention_topk_index, p.attention_topk_k, p.save_attention_mass = "all", K, True
+            unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1),
+                 cross_attention_kwargs={"ref_keys": ck, "ref_values": cv, "ref_stats": cs})
+            fmt = lambda m: " ".join(f"{v:.4f}" for v in m.tolist())
+            for p in shared:
+                (index, prob), p.attention_topk_index = p.attention_topk, None
+                mass, p.save_attention_mass = p.attention_mass.mean(dim=1), False       # (B, L, S): of the head mean
+                first = int(p.train_input)                                       # column of reference 0
+                tokens = ck[p.self_attn_idx].shape[2]
+                cover = topk_coverage(prob, mass)[..., first:]                   # (B, L, N)
+                line = f"shared layer {p.self_attn_idx}: top-{K} {tuple(index.shape)}"
+                if K >= 2:
+                    line += f"; mean ambiguity per reference {fmt(match_ambiguity(prob)[..., first:].mean(dim=(0, 1)))}"
+                line += f"; mean coverage of the {K} best keys per reference {fmt(cover.mean(dim=(0, 1)))}"
+                if args.prune_topk:
+                    keep = keep_from_topk(index, N, tokens, bool(p.train_input))     # (B, N, tokens) bool
+                    line += f"; fraction of reference tokens keep_from_topk keeps {float(keep.float().mean()):.4f}"
+                    assert keep.shape == (B, N, tokens) and bool(keep.any(-1).all())
+                print(line)
+                assert int(index[..., :min(K, tokens)].min()) >= 0 and int(index.max()) < tokens
+                assert float(cover.min()) > 0 and float(cover.max()) <= 1 and bool((prob[..., :-1] >= prob[..., 1:]).all())
         # Where in each reference does every token of the degraded face look, to a fraction of a token?  The payload holds the
         # (y, x) of every key; each shared layer leaves (sums, mass) of the head-mean attention behind - fp32 (B, L, [self?] + N, 2)
         # and (B, L, [self?] + N) - and soft_match_field divides: the expected position inside every segment, its displacement

@@ -509,6 +509,42 @@ int ir_attn_received(const ir_shared_attn_args* args, const float* weights, int6
                      int32_t reduce, float* recv, void* stream);
 
 /*
+ * ir_attn_topk (opt-in) - the k best keys of every K/V segment for a caller-chosen set of query tokens, without the probability
+ * matrix: ir_attn_match with ranks.
+ *
+ * Replaces `torch.topk(attention_probs[..., segment], k)` per segment s of the column order above ([self (iff INCLUDE_SELF)] ++
+ * ref 0 ++ ... ++ ref N-1, S = include_self + N): the runner-up of a match (the ratio test - a face repeats its structure, and
+ * one probability cannot tell one sharp peak from two equal ones), the few best hypotheses of a token, the share of a segment's
+ * attention that its k best keys carry - at resolutions where the dump cannot be formed.  Same args as ir_attn_rows /
+ * ir_attn_match (q, the K pointers or the K table, lse; v_*, adain_*, out, valid_refs, seg_mass and workspace are ignored - every
+ * reference is walked - and `tuning` must be 0; IR_FLAG_Q_PRESCALED: same rule; IR_FLAG_BATCH_INVARIANT: accepted, inert) plus
+ *   row_index, n_rows   exactly as for ir_attn_match: duplicates are rows like any other; an index outside [0, len_q) gives
+ *              index = -1, prob = 0 in every rank and is never used as an address.  Read by the kernel when it runs: a replayed
+ *              hipGraph follows in-place updates of it (and of the pointer tables).
+ *   k          1 ... IR_TOPK_MAX
+ *   reduce     IR_MATCH_PER_HEAD   index int32 (B, H, n_rows, S, k), prob fp32 (B, H, n_rows, S, k), over the fp32
+ *                                  p = exp2(fma(<q[idx[b,r]], k_j>, scale*log2(e), -lse[b,h,idx[b,r]]*log2(e))) - the value ir_attn_probs and
+ *                                  ir_attn_rows round to `dtype`, so prob rounded to `dtype` holds the k largest values of their row segment
+ *              IR_MATCH_HEAD_MEAN  index int32 (B, n_rows, S, k), prob fp32 (B, n_rows, S, k), over the head mean formed as
+ *                                  IR_ROWS_HEAD_MEAN forms it ((sum over heads, ascending, of the fp32 p) * (1/H)) - bit for bit a
+ *                                  stable descending sort of ir_attn_rows' head-mean row segment
+ *   index, prob  contiguous, 4-byte aligned.  Rank t of a (row, segment) holds the t-th key of the segment under the TOTAL order
+ *              (p descending, key ascending): among equal p the lower key comes first.  index counts from 0 inside its segment.
+ *              A segment with fewer than k keys fills the ranks len ... k - 1 with index = -1, prob = 0.
+ * Bit for bit (part of the interface): rank 0 IS ir_attn_match of the same call, index and prob, in both forms.
+ * Bound: K read once per group of 96 rows (ceil(n_rows / 96) * B * H * Lkv * 128 bytes) and 2 k numbers per (row, segment)
+ * written; no workspace, no atomics, one launch; asynchronous and capturable.  One wave walks a whole segment for up to 96
+ * rows, so every output element has one writer and one order; the cut follows len_self, len_ref, n_refs, n_rows, k and reduce
+ * only: the call is batch invariant with or without IR_FLAG_BATCH_INVARIANT.  Any segment length.
+ * Refused: a key_bias or ref_lens block (IR_ERR_UNSUPPORTED, as for the other read-outs), tuning != 0; IR_ERR_INVALID_ARG: NULL
+ * args / row_index / index / prob / lse, n_rows outside 1 ... len_q; IR_ERR_UNSUPPORTED: another reduce, a misaligned row_index /
+ * index / prob, k outside 1 ... IR_TOPK_MAX, more work items than ir_attn_match accepts (2^31 - 4).
+ */
+#define IR_TOPK_MAX 8
+int ir_attn_topk(const ir_shared_attn_args* args, const int32_t* row_index, int32_t n_rows, int32_t k, int32_t reduce,
+                 int32_t* index, float* prob, void* stream);
+
+/*
  * ir_adain_stats - per-(b, n, channel) AdaIN affine from token statistics.
  *
  * Replaces the statistics half of adain() (attn_processors.py:9-10) and of its call site

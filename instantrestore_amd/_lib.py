@@ -25,6 +25,7 @@ IR_TRANSFER_PER_HEAD, IR_TRANSFER_HEAD_MEAN = 0, 1   # the `reduce` argument of 
 IR_TRANSFER_MAX_CHANNELS = 8
 IR_RECEIVED_PER_HEAD, IR_RECEIVED_HEAD_MEAN = 0, 1   # the `reduce` argument of ir_attn_received
 IR_RECEIVED_MAX_CHANNELS = 8
+IR_TOPK_MAX = 8   # the largest `k` of ir_attn_topk (its `reduce` argument takes IR_MATCH_*)
 IR_LIN_BATCH_INVARIANT = 16   # ABI v10: the kernel selector of ir_linear_fwd_ex / ir_linear_fwd_stats_ex / ir_linear_kernel_for_ex
 
 i32, i64, f32, u32, vp = C.c_int32, C.c_int64, C.c_float, C.c_uint32, C.c_void_p
@@ -102,6 +103,7 @@ SYMBOLS = {
     "ir_attn_match": (C.c_int, [C.POINTER(SharedAttnArgs), vp, i32, i32, vp, vp, vp]),
     "ir_attn_transfer": (C.c_int, [C.POINTER(SharedAttnArgs), vp, i64, i64, i32, vp, i32, i32, vp, vp, vp]),
     "ir_attn_received": (C.c_int, [C.POINTER(SharedAttnArgs), vp, i64, i64, i32, i32, vp, vp]),
+    "ir_attn_topk": (C.c_int, [C.POINTER(SharedAttnArgs), vp, i32, i32, i32, vp, vp, vp]),
     "ir_adain_stats_workspace_bytes": (C.c_size_t, [i32, i32, i32, i32, i32]),
     "ir_adain_stats": (C.c_int, [i32, i32, i32, i32, i32, i32, vp, i64, i64, i64, vp, i64, i64, i64, i64,
                                  f32, vp, vp, vp, C.c_size_t, vp]),

@@ -8,7 +8,9 @@ ever computed.  ``match_coordinates`` / ``match_field`` turn the key indices of 
 the per-key payloads of ``ops.attn_transfer`` / ``SharedAttnProcessor.attention_transfer_payload`` and ``soft_match_field`` reads
 its sums back as expected positions: the soft form of ``match_field``.  ``received_maps`` / ``keep_from_received`` read the per-key
 sums of ``ops.attn_received`` / ``SharedAttnProcessor.attention_received``: pictures per segment, and a ``keep`` mask for
-``ops.compact_refs``."""
+``ops.compact_refs``.  ``topk_coordinates`` / ``match_ambiguity`` / ``topk_coverage`` / ``keep_from_topk`` read the ranks of
+``ops.attn_topk`` / ``SharedAttnProcessor.attention_topk``: positions per rank, the ratio test, the share of a segment's attention
+its k best keys carry, and the per-query ``keep`` mask."""
 import numpy as np
 
 
@@ -216,3 +218,84 @@ def keep_from_received(recv, len_self: int, n_refs: int, len_ref: int, include_s
     keep = torch.zeros(score.shape, dtype=torch.bool, device=score.device)
     keep.scatter_(-1, order[..., :count], True)
     return keep
+
+
+def topk_coordinates(index, side: int):
+    """``index`` of ``ops.attn_topk`` / ``SharedAttnProcessor.attention_topk`` (``(..., S, k)``; the token inside its segment,
+    row-major on a ``side x side`` grid) -> ``(y, x)`` per rank, two int64 arrays of ``index``'s shape on its device.  ``-1`` (a row
+    index out of range, or a rank beyond the segment's keys) stays ``-1`` in both.  This is :func:`match_coordinates` on the wider
+    shape: index arithmetic only, nothing is read back from the device."""
+    return _divmod_side(index, side)
+
+
+def match_ambiguity(prob):
+    """the ratio test on ``prob`` of ``ops.attn_topk`` (``(..., S, k)``, ``k >= 2``): ``prob[..., 1] / prob[..., 0]``, the runner-up
+    over the best, in ``[0, 1]`` - 0 for one sharp peak, 1 for two equal ones (a match that may flip between them).  0 where the
+    best is 0 or there is no second key (its ``prob`` is 0).  Torch tensor on either device or anything NumPy takes; ``k < 2``:
+    ``ValueError``."""
+    if prob.shape[-1] < 2:
+        raise ValueError(f"match_ambiguity needs the runner-up: k >= 2, got prob of shape {tuple(prob.shape)}")
+    best, second = prob[..., 0], prob[..., 1]
+    if hasattr(prob, "detach"):
+        import torch
+        return torch.where(best > 0, second / torch.where(best > 0, best, torch.ones_like(best)), torch.zeros_like(best))
+    best, second = np.asarray(best), np.asarray(second)
+    return np.where(best > 0, second / np.where(best > 0, best, 1), 0 * best)
+
+
+def topk_coverage(prob, mass):
+    """the share of every segment's attention that its k best keys carry: ``prob.sum(-1) / mass``, clamped to ``[0, 1]``, 0 where
+    the mass is 0.  ``prob`` ``(..., S, k)`` of ``ops.attn_topk``; ``mass`` ``(..., S)``: the segment masses of
+    ``shared_attention(return_mass=True)`` gathered to the same rows - for a head-mean ``prob`` that mass averaged over the heads.
+    Near 1: the attention inside the segment is as sparse as k keys (and ``compact_refs`` may prune hard).  Torch tensors on either
+    device or anything NumPy takes."""
+    if tuple(prob.shape[:-1]) != tuple(mass.shape):
+        raise ValueError(f"topk_coverage: prob {tuple(prob.shape)} needs mass of shape {tuple(prob.shape[:-1])}, got {tuple(mass.shape)}")
+    if hasattr(prob, "detach"):
+        import torch
+        mass = torch.as_tensor(mass).to(device=prob.device, dtype=prob.dtype)
+        share = prob.sum(-1) / torch.where(mass > 0, mass, torch.ones_like(mass))
+        return torch.where(mass > 0, share, torch.zeros_like(share)).clamp(0, 1)
+    prob, mass = np.asarray(prob), np.asarray(mass)
+    return np.clip(np.where(mass > 0, prob.sum(-1) / np.where(mass > 0, mass, 1), 0 * mass), 0, 1)
+
+
+def keep_from_topk(index, n_refs: int, len_ref: int, include_self: bool, min_prob=None, prob=None):
+    """a ``keep`` mask for ``ops.compact_refs`` from the ranks of ``ops.attn_topk`` on a warm-up frame: bool ``(B, N, len_ref)``,
+    ``True`` on every reference token that is among the k best keys of ANY chosen row (and head) - the per-query counterpart of
+    :func:`keep_from_received`, which ranks the tokens by what all rows together give them.  ``index`` ``(B, R, S, k)`` or
+    ``(B, H, R, S, k)``, ``S = include_self + n_refs``; the self segment and ``-1`` entries are ignored.  With ``min_prob`` (and the
+    ``prob`` of the same call) only ranks with ``prob >= min_prob`` count.  Torch tensors stay on their device; NumPy arrays give a
+    NumPy mask."""
+    if int(n_refs) < 1:
+        raise ValueError("keep_from_topk needs n_refs >= 1")
+    first = 1 if include_self else 0
+    if len(index.shape) not in (4, 5) or index.shape[-2] != first + int(n_refs):
+        raise ValueError(f"index must be (B, R, S, k) or (B, H, R, S, k) with S = {first + int(n_refs)}, got {tuple(index.shape)}")
+    if (min_prob is None) != (prob is None):
+        raise ValueError("keep_from_topk: min_prob and prob go together")
+    if prob is not None and tuple(prob.shape) != tuple(index.shape):
+        raise ValueError(f"prob {tuple(prob.shape)} must have index's shape {tuple(index.shape)}")
+    B, N, L = index.shape[0], int(n_refs), int(len_ref)
+    torch_in = hasattr(index, "detach")
+    if torch_in:
+        import torch
+        idx = index.detach().long()[..., first:, :]
+        ok = (idx >= 0) & (idx < L)
+        if prob is not None:
+            ok = ok & (torch.as_tensor(prob).to(idx.device)[..., first:, :] >= min_prob)
+        idx = torch.movedim(idx, -2, 1).reshape(B, N, -1)        # (B, N, every row, head and rank)
+        ok = torch.movedim(ok, -2, 1).reshape(B, N, -1)
+        # a dropped entry goes to an extra column that is cut off again
+        keep = torch.zeros((B, N, L + 1), dtype=torch.bool, device=idx.device)
+        keep.scatter_(-1, torch.where(ok, idx, torch.full_like(idx, L)), True)
+        return keep[..., :L]
+    idx = np.asarray(index).astype(np.int64)[..., first:, :]
+    ok = (idx >= 0) & (idx < L)
+    if prob is not None:
+        ok = ok & (np.asarray(prob)[..., first:, :] >= min_prob)
+    idx = np.moveaxis(idx, -2, 1).reshape(B, N, -1)
+    ok = np.moveaxis(ok, -2, 1).reshape(B, N, -1)
+    keep = np.zeros((B, N, L + 1), dtype=bool)
+    np.put_along_axis(keep, np.where(ok, idx, L), True, axis=-1)
+    return keep[..., :L]

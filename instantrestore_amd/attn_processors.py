@@ -564,6 +564,18 @@ class SharedAttnProcessor(nn.Module):
         self.attention_received_weights = None
         self.attention_received_reduce = "head_mean"
         self.attention_received = None
+        # opt-in (plain attributes like ``attention_match_index``): ``attention_topk_index`` - ``"all"`` (every query token) or an integer
+        # tensor ``(R,)`` / ``(B, R)`` - makes every call of a shared layer leave ``attention_topk = (index, prob)``: per K/V segment the
+        # ``attention_topk_k`` (1 ... 8, default 4) largest probabilities of each chosen token and the keys, counted inside their segment,
+        # that attain them, under (probability descending, key ascending) (``ir_attn_topk``) - ``torch.topk`` over a segment's columns of
+        # ``attention_probs`` without the (B, H, L, Lkv) tensor; rank 0 is ``attention_match``.  ``attention_topk_reduce``: "head_mean" -
+        # int32 / fp32 (B, R, S, k), of the head mean; "none" - (B, H, R, S, k), per head.  ``attn_maps.topk_coordinates`` /
+        # ``match_ambiguity`` / ``topk_coverage`` / ``keep_from_topk`` read the result.  Uses the LSE of the same attention call.
+        # ``None``: off, nothing changes.
+        self.attention_topk_index = None
+        self.attention_topk_k = 4
+        self.attention_topk_reduce = "head_mean"
+        self.attention_topk = None
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                 ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None, ref_weights=None, ref_token_keep=None,
@@ -637,6 +649,9 @@ class SharedAttnProcessor(nn.Module):
                 if getattr(self, "attention_received_weights", None) is not None:
                     raise NotImplementedError("ref_lens together with attention_received_weights: ir_attn_received would walk the tails "
                                               "behind the counts (follow-up)")
+                if getattr(self, "attention_topk_index", None) is not None:
+                    raise NotImplementedError("ref_lens together with attention_topk_index: ir_attn_topk would walk the tails behind the "
+                                              "counts (follow-up)")
                 if self.use_adain and cstats is None:
                     raise ValueError("ref_lens with use_adain needs ref_stats: the AdaIN content statistics are those of the full reference, "
                                      "taken before compaction - computing them here would read the packed rows and whatever lies behind them")
@@ -686,8 +701,11 @@ class SharedAttnProcessor(nn.Module):
         received_weights = getattr(self, "attention_received_weights", None) if shared else None
         if isinstance(received_weights, str) and received_weights != "ones":          # before anything is launched
             raise ValueError(f"attention_received_weights must be None, \"ones\" or an fp32 tensor, got {received_weights!r}")
+        topk_index = getattr(self, "attention_topk_index", None) if shared else None
+        if isinstance(topk_index, str) and topk_index != "all":                       # before anything is launched
+            raise ValueError(f"attention_topk_index must be None, \"all\" or an integer tensor, got {topk_index!r}")
         want_lse = want_probs or rows_index is not None or match_index is not None or transfer_payload is not None or \
-            received_weights is not None
+            received_weights is not None or topk_index is not None
         kw = {"q_prescaled": True} if presc else {}
         kw.update(_bi_kw(bi))
         if shared and ref_valid is not None:
@@ -715,6 +733,9 @@ class SharedAttnProcessor(nn.Module):
             if received_weights is not None:
                 raise NotImplementedError("attention_received_weights together with an attention mask, ref_weights or ref_token_keep: "
                                           "ir_attn_received does not take the key bias yet (follow-up)")
+            if topk_index is not None:
+                raise NotImplementedError("attention_topk_index together with an attention mask, ref_weights or ref_token_keep: "
+                                          "ir_attn_topk does not take the key bias yet (follow-up)")
             kw["key_bias"] = bias
         # the masses are a by-product of the attention launch itself (ABI v9 ``seg_mass``: the kernels hold the row sums at every
         # segment boundary): no second pass over Q and K
@@ -756,6 +777,12 @@ class SharedAttnProcessor(nn.Module):
                                                          heads=attn.heads, scale=0.6931471805599453 if presc else attn.scale,
                                                          include_self=include_self,
                                                          reduce=getattr(self, "attention_received_reduce", "head_mean"), **_bi_kw(bi))
+        if topk_index is not None:
+            # the k best keys of every segment for the chosen tokens ("all": every token) from the same LSE
+            self.attention_topk = _ops.attn_topk(query, key, ref_k, lse, None if isinstance(topk_index, str) else topk_index,
+                                                 k=getattr(self, "attention_topk_k", 4), heads=attn.heads,
+                                                 scale=0.6931471805599453 if presc else attn.scale, include_self=include_self,
+                                                 reduce=getattr(self, "attention_topk_reduce", "head_mean"), **_bi_kw(bi))
         if want_probs:
             # (B, H, L, Lkv), columns [self?] ++ ref0 ++ ... ++ refN-1, in the compute dtype.  A pre-scaled query
             # already carries scale * log2(e): its scores are exponents, ln 2 turns them into the logits of the LSE

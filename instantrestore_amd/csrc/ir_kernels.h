@@ -238,6 +238,15 @@ constexpr int64_t kReceivedMaxItems = 0x7fffffffLL - 3;
 int64_t ir_attn_received_items(const AttnKParams& p, int channels, int reduce);
 hipError_t ir_launch_attn_received(const AttnKParams& p, int dtype, const float* weights, int64_t w_sb, int64_t w_si, int channels, int reduce,
                                    float* recv, hipStream_t s);
+// attn_topk.hip: per K/V segment, the `k` largest probabilities of each of `n_rows` chosen query tokens and the keys that attain
+// them under (probability descending, key ascending) (index int32, prob fp32: (B, H, n_rows, S, k) per head, (B, n_rows, S, k) of
+// the head mean); `reduce` is IR_MATCH_* of the public header, rank 0 is attn_match.hip's result.  The items of ir_attn_match: one
+// wave each, at most kTopkMaxItems
+constexpr int kTopkMax = 8;
+constexpr int64_t kTopkMaxItems = kMatchMaxItems;
+int64_t ir_attn_topk_items(const AttnKParams& p, int n_rows, int reduce);
+hipError_t ir_launch_attn_topk(const AttnKParams& p, int dtype, const int32_t* row_index, int n_rows, int k, int reduce, int32_t* index, float* prob,
+                               hipStream_t s);
 hipError_t ir_launch_adain_stats(const AdainKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_token_stats(const AdainKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_adain_stats_cached(const AdainKParams& p, int dtype, hipStream_t s);

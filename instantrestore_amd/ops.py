@@ -813,6 +813,43 @@ def attn_match(q, k_self, ref_k, lse, rows=None, *, heads: int, scale: float, in
     return index, prob
 
 
+@_on_tensor_device
+def attn_topk(q, k_self, ref_k, lse, rows=None, *, k: int, heads: int, scale: float, include_self: bool = True, reduce: str = "none",
+              q_prescaled: bool = False, batch_invariant: bool = False):
+    """The ``k`` best keys of every K/V segment for the query tokens ``rows`` from the LSE of the fused forward, without the
+    ``(B, H, Lq, Lkv)`` tensor (``ir_attn_topk``): ``torch.topk(attention_probs[..., segment], k)`` per segment of
+    ``[self (iff include_self)] ++ ref 0 ++ ... ++ ref N-1``, :func:`attn_match` with ranks.
+
+    ``k``: ``1 ... IR_TOPK_MAX`` (8).  ``rows``: ``None`` - every query token, in order - or an integer tensor ``(R,)`` / ``(B, R)`` as
+    for :func:`attn_match` (duplicates are rows like any other; a device index outside ``[0, Lq)`` gives ``index = -1``,
+    ``prob = 0`` in every rank).  Returns ``(index, prob)``: int32 and fp32, ``(B, H, R, S, k)`` with ``reduce="none"`` (per head),
+    ``(B, R, S, k)`` with ``"head_mean"`` (of the head mean as :func:`attn_rows` forms it).  Rank ``t`` holds the ``t``-th key of the
+    segment under (fp32 probability descending, key ascending) - equal probabilities come in ascending key order - counted inside
+    its segment; a segment with fewer than ``k`` keys ends in ``index = -1``, ``prob = 0``.  Rank 0 is :func:`attn_match` of the same
+    call bit for bit; the head-mean ranks are a stable descending sort of :func:`attn_rows`' head-mean row segment.
+    :func:`instantrestore_amd.attn_maps.topk_coordinates`, ``match_ambiguity``, ``topk_coverage`` and ``keep_from_topk`` read the
+    result.  ``q_prescaled`` as in :func:`attn_probs`.  Batch invariant by construction; ``batch_invariant`` is accepted and changes
+    nothing."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _lib.IR_TOPK_MAX:
+        raise ValueError(f"k must be an integer in 1 ... {_lib.IR_TOPK_MAX}, got {k!r}")
+    if reduce not in MATCH_REDUCE:
+        raise ValueError(f"reduce must be one of {sorted(MATCH_REDUCE)}, got {reduce!r}")
+    args, q, B, Lq, _, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant)
+    args.tuning = 0   # one kernel: the A/B hook of the forward does not apply
+    if rows is None:
+        idx = torch.arange(Lq, dtype=torch.int32, device=q.device).unsqueeze(0).expand(B, -1).contiguous()
+    else:
+        idx = _row_index(rows, B, Lq, q.device)
+    R = idx.shape[1]
+    nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
+    shape = (B, heads, R, nseg, k) if reduce == "none" else (B, R, nseg, k)
+    index = torch.empty(shape, dtype=torch.int32, device=q.device)
+    prob = torch.empty(shape, dtype=torch.float32, device=q.device)
+    _lib.check(_lib.lib().ir_attn_topk(C.byref(args), idx.data_ptr(), R, k, MATCH_REDUCE[reduce], index.data_ptr(), prob.data_ptr(), _stream()),
+               "ir_attn_topk")
+    return index, prob
+
+
 TRANSFER_REDUCE = {"none": _lib.IR_TRANSFER_PER_HEAD, "head_mean": _lib.IR_TRANSFER_HEAD_MEAN}
 
 
