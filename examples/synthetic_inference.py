@@ -42,6 +42,9 @@ class StandInVAE(nn.Module):
         return torch.tanh(nn.functional.interpolate(y, scale_factor=8, mode="nearest"))
 
 
+MUTUAL_MIN_FACTOR = 2.0     # --mutual: a reference token is kept when some query token gives it this many times the uniform probability 1 / Lkv
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--identities", type=int, default=2)
@@ -65,6 +68,10 @@ def main(argv=None):
                     help="one more frame that leaves the attention-weighted mean position inside every reference behind for every query "
                          "token (attention_transfer with the coordinate payload): prints, per shared layer and reference, the mean soft "
                          "displacement, the mean mass and how often the rounded expected position is attention_match's hard match")
+    ap.add_argument("--mutual", action="store_true",
+                    help="one more frame that leaves, beside attention_match, the best query token of every key behind (attention_key_match): "
+                         "prints, per shared layer and reference, the share of query tokens whose match survives the mutual check "
+                         "(attn_maps.mutual_matches) and the share of reference tokens attn_maps.keep_from_key_match keeps at one threshold")
     ap.add_argument("--received", action="store_true",
                     help="one more frame that leaves, for every token of every reference, the attention it receives from the whole "
                          "degraded face behind (attention_received, unweighted): prints, per shared layer, the received mass per reference")
@@ -307,6 +314,36 @@ def main(argv=None):
                 print(line)
                 assert int(index[..., :min(K, tokens)].min()) >= 0 and int(index.max()) < tokens
                 assert float(cover.min()) > 0 and float(cover.max()) <= 1 and bool((prob[..., :-1] >= prob[..., 1:]).all())
+        # Every query token has a best key in every reference - occluded skin, hair and background too, where it is the best of a bad
+        # lot.  The mutual (cycle) check keeps the pair (token i, key j) only if j is the best key of i AND i is the best token of
+        # j: each shared layer leaves the best query token of every key behind (attention_key_match, the column maximum of the
+        # attention without the (B, H, L, Lkv) tensor) beside attention_match of the same frame.  The column maximum itself is a keep
+        # rule for reference tokens: those that at least one query token looks at with MUTUAL_MIN_FACTOR times the uniform
+        # probability 1 / Lkv or more.
+        if args.mutual:
+            from instantrestore_amd.attn_maps import keep_from_key_match, mutual_matches
+            shared = sorted((p for p in unet.attn_processors.values() if getattr(p, "self_attn_idx", None) is not None),
+                            key=lambda p: p.self_attn_idx)
+            for p in shared:
+                p.attention_match_index, p.attention_match_reduce, p.attention_key_match_reduce = "all", "head_mean", "head_mean"
+            unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1),
+                 cross_attention_kwargs={"ref_keys": ck, "ref_values": cv, "ref_stats": cs})
+            fmt = lambda m: " ".join(f"{v:.4f}" for v in m.tolist())
+            for p in shared:
+                (index, _), p.attention_match_index = p.attention_match, None
+                (key_index, key_prob), p.attention_key_match_reduce = p.attention_key_match, None
+                first = int(p.train_input)                                       # column of reference 0
+                tokens = ck[p.self_attn_idx].shape[2]
+                mutual = mutual_matches(index, key_index, tokens, N, tokens, bool(p.train_input))       # (B, L, S) bool
+                min_prob = MUTUAL_MIN_FACTOR / key_prob.shape[-1]
+                keep = keep_from_key_match(key_prob, tokens, N, tokens, bool(p.train_input), min_prob=min_prob)
+                print(f"shared layer {p.self_attn_idx}: key match {tuple(key_index.shape)}; share of query tokens whose match survives the "
+                      f"mutual check per reference {fmt(mutual[..., first:].float().mean(dim=(0, 1)))}; share of reference tokens some "
+                      f"query token looks at with p >= {min_prob:.2e} {fmt(keep.float().mean(dim=(0, 2)))}")
+                assert mutual.shape == index.shape and keep.shape == (B, N, tokens)
+                assert int(key_index.min()) >= 0 and int(key_index.max()) < index.shape[1] and float(key_prob.min()) >= 0
+                # a key has ONE best token: at most one surviving pair per key
+                assert int(mutual[..., first:].sum(dim=1).max()) <= tokens
         # Where in each reference does every token of the degraded face look, to a fraction of a token?  The payload holds the
         # (y, x) of every key; each shared layer leaves (sums, mass) of the head-mean attention behind - fp32 (B, L, [self?] + N, 2)
         # and (B, L, [self?] + N) - and soft_match_field divides: the expected position inside every segment, its displacement

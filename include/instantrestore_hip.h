@@ -545,6 +545,43 @@ int ir_attn_topk(const ir_shared_attn_args* args, const int32_t* row_index, int3
                  int32_t* index, float* prob, void* stream);
 
 /*
+ * ir_attn_key_match (opt-in) - per key, the largest attention probability over ALL query rows and the query row that attains it,
+ * without the probability matrix: the column maximum of P.
+ *
+ * Replaces `attention_probs.max(dim=-2)` / `.argmax(dim=-2)`: which token of the degraded face looks hardest at every token of
+ * every reference.  ir_attn_match answers for every query row - occluded skin, hair and background included - and its answer there
+ * is the best of a bad lot; correspondence pipelines filter it with the MUTUAL (cycle) check: keep the pair (i, j) only if j is the
+ * best key of row i (ir_attn_match) AND i is the best row of key j (this call).  The column maximum is also a keep rule for
+ * reference tokens: a token that at least one query token looks at strongly.  Same args as ir_attn_received (q, the K pointers or
+ * the K table, lse; v_*, adain_*, out, valid_refs, seg_mass and workspace are ignored - every reference is walked - and `tuning`
+ * must be 0; IR_FLAG_Q_PRESCALED: same rule; IR_FLAG_BATCH_INVARIANT: accepted, inert) plus
+ *   reduce     IR_MATCH_PER_HEAD   index int32 (B, H, Lkv), prob fp32 (B, H, Lkv): prob[b,h,j] = max over i = 0 .. len_q - 1 of
+ *                                  the fp32 p[b,h,i,j] = exp2(fma(<q_i, k_j>, scale*log2(e), -lse[b,h,i]*log2(e))) - the value
+ *                                  ir_attn_probs and ir_attn_rows round to `dtype`
+ *              IR_MATCH_HEAD_MEAN  index int32 (B, Lkv), prob fp32 (B, Lkv): the maximum over i of the head mean formed as
+ *                                  IR_ROWS_HEAD_MEAN forms it ((sum over heads, ascending, of the fp32 p) * (1.0f / (float)H))
+ *   index, prob  contiguous, 4-byte aligned; j on the PACKED extended key axis [self (iff INCLUDE_SELF)] ++ ref 0 ++ ... ++ ref N-1
+ *              (the axis of ir_attn_received's recv).  index is the LOWEST query row that attains prob: the order is TOTAL (p
+ *              descending, then row ascending).  A column whose probabilities are all 0 gives index 0, prob 0.
+ * Bit for bit (part of the interface):
+ *   - prob IS the maximum of the fp32 values named above and index its first row.  The order is total, so the result does not
+ *     depend on the order in which the rows meet: unlike its siblings, which have to state their summation order, this call has
+ *     none to state;
+ *   - IR_MATCH_HEAD_MEAN: prob is the column maximum of ir_attn_rows' IR_ROWS_HEAD_MEAN rows (all rows), index the first row of it;
+ *   - rows of the padding to a whole 32-row block never take part: they are not compared, index is always in [0, len_q), and
+ *     nothing behind row len_q - 1 of q or lse is read; keys past the end of a segment are never written.
+ * Bound: K read once per head (head mean: once per 32-row block, from L2); Q and lse once per group of 64 keys; 2 * Lkv numbers
+ * written per (head,) batch entry; no workspace, no atomics, one launch; asynchronous and capturable.  One wave walks the whole
+ * query axis for its keys, so every output element has one writer; the cut follows len_self, len_ref, n_refs and reduce only.
+ * Every offset is formed in 64 bits; the pointer tables are read by the kernel when it runs: a replayed hipGraph follows in-place
+ * updates of them.  Any segment length, any len_q.
+ * Checked in this order, after the checks of the args block: IR_ERR_INVALID_ARG: NULL index, NULL prob, NULL lse;
+ * IR_ERR_UNSUPPORTED: another reduce, a misaligned index / prob, more than 2^31 - 4 work items.  Refused with the args block: a
+ * key_bias or ref_lens block (IR_ERR_UNSUPPORTED, as for the other read-outs), tuning != 0.
+ */
+int ir_attn_key_match(const ir_shared_attn_args* args, int32_t reduce, int32_t* index, float* prob, void* stream);
+
+/*
  * ir_adain_stats - per-(b, n, channel) AdaIN affine from token statistics.
  *
  * Replaces the statistics half of adain() (attn_processors.py:9-10) and of its call site

@@ -104,6 +104,7 @@ SYMBOLS = {
     "ir_attn_transfer": (C.c_int, [C.POINTER(SharedAttnArgs), vp, i64, i64, i32, vp, i32, i32, vp, vp, vp]),
     "ir_attn_received": (C.c_int, [C.POINTER(SharedAttnArgs), vp, i64, i64, i32, i32, vp, vp]),
     "ir_attn_topk": (C.c_int, [C.POINTER(SharedAttnArgs), vp, i32, i32, i32, vp, vp, vp]),
+    "ir_attn_key_match": (C.c_int, [C.POINTER(SharedAttnArgs), i32, vp, vp, vp]),
     "ir_adain_stats_workspace_bytes": (C.c_size_t, [i32, i32, i32, i32, i32]),
     "ir_adain_stats": (C.c_int, [i32, i32, i32, i32, i32, i32, vp, i64, i64, i64, vp, i64, i64, i64, i64,
                                  f32, vp, vp, vp, C.c_size_t, vp]),

@@ -10,7 +10,9 @@ its sums back as expected positions: the soft form of ``match_field``.  ``receiv
 sums of ``ops.attn_received`` / ``SharedAttnProcessor.attention_received``: pictures per segment, and a ``keep`` mask for
 ``ops.compact_refs``.  ``topk_coordinates`` / ``match_ambiguity`` / ``topk_coverage`` / ``keep_from_topk`` read the ranks of
 ``ops.attn_topk`` / ``SharedAttnProcessor.attention_topk``: positions per rank, the ratio test, the share of a segment's attention
-its k best keys carry, and the per-query ``keep`` mask."""
+its k best keys carry, and the per-query ``keep`` mask.  ``mutual_matches`` / ``mutual_match_field`` / ``keep_from_key_match`` read
+``ops.attn_key_match`` / ``SharedAttnProcessor.attention_key_match``: the mutual (cycle) check of ``attn_match``'s pairs, the field
+through it, and the max-based ``keep`` mask."""
 import numpy as np
 
 
@@ -299,3 +301,92 @@ def keep_from_topk(index, n_refs: int, len_ref: int, include_self: bool, min_pro
     keep = np.zeros((B, N, L + 1), dtype=bool)
     np.put_along_axis(keep, np.where(ok, idx, L), True, axis=-1)
     return keep[..., :L]
+
+
+def _segment_starts(len_self: int, n_refs: int, len_ref: int, include_self: bool):
+    """the first column of every segment of ``[self (iff include_self)] ++ ref 0 ++ ... ++ ref N-1`` and the axis' length"""
+    off = int(len_self) if include_self else 0
+    starts = ([0] if include_self else []) + [off + n * int(len_ref) for n in range(int(n_refs))]
+    if not starts:
+        raise ValueError("empty key axis: include_self is False and n_refs is 0")
+    return starts, off + int(n_refs) * int(len_ref)
+
+
+def mutual_matches(match_index, key_index, len_self: int, n_refs: int, len_ref: int, include_self: bool, rows=None):
+    """the mutual (cycle) check of a correspondence: keep the pair (row ``i``, key ``j``) only if ``j`` is the best key of row
+    ``i`` in its segment AND ``i`` is the best row of key ``j``.  ``match_index`` ``(B, R, S)`` or ``(B, H, R, S)`` is the ``index``
+    of ``ops.attn_match`` / ``SharedAttnProcessor.attention_match`` (keys counted inside their segments), ``key_index`` ``(B, Lkv)``
+    or ``(B, H, Lkv)`` the ``index`` of ``ops.attn_key_match`` / ``SharedAttnProcessor.attention_key_match`` of the SAME call and form
+    (query rows, over the packed key axis).  ``rows``: the query tokens ``match_index`` was computed for - ``(R,)``, ``(B, R)`` or
+    ``None`` / ``"all"`` for ``arange(R)``.  Returns a bool tensor of ``match_index``'s shape: ``True`` where
+    ``key_index[.., col0_s + match_index[.., r, s]] == rows[r]`` with ``col0_s`` the first column of segment ``s``; entries with
+    ``match_index < 0`` (or a negative row) are ``False``.  Torch tensors on either device; index arithmetic and one gather, no
+    host sync."""
+    import torch
+    starts, lkv = _segment_starts(len_self, n_refs, len_ref, include_self)
+    if match_index.dim() not in (3, 4) or match_index.shape[-1] != len(starts):
+        raise ValueError(f"match_index must be (B, R, S) or (B, H, R, S) with S = {len(starts)}, got {tuple(match_index.shape)}")
+    if key_index.dim() != match_index.dim() - 1 or key_index.shape[-1] != lkv or tuple(key_index.shape[:-1]) != tuple(match_index.shape[:-2]):
+        raise ValueError(f"key_index must be {tuple(match_index.shape[:-2]) + (lkv,)} (the same call and form as match_index), got "
+                         f"{tuple(key_index.shape)}")
+    dev = match_index.device
+    R, S = match_index.shape[-2], match_index.shape[-1]
+    if rows is None or isinstance(rows, str):
+        rows = torch.arange(R, device=dev)
+    else:
+        rows = torch.as_tensor(rows).to(dev).long()
+    if rows.shape[-1] != R or rows.dim() not in (1, 2):
+        raise ValueError(f"rows must be ({R},) or (B, {R}), got {tuple(rows.shape)}")
+    if rows.dim() == 2 and match_index.dim() == 4:        # (B, R) against (B, H, R, S)
+        rows = rows[:, None]
+    rows = rows[..., None]                                 # over the segments
+    idx = match_index.detach().long()
+    ok = (idx >= 0) & (rows >= 0)
+    col = torch.as_tensor(starts, device=dev) + idx.clamp(min=0)
+    col = col.clamp(max=lkv - 1)                           # (an index past its segment cannot come from attn_match; never an address)
+    back = torch.gather(key_index.detach().long().to(dev), -1, col.reshape(tuple(idx.shape[:-2]) + (R * S,))).reshape(idx.shape)
+    return ok & (back == rows)
+
+
+def mutual_match_field(match_index, key_index, rows, side: int, len_self: int, n_refs: int, len_ref: int, include_self: bool):
+    """:func:`match_field` over the pairs that pass :func:`mutual_matches`: ``(dy, dx, mutual)``.  Where the check fails both
+    displacements are 0 - exactly as :func:`match_field` marks an entry out of range - and ``mutual`` is ``False`` there: read the
+    field through the mask.  Arguments as for the two functions; ``rows`` ``None`` / ``"all"`` for ``arange(R)``."""
+    import torch
+    rr = None if rows is None or isinstance(rows, str) else rows
+    mutual = mutual_matches(match_index, key_index, len_self, n_refs, len_ref, include_self, rows=rr)
+    dy, dx = match_field(match_index, rows, side)
+    zero = torch.zeros_like(dy)
+    return torch.where(mutual, dy, zero), torch.where(mutual, dx, zero), mutual
+
+
+def keep_from_key_match(prob, len_self: int, n_refs: int, len_ref: int, include_self: bool, *, min_prob=None, keep_fraction=None):
+    """a ``keep`` mask for ``ops.compact_refs`` from the column maxima of ``ops.attn_key_match`` on a warm-up frame: bool
+    ``(B, N, len_ref)``.  The max-based counterpart of :func:`keep_from_received`: that one keeps tokens that collect a lot of
+    attention in total, this one tokens that AT LEAST ONE query token looks at strongly - which a small but decisive feature (an eye
+    corner) survives.  ``prob`` ``(B, Lkv)`` (the head-mean form) or ``(B, H, Lkv)`` (per head: reduced by a maximum over the
+    heads).  Exactly one rule: ``min_prob`` - ``True`` where the score is ``>= min_prob``; ``keep_fraction`` - per reference the
+    ``ceil(keep_fraction * len_ref - 1e-9)`` tokens with the largest score, at least 1 and at most ``len_ref``, ties to the LOWER
+    token index (the count and the order of :func:`keep_from_received`).  Everything stays on ``prob``'s device."""
+    import math
+
+    import torch
+    starts, lkv = _segment_starts(len_self, n_refs, len_ref, include_self)
+    if int(n_refs) < 1:
+        raise ValueError("keep_from_key_match needs n_refs >= 1")
+    if prob.dim() not in (2, 3) or prob.shape[-1] != lkv:
+        raise ValueError(f"prob must be (B, Lkv) or (B, H, Lkv) with Lkv = {lkv}, got {tuple(prob.shape)}")
+    if (min_prob is None) == (keep_fraction is None):
+        raise ValueError("keep_from_key_match takes exactly one of min_prob and keep_fraction")
+    score = prob.amax(dim=1) if prob.dim() == 3 else prob
+    off = lkv - int(n_refs) * int(len_ref)
+    score = score[:, off:lkv].reshape(score.shape[0], int(n_refs), int(len_ref))
+    if min_prob is not None:
+        return score >= min_prob
+    if not 0.0 < float(keep_fraction) <= 1.0:
+        raise ValueError(f"keep_fraction must lie in (0, 1], got {keep_fraction}")
+    count = min(int(len_ref), max(1, math.ceil(float(keep_fraction) * int(len_ref) - 1e-9)))
+    order = torch.sort(-score, dim=-1, stable=True).indices                 # descending, equal scores in ascending token order
+    keep = torch.zeros(score.shape, dtype=torch.bool, device=score.device)
+    keep.scatter_(-1, order[..., :count], True)
+    return keep

@@ -576,6 +576,15 @@ class SharedAttnProcessor(nn.Module):
         self.attention_topk_k = 4
         self.attention_topk_reduce = "head_mean"
         self.attention_topk = None
+        # opt-in (plain attributes like ``attention_received_weights``): ``attention_key_match_reduce`` - "head_mean" or "none" - makes
+        # every call of a shared layer leave ``attention_key_match = (index, prob)``: per key of the packed key axis the largest
+        # probability over ALL query tokens and the LOWEST query token that attains it (``ir_attn_key_match``) -
+        # ``attention_probs.max(-2)`` / ``.argmax(-2)`` without the (B, H, L, Lkv) tensor.  "head_mean" - int32 / fp32 (B, Lkv), of the
+        # head mean; "none" - (B, H, Lkv), per head.  With ``attention_match_index = "all"`` and the same reduce,
+        # ``attn_maps.mutual_matches`` / ``mutual_match_field`` keep the pairs that pass the mutual check; ``keep_from_key_match`` turns
+        # ``prob`` into a ``keep`` mask for ``ops.compact_refs``.  Uses the LSE of the same attention call.  ``None``: off, nothing changes.
+        self.attention_key_match_reduce = None
+        self.attention_key_match = None
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                 ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None, ref_weights=None, ref_token_keep=None,
@@ -652,6 +661,9 @@ class SharedAttnProcessor(nn.Module):
                 if getattr(self, "attention_topk_index", None) is not None:
                     raise NotImplementedError("ref_lens together with attention_topk_index: ir_attn_topk would walk the tails behind the "
                                               "counts (follow-up)")
+                if getattr(self, "attention_key_match_reduce", None) is not None:
+                    raise NotImplementedError("ref_lens together with attention_key_match_reduce: ir_attn_key_match would walk the tails "
+                                              "behind the counts (follow-up)")
                 if self.use_adain and cstats is None:
                     raise ValueError("ref_lens with use_adain needs ref_stats: the AdaIN content statistics are those of the full reference, "
                                      "taken before compaction - computing them here would read the packed rows and whatever lies behind them")
@@ -704,8 +716,11 @@ class SharedAttnProcessor(nn.Module):
         topk_index = getattr(self, "attention_topk_index", None) if shared else None
         if isinstance(topk_index, str) and topk_index != "all":                       # before anything is launched
             raise ValueError(f"attention_topk_index must be None, \"all\" or an integer tensor, got {topk_index!r}")
+        key_match_reduce = getattr(self, "attention_key_match_reduce", None) if shared else None
+        if key_match_reduce is not None and key_match_reduce not in ("none", "head_mean"):    # before anything is launched
+            raise ValueError(f"attention_key_match_reduce must be None, \"none\" or \"head_mean\", got {key_match_reduce!r}")
         want_lse = want_probs or rows_index is not None or match_index is not None or transfer_payload is not None or \
-            received_weights is not None or topk_index is not None
+            received_weights is not None or topk_index is not None or key_match_reduce is not None
         kw = {"q_prescaled": True} if presc else {}
         kw.update(_bi_kw(bi))
         if shared and ref_valid is not None:
@@ -736,6 +751,9 @@ class SharedAttnProcessor(nn.Module):
             if topk_index is not None:
                 raise NotImplementedError("attention_topk_index together with an attention mask, ref_weights or ref_token_keep: "
                                           "ir_attn_topk does not take the key bias yet (follow-up)")
+            if key_match_reduce is not None:
+                raise NotImplementedError("attention_key_match_reduce together with an attention mask, ref_weights or ref_token_keep: "
+                                          "ir_attn_key_match does not take the key bias yet (follow-up)")
             kw["key_bias"] = bias
         # the masses are a by-product of the attention launch itself (ABI v9 ``seg_mass``: the kernels hold the row sums at every
         # segment boundary): no second pass over Q and K
@@ -783,6 +801,11 @@ class SharedAttnProcessor(nn.Module):
                                                  k=getattr(self, "attention_topk_k", 4), heads=attn.heads,
                                                  scale=0.6931471805599453 if presc else attn.scale, include_self=include_self,
                                                  reduce=getattr(self, "attention_topk_reduce", "head_mean"), **_bi_kw(bi))
+        if key_match_reduce is not None:
+            # the best query token of every key over all query tokens, same LSE
+            self.attention_key_match = _ops.attn_key_match(query, key, ref_k, lse, heads=attn.heads,
+                                                           scale=0.6931471805599453 if presc else attn.scale,
+                                                           include_self=include_self, reduce=key_match_reduce, **_bi_kw(bi))
         if want_probs:
             # (B, H, L, Lkv), columns [self?] ++ ref0 ++ ... ++ refN-1, in the compute dtype.  A pre-scaled query
             # already carries scale * log2(e): its scores are exponents, ln 2 turns them into the logits of the LSE

@@ -6,7 +6,7 @@ HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="${IR_OUT:-${HERE}/../libinstantrestore_hip.so}"
 BUILD_DIR="${IR_BUILD_DIR:-build}"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
-SRCS=(linear_tiled.hip shared_attn_fwd.hip shared_attn_fwd_pipe.hip shared_attn_fwd_pipe_bias.hip shared_attn_fwd_pipe_ragged.hip shared_attn_fwd_w64.hip shared_attn_fwd_w128.hip shared_attn_fwd_w128_forms.hip attn_probs.hip attn_rows.hip attn_match.hip attn_transfer.hip attn_received.hip attn_topk.hip adain.hip compact_refs.hip image_io.hip linear_skinny.hip bench_hooks.hip c_abi.hip)
+SRCS=(linear_tiled.hip shared_attn_fwd.hip shared_attn_fwd_pipe.hip shared_attn_fwd_pipe_bias.hip shared_attn_fwd_pipe_ragged.hip shared_attn_fwd_w64.hip shared_attn_fwd_w128.hip shared_attn_fwd_w128_forms.hip attn_probs.hip attn_rows.hip attn_match.hip attn_transfer.hip attn_received.hip attn_topk.hip attn_key_match.hip adain.hip compact_refs.hip image_io.hip linear_skinny.hip bench_hooks.hip c_abi.hip)
 cd "${HERE}"
 # the hand-placed instruction stream of the 128-row attention kernel is generated (committed; regenerated here so it cannot go stale)
 python3 "${HERE}/w128/gen.py"
@@ -24,6 +24,7 @@ for s in "${SRCS[@]}"; do
   [[ "$s" == attn_probs.hip || "$s" == attn_rows.hip || "$s" == attn_match.hip || "$s" == attn_transfer.hip ]] && extra+=(-mllvm -amdgpu-mfma-vgpr-form)
   [[ "$s" == attn_received.hip ]] && extra+=(-mllvm -amdgpu-mfma-vgpr-form)   # the same for the key-side read-out
   [[ "$s" == attn_topk.hip ]] && extra+=(-mllvm -amdgpu-mfma-vgpr-form)       # and for the top-k read-out
+  [[ "$s" == attn_key_match.hip ]] && extra+=(-mllvm -amdgpu-mfma-vgpr-form)  # and for the column maximum
   # round 6: the 128-rows-per-wave kernel (one wave per SIMD, hand-placed stream) is the default wherever the 64-row kernel was and
   # the call is in its domain: same-box sustained A/B at cfg 2's top layer 0.709 vs 0.791 ms (profiles/r6_w128_ab.txt); IR_ATTN_W128=0 restores
   [[ "$s" == shared_attn_fwd.hip ]] && extra+=(-DIR_W128_DEFAULT=${IR_W128_DEFAULT:-1})

@@ -35,7 +35,7 @@ int64_t seg_stride_limit(int32_t len, int64_t sl) {
 }
 
 // `fwd`: the call is (or describes) a launch of the attention forward, whose segment-span limit applies; the read-out entry points
-// (ir_attn_probs*, ir_attn_segment_mass, ir_attn_rows, ir_attn_match, ir_attn_transfer, ir_attn_received, ir_attn_topk) address K through 64-bit pointers and take any stride
+// (ir_attn_probs*, ir_attn_segment_mass, ir_attn_rows, ir_attn_match, ir_attn_transfer, ir_attn_received, ir_attn_topk, ir_attn_key_match) address K through 64-bit pointers and take any stride
 bool attn_block_size_ok(uint32_t n) {
   return n == sizeof(ir_shared_attn_args) || n == sizeof(ir_shared_attn_table_args) || n == sizeof(ir_shared_attn_bias_args) ||
          n == sizeof(ir_shared_attn_ragged_args);
@@ -86,7 +86,7 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
   if (a->seg_mass != nullptr && (reinterpret_cast<uintptr_t>(a->seg_mass) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "seg_mass must be 4-byte aligned");
   if (kbias != nullptr) {
     if (!fwd)
-      return fail(IR_ERR_UNSUPPORTED, "key_bias: ir_attn_probs[_ex], ir_attn_segment_mass, ir_attn_rows, ir_attn_match, ir_attn_transfer, ir_attn_received and ir_attn_topk do not take a key bias yet (their exp(s - lse) would "
+      return fail(IR_ERR_UNSUPPORTED, "key_bias: ir_attn_probs[_ex], ir_attn_segment_mass, ir_attn_rows, ir_attn_match, ir_attn_transfer, ir_attn_received, ir_attn_topk and ir_attn_key_match do not take a key bias yet (their exp(s - lse) would "
                   "leave it out); the forward's seg_mass by-product does");
     if ((reinterpret_cast<uintptr_t>(kbias) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "key_bias must be 4-byte aligned");
     if (ba->kb_sb < 0 || ba->kb_sh < 0) return fail(IR_ERR_INVALID_ARG, "key_bias strides kb_sb %lld, kb_sh %lld must be >= 0", (long long)ba->kb_sb, (long long)ba->kb_sh);
@@ -99,7 +99,7 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
   }
   if (rlens != nullptr) {
     if (!fwd)
-      return fail(IR_ERR_UNSUPPORTED, "ref_lens: ir_attn_probs[_ex], ir_attn_segment_mass, ir_attn_rows, ir_attn_match, ir_attn_transfer, ir_attn_received and ir_attn_topk do not take per-reference counts yet (they would "
+      return fail(IR_ERR_UNSUPPORTED, "ref_lens: ir_attn_probs[_ex], ir_attn_segment_mass, ir_attn_rows, ir_attn_match, ir_attn_transfer, ir_attn_received, ir_attn_topk and ir_attn_key_match do not take per-reference counts yet (they would "
                   "walk the tails behind the counts); the forward's seg_mass by-product does");
     if ((reinterpret_cast<uintptr_t>(rlens) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "ref_lens must be 4-byte aligned");
     if (a->n_refs == 0) return fail(IR_ERR_UNSUPPORTED, "ref_lens with n_refs == 0: there is no reference to count");
@@ -239,7 +239,7 @@ int launch_fwd(const ir_shared_attn_args* a, const AttnKParams& p, hipStream_t s
 }
 
 // The parameter block of a read-out of the forward's LSE (ir_attn_probs_ex, ir_attn_segment_mass, ir_attn_rows, ir_attn_match,
-// ir_attn_transfer, ir_attn_received, ir_attn_topk).
+// ir_attn_transfer, ir_attn_received, ir_attn_topk, ir_attn_key_match).
 // `single_kernel`: the name of an entry point that has one kernel and refuses a tuning value, or nullptr.  A key bias and
 // per-reference counts are refused for the whole family in build_attn_params (!fwd)
 int build_readout_params(const ir_shared_attn_args* args, AttnKParams* p, const char* single_kernel) {
@@ -531,6 +531,25 @@ int ir_attn_topk(const ir_shared_attn_args* args, const int32_t* row_index, int3
   if (ir_attn_topk_items(p, n_rows, reduce) > kTopkMaxItems) return fail(IR_ERR_UNSUPPORTED, "grid too large");
   const hipError_t e = ir_launch_attn_topk(p, args->dtype, row_index, n_rows, k, reduce, index, prob, (hipStream_t)stream);
   if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "attn_topk launch: %s", hipGetErrorString(e));
+  return IR_OK;
+}
+
+// The checks of its own arguments, in this order (the header states it): NULL index, NULL prob, NULL lse, the form, the
+// alignments, the item count
+int ir_attn_key_match(const ir_shared_attn_args* args, int32_t reduce, int32_t* index, float* prob, void* stream) {
+  AttnKParams p;
+  const int rc = build_readout_params(args, &p, "ir_attn_key_match");
+  if (rc != IR_OK) return rc;
+  if (index == nullptr) return fail(IR_ERR_INVALID_ARG, "index is NULL");
+  if (prob == nullptr) return fail(IR_ERR_INVALID_ARG, "prob is NULL");
+  if (args->lse == nullptr) return fail(IR_ERR_INVALID_ARG, "lse is NULL");
+  if (reduce != IR_MATCH_PER_HEAD && reduce != IR_MATCH_HEAD_MEAN)
+    return fail(IR_ERR_UNSUPPORTED, "reduce %d: IR_MATCH_PER_HEAD (0) or IR_MATCH_HEAD_MEAN (1)", reduce);
+  if ((reinterpret_cast<uintptr_t>(index) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "index must be 4-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(prob) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "prob must be 4-byte aligned");
+  if (ir_attn_key_match_items(p, reduce) > kKeyMatchMaxItems) return fail(IR_ERR_UNSUPPORTED, "grid too large");
+  const hipError_t e = ir_launch_attn_key_match(p, args->dtype, reduce, index, prob, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "attn_key_match launch: %s", hipGetErrorString(e));
   return IR_OK;
 }
 

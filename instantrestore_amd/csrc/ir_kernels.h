@@ -247,6 +247,13 @@ constexpr int64_t kTopkMaxItems = kMatchMaxItems;
 int64_t ir_attn_topk_items(const AttnKParams& p, int n_rows, int reduce);
 hipError_t ir_launch_attn_topk(const AttnKParams& p, int dtype, const int32_t* row_index, int n_rows, int k, int reduce, int32_t* index, float* prob,
                                hipStream_t s);
+// attn_key_match.hip: per key of the packed extended key axis, the largest probability over ALL query rows and the lowest row that
+// attains it (index int32, prob fp32: (B, H, Lkv) per head, (B, Lkv) of the head mean); `reduce` is IR_MATCH_* of the public
+// header.  One wave per item (a group of keys of one segment), at most kKeyMatchMaxItems
+constexpr int kKeyMatchPerHead = 0, kKeyMatchHeadMean = 1;
+constexpr int64_t kKeyMatchMaxItems = 0x7fffffffLL - 3;
+int64_t ir_attn_key_match_items(const AttnKParams& p, int reduce);
+hipError_t ir_launch_attn_key_match(const AttnKParams& p, int dtype, int reduce, int32_t* index, float* prob, hipStream_t s);
 hipError_t ir_launch_adain_stats(const AdainKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_token_stats(const AdainKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_adain_stats_cached(const AdainKParams& p, int dtype, hipStream_t s);

@@ -986,6 +986,35 @@ def attn_received(q, k_self, ref_k, lse, weights=None, *, heads: int, scale: flo
 
 
 @_on_tensor_device
+def attn_key_match(q, k_self, ref_k, lse, *, heads: int, scale: float, include_self: bool = True, reduce: str = "none",
+                   q_prescaled: bool = False, batch_invariant: bool = False):
+    """The query row that looks hardest at every key, from the LSE of the fused forward, without the ``(B, H, Lq, Lkv)`` tensor
+    (``ir_attn_key_match``): ``attention_probs.max(dim=-2)`` / ``.argmax(dim=-2)`` over ALL query rows.  The query-axis
+    counterpart of :func:`attn_match`, and the second half of the mutual check
+    (:func:`instantrestore_amd.attn_maps.mutual_matches`).
+
+    Returns ``(index, prob)``: int32 and fp32, ``(B, H, Lkv)`` with ``reduce="none"`` (per head), ``(B, Lkv)`` with
+    ``"head_mean"`` (of the head mean as :func:`attn_rows` forms it), over the packed key axis
+    ``[self (iff include_self)] ++ ref 0 ++ ... ++ ref N-1`` (the axis of :func:`attn_received`).  ``prob`` is the largest fp32
+    probability of the column - rounded to q's dtype it is the maximum of :func:`attn_probs` there; the head-mean ``prob`` is the
+    column maximum of :func:`attn_rows`' head-mean rows bit for bit - and ``index`` the LOWEST query row that attains it.  The
+    order (probability descending, row ascending) is total, so the result depends on no order of evaluation; a column of zeros
+    gives ``index 0``, ``prob 0``.  :func:`instantrestore_amd.attn_maps.keep_from_key_match` turns ``prob`` into a ``keep`` mask
+    for :func:`compact_refs`.  ``q_prescaled`` as in :func:`attn_probs`.  Batch invariant by construction; ``batch_invariant`` is
+    accepted and changes nothing."""
+    if reduce not in MATCH_REDUCE:
+        raise ValueError(f"reduce must be one of {sorted(MATCH_REDUCE)}, got {reduce!r}")
+    args, q, B, Lq, lkv, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant)
+    args.tuning = 0   # one kernel: the A/B hook of the forward does not apply
+    shape = (B, heads, lkv) if reduce == "none" else (B, lkv)
+    index = torch.empty(shape, dtype=torch.int32, device=q.device)
+    prob = torch.empty(shape, dtype=torch.float32, device=q.device)
+    _lib.check(_lib.lib().ir_attn_key_match(C.byref(args), MATCH_REDUCE[reduce], index.data_ptr(), prob.data_ptr(), _stream()),
+               "ir_attn_key_match")
+    return index, prob
+
+
+@_on_tensor_device
 def adain_stats(v_self: torch.Tensor, ref_v: torch.Tensor, *, heads: int, eps: float = ADAIN_EPS):
     """AdaIN as a per-(b, n, head, channel) affine ``x*a + b`` (``ir_adain_stats``).
 
