@@ -86,6 +86,10 @@ def main(argv=None):
                     help="keep a centred elliptical region of that area of every reference (e.g. 0.5): the kept tokens are packed to the "
                          "front of their segments once (ops.compact_refs) and the shared layers walk the counts (ref_lens); prints the top "
                          "shared layer's attention masses with and without")
+    ap.add_argument("--regions", action="store_true",
+                    help="one more cached frame under a per-query restriction by region labels (region_labels / region_allow): synthetic label "
+                         "pictures - a 4 x 4 grid of classes, shifted by n cells on reference n - and the rule \"own class only, self "
+                         "free\"; prints the top shared layer's attention masses with and without")
     ap.add_argument("--kv-tables", action="store_true",
                     help="one more cached frame whose reference K/V are pointer tables into the cache entries (assemble_tables: no copy)")
     args = ap.parse_args(argv)
@@ -233,6 +237,30 @@ def main(argv=None):
             for b in range(B):
                 print(f"identity {b}: mass [self?] ++ references  full {fmt(m0[b])}  |  {kept} of {ck[8].shape[2]} tokens kept: {fmt(m1[b])}")
             assert bool(torch.isfinite(zc).all()) and float((m1.sum(-1) - 1).abs().max()) < 2e-3
+        # "Eye tokens draw from eye tokens of the references, mouth from mouth, the picture itself is free": a per-QUERY restriction.
+        # Label pictures (a face parsing map; here a coarse grid of classes) and a class-by-class rule go in once; every shared layer
+        # samples the labels at its own token centres and hands the kernel one 32-bit word per query row and one small integer per
+        # key (ops.region_masks) - never a (Lq, Lkv) mask.  AdaIN is unchanged; the masses are the read-back.
+        if args.regions:
+            G, px = 4, 64
+            cell = torch.arange(px, device=dev) * G // px
+            grid = cell[:, None] * G + cell[None, :]                                       # (px, px): classes 0 .. G * G - 1
+            q_labels = grid.expand(B, px, px).contiguous()
+            ref_labels = torch.stack([torch.roll(grid, shifts=n * (px // G), dims=1) for n in range(N)]).expand(B, N, px, px).contiguous()
+            allow = torch.eye(G * G, dtype=torch.bool, device=dev)                        # own class only
+            top = [p for p in unet.attn_processors.values() if getattr(p, "self_attn_idx", None) == 8][0]
+            top.save_attention_mass = True
+            kw = {"ref_keys": ck, "ref_values": cv, "ref_stats": cs}
+            unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1), cross_attention_kwargs=kw)
+            m0 = top.attention_mass.mean(dim=(1, 2))
+            zr = unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1),
+                      cross_attention_kwargs=dict(kw, region_labels=(q_labels, ref_labels), region_allow=allow)).sample
+            m1 = top.attention_mass.mean(dim=(1, 2))
+            top.save_attention_mass = False
+            fmt = lambda m: " ".join(f"{v:.3f}" for v in m.tolist())
+            for b in range(B):
+                print(f"identity {b}: mass [self?] ++ references  unrestricted {fmt(m0[b])}  |  {G * G} classes, own class only, self free: {fmt(m1[b])}")
+            assert bool(torch.isfinite(zr).all()) and float((m1.sum(-1) - 1).abs().max()) < 2e-3
         # Where do the facial landmarks look (vis_utils.py:88-110)?  Each shared layer is told which query tokens they fall on
         # and leaves the sum of those tokens' head-mean probability rows behind - (B, Lkv) fp32, reshaped to one side x 5*side
         # picture over the degraded image and its references - instead of the (B, H, L, Lkv) tensor of save_self_attentions.

@@ -99,7 +99,7 @@ typedef enum ir_dtype { IR_DTYPE_F16 = 0, IR_DTYPE_BF16 = 1 } ir_dtype;
  */
 #define IR_ATTN_SEG_BYTES_MAX 2147483647LL
 typedef struct ir_shared_attn_args {
-  uint32_t struct_size; /* = sizeof(ir_shared_attn_args), or sizeof(ir_shared_attn_table_args) / sizeof(ir_shared_attn_bias_args) / sizeof(ir_shared_attn_ragged_args) when the block is one (below) */
+  uint32_t struct_size; /* = sizeof(ir_shared_attn_args), or sizeof(ir_shared_attn_table_args) / sizeof(ir_shared_attn_bias_args) / sizeof(ir_shared_attn_ragged_args) / sizeof(ir_shared_attn_region_args) when the block is one (below) */
   int32_t dtype;        /* ir_dtype */
   uint32_t flags;       /* IR_FLAG_* */
   int32_t batch;        /* B */
@@ -250,6 +250,47 @@ typedef struct ir_shared_attn_ragged_args {
   const int32_t* ref_lens;       /* device, int32 [B][N] rows rl_sb apart, or NULL (= the call of the shorter blocks in every respect) */
   int64_t rl_sb;                 /* elements between batch rows, >= N */
 } ir_shared_attn_ragged_args;
+
+/*
+ * Region-restricted attention: per-query masks from region labels.  A fifth block, ir_shared_attn_ragged_args with four fields
+ * appended, told apart by `struct_size` as the others are (sizeof(ir_shared_attn_region_args) = the ragged block's size + 32; every
+ * size other than the five is IR_ERR_INVALID_ARG; IR_ABI_VERSION stays 10).  Tables, key_bias and ref_lens may be NULL; q_allow and
+ * key_region may BOTH be NULL, and then the call is the call of the shorter blocks in every respect (kernel, plan, bytes).  Exactly
+ * one of them NULL is IR_ERR_INVALID_ARG.
+ *
+ *   region[b,j]  = key_region[b * kg_sb + j]      one small integer per key of the PACKED extended key axis (the axis of key_bias)
+ *   allow[b,i]   = q_allow[b * qa_sb + i]         one 32-bit word per query row: bit g set = the row may attend keys of region g
+ *   allowed(b,i,j) = region[b,j] in [0, IR_REGION_MAX - 1]  &&  ((allow[b,i] >> region[b,j]) & 1)
+ *   P[b,h,i,:]   = softmax over the allowed j of scale * <q_i, k_j>
+ *
+ * One rule for all heads.  A key whose region is outside [0, 31] belongs to nobody.  A pair that is not allowed has probability
+ * exactly 0 and never moves the row's running reference, whatever its score (the rule of a masked key of the bias).  A row with no
+ * allowed key (allow == 0, or no key of its regions present) gives out = 0 (exact zeros), lse = -inf and masses 0 - never NaN.  lse
+ * and seg_mass are over the allowed keys.  AdaIN is unchanged: the affine is an input; a region rule merely takes attention away.
+ * Both arrays are read when the kernel RUNS: a replayed hipGraph follows in-place updates.  Both are 4-byte aligned, and nothing
+ * outside the len_q / Lkv words of an entry is used.  The mask costs what a key bias costs in bytes: a dense (len_q, Lkv) bias never
+ * exists.
+ *
+ * Taken by ir_shared_attn_fwd, ir_time_shared_attn_fwd, ir_shared_attn_kernel_name, ir_shared_attn_plan and
+ * ir_shared_attn_workspace_bytes_for.  A call with regions always runs the software-pipelined 32-row kernel (its REGION form: the
+ * pre-scaled-Q form with IR_FLAG_Q_PRESCALED or IR_TUNE_PIPE32_PRESCALE_Q, the early-QK form otherwise), at every len_q.  Every tile
+ * is walked: a tile no row of a 32-row block may attend contributes zeros (skipping it is a follow-up).
+ * Accepted with it: seg_mass, lse, IR_FLAG_OUT_F32, IR_FLAG_Q_PRESCALED, AdaIN, tables, IR_FLAG_BATCH_INVARIANT, n_refs = 0.
+ * Refused (IR_ERR_UNSUPPORTED): regions with a non-NULL key_bias and regions with a non-NULL ref_lens (regions together with a bias
+ * or with counts are a follow-up); regions with valid_refs (the closed form of the zero suffix gives every row its keys); a tuning
+ * other than IR_TUNE_DEFAULT, IR_TUNE_PIPE32_PRESCALE_Q, IR_TUNE_PIPE32_EARLYQK; arrays that are not 4-byte aligned; and every
+ * read-out entry point (ir_attn_probs[_ex], ir_attn_segment_mass, ir_attn_rows, ir_attn_match, ir_attn_topk, ir_attn_transfer,
+ * ir_attn_received, ir_attn_key_match) with non-NULL arrays (their exp(s - lse) would count the pairs the forward left out).
+ * qa_sb < len_q and kg_sb < Lkv are IR_ERR_INVALID_ARG.
+ */
+#define IR_REGION_MAX 32
+typedef struct ir_shared_attn_region_args {
+  ir_shared_attn_ragged_args r;   /* r.b.t.args.struct_size = sizeof(ir_shared_attn_region_args); tables, key_bias and ref_lens may be NULL */
+  const uint32_t* q_allow;        /* device, (B, Lq) rows qa_sb apart: bit g set = the row may attend keys of region g; or NULL (both) */
+  int64_t qa_sb;                  /* elements between batch rows, >= len_q */
+  const int32_t* key_region;      /* device, (B, Lkv) over the PACKED extended key axis (the axis of key_bias), rows kg_sb apart */
+  int64_t kg_sb;                  /* >= Lkv */
+} ir_shared_attn_region_args;
 
 /* values of ir_shared_attn_args.tuning (csrc/shared_attn_fwd.hip: kAttnVariants has one row per value - kernel family, form, what
  * it takes; ir_attn_choose is the dispatch) */

@@ -19,6 +19,7 @@ IR_DTYPE_F16, IR_DTYPE_BF16 = 0, 1
 IR_FLAG_INCLUDE_SELF, IR_FLAG_Q_PRESCALED, IR_FLAG_OUT_F32 = 1, 2, 4
 IR_FLAG_BATCH_INVARIANT = 8   # ABI v10
 IR_KEY_BIAS_MASKED = -1.0e4   # a key whose bias is -inf or <= this is masked (probability exactly 0)
+IR_REGION_MAX = 32   # regions of ir_shared_attn_region_args: key_region in [0, 31], one bit of q_allow each
 IR_ROWS_NONE, IR_ROWS_HEAD_MEAN, IR_ROWS_MAP = 0, 1, 2   # the `reduce` argument of ir_attn_rows
 IR_MATCH_PER_HEAD, IR_MATCH_HEAD_MEAN = 0, 1   # the `reduce` argument of ir_attn_match
 IR_TRANSFER_PER_HEAD, IR_TRANSFER_HEAD_MEAN = 0, 1   # the `reduce` argument of ir_attn_transfer
@@ -65,6 +66,14 @@ class SharedAttnRaggedArgs(SharedAttnBiasArgs):
     counts appended - int32 ``[B][N]`` on the device, rows ``rl_sb`` elements apart"""
 
     _fields_ = [("ref_lens", vp), ("rl_sb", i64)]
+
+
+class SharedAttnRegionArgs(SharedAttnRaggedArgs):
+    """mirror of ``ir_shared_attn_region_args``: the ragged block (tables, key_bias and ref_lens may be NULL) with the region rule
+    appended - ``q_allow`` uint32 ``(B, Lq)`` rows ``qa_sb`` apart (bit g: the row may attend region g), ``key_region`` int32
+    ``(B, Lkv)`` over the packed extended key axis, rows ``kg_sb`` apart; both on the device, both or neither"""
+
+    _fields_ = [("q_allow", vp), ("qa_sb", i64), ("key_region", vp), ("kg_sb", i64)]
 
 
 class SharedAttnPlan(C.Structure):

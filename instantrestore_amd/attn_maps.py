@@ -12,7 +12,8 @@ sums of ``ops.attn_received`` / ``SharedAttnProcessor.attention_received``: pict
 ``ops.attn_topk`` / ``SharedAttnProcessor.attention_topk``: positions per rank, the ratio test, the share of a segment's attention
 its k best keys carry, and the per-query ``keep`` mask.  ``mutual_matches`` / ``mutual_match_field`` / ``keep_from_key_match`` read
 ``ops.attn_key_match`` / ``SharedAttnProcessor.attention_key_match``: the mutual (cycle) check of ``attn_match``'s pairs, the field
-through it, and the max-based ``keep`` mask."""
+through it, and the max-based ``keep`` mask.  ``token_labels`` samples an integer label picture (a face parsing map) at the token
+centres of a layer's grid: the labels ``ops.region_masks`` / the processors' ``region_labels`` take."""
 import numpy as np
 
 
@@ -140,6 +141,32 @@ def image_payload(self_image, ref_images, len_self: int, len_ref: int, include_s
     if len(parts) == 2 and (parts[0].shape[0] != parts[1].shape[0] or parts[0].shape[2] != parts[1].shape[2]):
         raise ValueError(f"image_payload: self_image and ref_images disagree on batch or channels: {tuple(self_image.shape)} vs {tuple(ref_images.shape)}")
     return torch.cat(parts, dim=1).contiguous()
+
+
+def token_labels(label_image, side: int):
+    """per-token class labels from a label picture (a face parsing map): integer ``(B, Hpx, Wpx)`` -> ``(B, side * side)``, or
+    ``(B, N, Hpx, Wpx)`` -> ``(B, N * side * side)`` (the references laid end to end, as the key axis lays them), row-major on the
+    ``side x side`` token grid - the labels ``ops.region_masks`` takes.  A label is SAMPLED, never averaged: token ``(ty, tx)`` takes
+    the pixel at its centre,
+
+        ``py = ((2 * ty + 1) * Hpx) // (2 * side)``,   ``px = ((2 * tx + 1) * Wpx) // (2 * side)``
+
+    (integer floor division; for ``Hpx = k * side`` that is ``ty * k + k // 2``, and for ``Hpx == side`` the picture itself).
+    ``Hpx, Wpx >= 1``; a picture smaller than the grid repeats pixels.  Index arithmetic on the picture's device, no sync; the dtype
+    is kept."""
+    import torch
+    img = torch.as_tensor(label_image)
+    if img.dim() not in (3, 4) or img.dtype.is_floating_point or img.dtype.is_complex or img.dtype == torch.bool:
+        raise ValueError(f"token_labels: label_image must be an integer (B, Hpx, Wpx) or (B, N, Hpx, Wpx) tensor, got {img.dtype} {tuple(img.shape)}")
+    side = int(side)
+    hpx, wpx = int(img.shape[-2]), int(img.shape[-1])
+    if side < 1 or hpx < 1 or wpx < 1:
+        raise ValueError(f"token_labels: side {side} and picture {hpx} x {wpx} must be >= 1")
+    t = torch.arange(side, device=img.device, dtype=torch.int64)
+    py = torch.div((2 * t + 1) * hpx, 2 * side, rounding_mode="floor")
+    px = torch.div((2 * t + 1) * wpx, 2 * side, rounding_mode="floor")
+    picked = img.index_select(-2, py).index_select(-1, px)          # (..., side, side)
+    return picked.reshape(img.shape[0], -1).contiguous()
 
 
 def soft_match_field(sums, mass, rows, side: int):

@@ -102,7 +102,7 @@ def _mask_bias(mask, batch: int, heads: int, lkv: int, len_self: int, shared: bo
     if mask.dim() == 3:
         if mask.shape[1] != 1:
             raise NotImplementedError(f"attention_mask {tuple(mask.shape)}: a query axis of {mask.shape[1]} - per-query masks are not supported "
-                                      "(the fused kernel takes one bias per key)")
+                                      "(the fused kernel takes one bias per key; a per-query restriction by region labels goes in as region_labels / region_allow)")
         mask = mask[:, 0]
     elif mask.dim() != 2:
         raise ValueError(f"attention_mask must be (B, Lkv), (B, 1, Lkv) or (B * H, 1, Lkv), got {tuple(mask.shape)}")
@@ -140,6 +140,56 @@ def _ref_bias_row(ref_weights, ref_token_keep, batch: int, len_self: int, n_refs
         _BIAS_ROWS.pop(next(iter(_BIAS_ROWS)))
     _BIAS_ROWS[key] = (ref_weights, ref_token_keep, row)
     return row
+
+
+# (q_allow, key_region) of ``region_labels`` / ``region_allow``, built once per (kwargs identity and version, key-axis geometry) the way
+# _BIAS_ROWS caches bias rows: the nine shared layers of a step have three geometries, so they build three pairs
+_REGION_PAIRS: dict = {}
+_REGION_PAIRS_MAX = 8
+
+
+def _labels_on_grid(labels, length: int, what: str):
+    """label pictures ``(B, [N,] Hpx, Wpx)`` or per-token labels ``(B, [N,] L)`` (the row-major picture of their own square grid) sampled
+    at the token centres of the square grid of ``length`` tokens (``attn_maps.token_labels``) -> ``(B, [N *] length)``"""
+    from . import attn_maps as _maps
+    side = _maps._square_side(length, what)
+    t = torch.as_tensor(labels)
+    pictures = 3 if what == "len_q" else 4
+    if t.dim() == pictures - 1:      # per-token labels
+        s = _maps._square_side(t.shape[-1], f"{what}: the per-token labels' length")
+        t = t.reshape(*t.shape[:-1], s, s)
+    if t.dim() != pictures:
+        raise ValueError(f"region_labels: the {'query' if pictures == 3 else 'reference'} labels must be label pictures "
+                         f"{'(B, Hpx, Wpx)' if pictures == 3 else '(B, N, Hpx, Wpx)'} or per-token labels, got {tuple(torch.as_tensor(labels).shape)}")
+    return _maps.token_labels(t, side)
+
+
+def _region_pair(region_labels, region_allow, batch: int, len_q: int, len_self: int, n_refs: int, len_ref: int,
+                 include_self: bool, device):
+    if not isinstance(region_labels, (tuple, list)) or len(region_labels) != 2:
+        raise ValueError("region_labels must be the pair (query_labels, ref_labels)")
+    if region_allow is None:
+        raise ValueError("region_labels needs region_allow: the (C, C) bool matrix or the (C,) bitmasks of ops.region_masks")
+    q_lab, r_lab = region_labels
+    ver = lambda t: (id(t), getattr(t, "_version", None))
+    key = (ver(q_lab), ver(r_lab), ver(region_allow), batch, len_q, len_self, n_refs, len_ref, include_self, str(device))
+    hit = _REGION_PAIRS.get(key)
+    if hit is not None and hit[0] is q_lab and hit[1] is r_lab and hit[2] is region_allow:
+        return hit[3]
+    ql = _labels_on_grid(q_lab, len_q, "len_q").to(device)
+    rl = _labels_on_grid(r_lab, len_ref, "len_ref").to(device)
+    if ql.shape[0] != batch or rl.shape[0] != batch or rl.shape[1] != n_refs * len_ref:
+        raise ValueError(f"region_labels: labels of {tuple(ql.shape)} query and {tuple(rl.shape)} reference tokens for a batch of {batch} with "
+                         f"{n_refs} references of {len_ref} tokens")
+    parts = [rl.to(torch.int64)]
+    if include_self:     # the self keys are this picture's own tokens: the query labels on the self grid
+        parts.insert(0, (ql if len_self == len_q else _labels_on_grid(q_lab, len_self, "len_q").to(device)).to(torch.int64))
+    pair = _ops.region_masks(ql, torch.cat(parts, dim=1), torch.as_tensor(region_allow).to(device),
+                             self_len=len_self if include_self else 0, self_free=True)    # a token always sees its own picture
+    while len(_REGION_PAIRS) >= _REGION_PAIRS_MAX:
+        _REGION_PAIRS.pop(next(iter(_REGION_PAIRS)))
+    _REGION_PAIRS[key] = (q_lab, r_lab, region_allow, pair)
+    return pair
 
 
 def _kv_source(attn, st: _Prepared) -> torch.Tensor:
@@ -424,8 +474,8 @@ class AttnProcessor(nn.Module):
                 self.ready.record(self.stream)
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
-                ref_weights=None, ref_token_keep=None, ref_lens=None):
-        # ref_weights / ref_token_keep / ref_lens: accepted and ignored (no references here), like ref_valid elsewhere
+                ref_weights=None, ref_token_keep=None, ref_lens=None, region_labels=None, region_allow=None):
+        # ref_weights / ref_token_keep / ref_lens / region_labels / region_allow: accepted and ignored (no references here), like ref_valid elsewhere
         st = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
         self.is_self_attn = encoder_hidden_states is None
         group = self.stop_after_capture
@@ -473,8 +523,8 @@ class FaceIDAttnProcessor(nn.Module):
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                 ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None, ref_weights=None, ref_token_keep=None,
-                ref_lens=None):
-        # ref_* accepted and ignored, like the reference: the host forwards ONE cross_attention_kwargs dict to every processor
+                ref_lens=None, region_labels=None, region_allow=None):
+        # ref_* / region_* accepted and ignored, like the reference: the host forwards ONE cross_attention_kwargs dict to every processor
         # (unet.py / diffusers), so whatever the harvest hands SharedAttnProcessor (ref_valid included) arrives here too
         st = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
         self.is_self_attn = encoder_hidden_states is None
@@ -588,7 +638,7 @@ class SharedAttnProcessor(nn.Module):
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                 ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None, ref_weights=None, ref_token_keep=None,
-                ref_lens=None):
+                ref_lens=None, region_labels=None, region_allow=None):
         """``attention_mask``: additive, ``(B, Lkv)``, ``(B, 1, Lkv)`` or ``(B * H, 1, Lkv)`` over this layer's key axis (with references: the
         extended one) - the fused kernel's key bias.  ``ref_weights`` ``(B, N)`` >= 0 and ``ref_token_keep`` (bool ``(B, N, len_ref)`` or
         ``(B, N, S, S)``), shared layers only (ignored elsewhere, as ``ref_valid`` is): ``ops.key_bias`` turns them into the bias -
@@ -605,9 +655,36 @@ class SharedAttnProcessor(nn.Module):
         ``ref_weights`` / ``ref_token_keep`` (counts with a key bias are a follow-up; ``ref_token_keep`` alone keeps running the bias
         path), with ``save_self_attentions`` and ``attention_rows_index`` (the read-out kernels would walk the tails);
         ``save_attention_mass`` works.  With ``use_adain`` it needs ``ref_stats``: the content statistics are those of the FULL
-        reference, taken before compaction - the rule of the bias path, so a compacted call and a masked call agree."""
+        reference, taken before compaction - the rule of the bias path, so a compacted call and a masked call agree.
+        ``region_labels = (query_labels, ref_labels)`` with ``region_allow`` (optional), shared layers only (ignored elsewhere, as
+        ``ref_valid`` is): a per-QUERY restriction by class labels - "eye tokens draw from eye tokens of the references".  The labels
+        are integer label pictures (``(B, Hpx, Wpx)`` of this image, ``(B, N, Hpx, Wpx)`` of its references: a face parsing map) or
+        per-token labels of a square grid (``(B, L)`` / ``(B, N, L)``); every layer samples them at its own token centres
+        (``attn_maps.token_labels``).  ``region_allow`` is the rule of ``ops.region_masks``: a ``(C, C)`` bool matrix (row = query class,
+        column = key class) or ``(C,)`` bitmasks, at most 31 classes.  With ``train_input`` the self keys carry the query labels and
+        every token sees its own picture whatever the rule (``self_free``).  The pair ``(q_allow, key_region)`` is built
+        once per key-axis geometry and cached by tensor identity and version.  AdaIN is unchanged; ``save_attention_mass`` honours the
+        regions.  Raises, before anything is launched, with an attention mask, ``ref_weights``, ``ref_token_keep`` or ``ref_lens``
+        (regions with a key bias or with counts are a follow-up) and with ``save_self_attentions`` or any read-out attribute (the
+        read-out kernels do not take regions yet); with ``ref_valid`` a dense call walks the zero-filled references, a table call raises."""
         st = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
         shared = self.self_attn_idx is not None and ref_keys is not None and ref_values is not None
+        regions = shared and region_labels is not None
+        if regions:     # refused before anything is launched
+            if region_allow is None:
+                raise ValueError("region_labels needs region_allow: the (C, C) bool matrix or the (C,) bitmasks of ops.region_masks")
+            if st.mask is not None or ref_weights is not None or ref_token_keep is not None:
+                raise NotImplementedError("region_labels together with an attention mask, ref_weights or ref_token_keep: the kernel carries either "
+                                          "the key bias or the region test; regions with a key bias are a follow-up")
+            if ref_lens is not None and ref_lens[self.self_attn_idx] is not None:
+                raise NotImplementedError("region_labels together with ref_lens: key_region indexes the packed uniform key axis; regions with "
+                                          "per-reference counts are a follow-up")
+            readouts = [n for n in ("attention_rows_index", "attention_match_index", "attention_topk_index", "attention_transfer_payload",
+                                    "attention_received_weights", "attention_key_match_reduce") if getattr(self, n, None) is not None]
+            if self.save_self_attentions or readouts:
+                raise NotImplementedError(f"region_labels together with {', '.join((['save_self_attentions'] if self.save_self_attentions else []) + readouts)}: "
+                                          "the read-out kernels do not take regions yet (their exp(s - lse) would count the pairs the forward "
+                                          "left out; follow-up); save_attention_mass honours the regions")
         # the GEMM's statistics tail (style partials of this layer's own V) only pays when the content statistics arrive
         # precomputed (``ref_stats``): without them ir_adain_stats reads every V anyway and would throw the partials away
         have_cstats = bool(shared and ref_stats is not None and ref_stats[self.self_attn_idx] is not None)
@@ -734,6 +811,9 @@ class SharedAttnProcessor(nn.Module):
             row = _ref_bias_row(ref_weights, ref_token_keep, query.shape[0], len_self, ref_k.shape[1], ref_k.shape[2], include_self, query.device)
             if row is not None:
                 bias = row if bias is None else (bias + (row if bias.dim() == 2 else row.unsqueeze(1)))
+        if regions:
+            kw["q_allow"], kw["key_region"] = _region_pair(region_labels, region_allow, query.shape[0],
+                                                           query.shape[1], len_self, ref_k.shape[1], ref_k.shape[2], include_self, query.device)
         if bias is not None:
             if want_probs or rows_index is not None:
                 raise NotImplementedError("save_self_attentions / attention_rows_index together with an attention mask, ref_weights or "

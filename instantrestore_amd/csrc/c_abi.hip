@@ -38,19 +38,22 @@ int64_t seg_stride_limit(int32_t len, int64_t sl) {
 // (ir_attn_probs*, ir_attn_segment_mass, ir_attn_rows, ir_attn_match, ir_attn_transfer, ir_attn_received, ir_attn_topk, ir_attn_key_match) address K through 64-bit pointers and take any stride
 bool attn_block_size_ok(uint32_t n) {
   return n == sizeof(ir_shared_attn_args) || n == sizeof(ir_shared_attn_table_args) || n == sizeof(ir_shared_attn_bias_args) ||
-         n == sizeof(ir_shared_attn_ragged_args);
+         n == sizeof(ir_shared_attn_ragged_args) || n == sizeof(ir_shared_attn_region_args);
 }
 
 int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_out, bool fwd) {
   if (a == nullptr) return fail(IR_ERR_INVALID_ARG, "args is NULL");
-  // the block up to and including seg_mass (no pointer tables), ir_shared_attn_table_args, ir_shared_attn_bias_args or
-  // ir_shared_attn_ragged_args; nothing in between
+  // the block up to and including seg_mass (no pointer tables), ir_shared_attn_table_args, ir_shared_attn_bias_args,
+  // ir_shared_attn_ragged_args or ir_shared_attn_region_args; nothing in between
   if (!attn_block_size_ok(a->struct_size))
-    return fail(IR_ERR_INVALID_ARG, "struct_size %u != %zu, %zu, %zu or %zu (ABI mismatch)", a->struct_size, sizeof(ir_shared_attn_args),
-                sizeof(ir_shared_attn_table_args), sizeof(ir_shared_attn_bias_args), sizeof(ir_shared_attn_ragged_args));
+    return fail(IR_ERR_INVALID_ARG, "struct_size %u != %zu, %zu, %zu, %zu or %zu (ABI mismatch)", a->struct_size, sizeof(ir_shared_attn_args),
+                sizeof(ir_shared_attn_table_args), sizeof(ir_shared_attn_bias_args), sizeof(ir_shared_attn_ragged_args), sizeof(ir_shared_attn_region_args));
   const ir_shared_attn_table_args* ta = a->struct_size >= sizeof(ir_shared_attn_table_args) ? (const ir_shared_attn_table_args*)a : nullptr;
   const ir_shared_attn_bias_args* ba = a->struct_size >= sizeof(ir_shared_attn_bias_args) ? (const ir_shared_attn_bias_args*)a : nullptr;
-  const ir_shared_attn_ragged_args* ra = a->struct_size == sizeof(ir_shared_attn_ragged_args) ? (const ir_shared_attn_ragged_args*)a : nullptr;
+  const ir_shared_attn_ragged_args* ra = a->struct_size >= sizeof(ir_shared_attn_ragged_args) ? (const ir_shared_attn_ragged_args*)a : nullptr;
+  const ir_shared_attn_region_args* ga = a->struct_size == sizeof(ir_shared_attn_region_args) ? (const ir_shared_attn_region_args*)a : nullptr;
+  const uint32_t* qallow = ga != nullptr ? ga->q_allow : nullptr;
+  const int32_t* kregion = ga != nullptr ? ga->key_region : nullptr;
   const float* kbias = ba != nullptr ? ba->key_bias : nullptr;
   const int32_t* rlens = ra != nullptr ? ra->ref_lens : nullptr;
   const void* const* ktab = ta != nullptr ? ta->k_ref_table : nullptr;
@@ -114,6 +117,28 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
       return fail(IR_ERR_UNSUPPORTED, "ref_lens: tuning %d has no RAGGED form (IR_TUNE_DEFAULT, IR_TUNE_PIPE32_PRESCALE_Q or IR_TUNE_PIPE32_EARLYQK: the "
                   "32-row kernel runs every call with per-reference counts)", a->tuning);
   }
+  if ((qallow == nullptr) != (kregion == nullptr)) return fail(IR_ERR_INVALID_ARG, "q_allow and key_region must both be set or both be NULL");
+  if (qallow != nullptr) {
+    if (!fwd)
+      return fail(IR_ERR_UNSUPPORTED, "q_allow / key_region: ir_attn_probs[_ex], ir_attn_segment_mass, ir_attn_rows, ir_attn_match, ir_attn_transfer, ir_attn_received, ir_attn_topk and ir_attn_key_match do not take "
+                  "regions yet (their exp(s - lse) would count the pairs the forward left out); the forward's seg_mass by-product does");
+    if (((reinterpret_cast<uintptr_t>(qallow) | reinterpret_cast<uintptr_t>(kregion)) & 3u) != 0) return fail(IR_ERR_UNSUPPORTED, "q_allow and key_region must be 4-byte aligned");
+    const int64_t lkv = (inc ? (int64_t)a->len_self : 0) + (int64_t)a->n_refs * a->len_ref;
+    if (ga->qa_sb < a->len_q) return fail(IR_ERR_INVALID_ARG, "q_allow row stride qa_sb %lld must be >= len_q %d", (long long)ga->qa_sb, a->len_q);
+    if (ga->kg_sb < lkv) return fail(IR_ERR_INVALID_ARG, "key_region row stride kg_sb %lld must be >= Lkv %lld", (long long)ga->kg_sb, (long long)lkv);
+    if (kbias != nullptr)
+      return fail(IR_ERR_UNSUPPORTED, "q_allow / key_region together with key_bias: one C operand carries either the bias or the region test; regions with a "
+                  "bias are a follow-up");
+    if (rlens != nullptr)
+      return fail(IR_ERR_UNSUPPORTED, "q_allow / key_region together with ref_lens: key_region indexes the packed uniform key axis (len_ref keys per reference); "
+                  "regions with counts are a follow-up");
+    if (a->valid_refs != nullptr && a->n_refs > 0)
+      return fail(IR_ERR_UNSUPPORTED, "q_allow / key_region together with valid_refs: the closed form of the zero-filled suffix gives every row its keys (pass "
+                  "valid_refs = NULL and let the kernel walk the zeros, or give those keys a region nobody may attend)");
+    if (a->tuning != IR_TUNE_DEFAULT && a->tuning != IR_TUNE_PIPE32_PRESCALE_Q && a->tuning != IR_TUNE_PIPE32_EARLYQK)
+      return fail(IR_ERR_UNSUPPORTED, "q_allow / key_region: tuning %d has no REGION form (IR_TUNE_DEFAULT, IR_TUNE_PIPE32_PRESCALE_Q or IR_TUNE_PIPE32_EARLYQK: the "
+                  "32-row kernel runs every call with regions)", a->tuning);
+  }
   const void* ptrs[] = {a->q, a->k_self, a->v_self, a->k_ref, a->v_ref, a->out, a->adain_a, a->adain_b};
   for (const void* q : ptrs)
     if (q != nullptr && !aligned16(q)) return fail(IR_ERR_UNSUPPORTED, "pointer %p is not 16-byte aligned", q);
@@ -155,6 +180,7 @@ int build_attn_params(const ir_shared_attn_args* a, AttnKParams* p, bool need_ou
   p->include_self = inc ? 1 : 0;
   if (kbias != nullptr) { p->key_bias = kbias; p->kb_sb = ba->kb_sb; p->kb_sh = ba->kb_sh; }
   if (rlens != nullptr) { p->ref_lens = rlens; p->rl_sb = ra->rl_sb; }
+  if (qallow != nullptr) { p->q_allow = qallow; p->qa_sb = ga->qa_sb; p->key_region = kregion; p->kg_sb = ga->kg_sb; }
   p->q_prescaled = (a->flags & IR_FLAG_Q_PRESCALED) ? 1 : 0;
   p->out_f32 = (a->flags & IR_FLAG_OUT_F32) ? 1 : 0;
   if (p->q_prescaled && ((a->tuning >> 5) != 0 || !ir_attn_variant(a->tuning)->presc_q))   // (the availability test above found the row)
@@ -213,6 +239,7 @@ AttnKParams batch_slice(const AttnKParams& p, int b0, int nb) {
   if (p.valid != nullptr) q.valid = p.valid + b0;
   if (p.key_bias != nullptr) q.key_bias = p.key_bias + (int64_t)b0 * p.kb_sb;
   if (p.ref_lens != nullptr) q.ref_lens = p.ref_lens + (int64_t)b0 * p.rl_sb;
+  if (p.q_allow != nullptr) { q.q_allow = p.q_allow + (int64_t)b0 * p.qa_sb; q.key_region = p.key_region + (int64_t)b0 * p.kg_sb; }
   return q;
 }
 
@@ -240,8 +267,8 @@ int launch_fwd(const ir_shared_attn_args* a, const AttnKParams& p, hipStream_t s
 
 // The parameter block of a read-out of the forward's LSE (ir_attn_probs_ex, ir_attn_segment_mass, ir_attn_rows, ir_attn_match,
 // ir_attn_transfer, ir_attn_received, ir_attn_topk, ir_attn_key_match).
-// `single_kernel`: the name of an entry point that has one kernel and refuses a tuning value, or nullptr.  A key bias and
-// per-reference counts are refused for the whole family in build_attn_params (!fwd)
+// `single_kernel`: the name of an entry point that has one kernel and refuses a tuning value, or nullptr.  A key bias,
+// per-reference counts and regions are refused for the whole family in build_attn_params (!fwd)
 int build_readout_params(const ir_shared_attn_args* args, AttnKParams* p, const char* single_kernel) {
   if (single_kernel != nullptr) {
     if (args == nullptr) return fail(IR_ERR_INVALID_ARG, "args is NULL");
@@ -327,10 +354,11 @@ const char* ir_shared_attn_kernel_name(const ir_shared_attn_args* args) {
     default: break;
   }
   if (head == nullptr) return "shared_attn_fwd (tuning variant)";
-  static thread_local char name[256];
-  int n = snprintf(name, sizeof(name), "%s%s%s%s%s%s%s>", head, fold ? fold_text : "", forms && p.valid != nullptr ? ", zero suffix in closed form" : "",
+  static thread_local char name[320];
+  int n = snprintf(name, sizeof(name), "%s%s%s%s%s%s%s%s>", head, fold ? fold_text : "", forms && p.valid != nullptr ? ", zero suffix in closed form" : "",
                    forms && p.seg_cum != nullptr ? ", segment masses" : "", bi && c.family == IR_FAM_W128_FORMS ? ", forms" : "",
-                   p.key_bias != nullptr ? ", key bias (reference follows every max)" : "", p.ref_lens != nullptr ? ", ragged refs (per-reference counts)" : "");
+                   p.key_bias != nullptr ? ", key bias (reference follows every max)" : "", p.ref_lens != nullptr ? ", ragged refs (per-reference counts)" : "",
+                   p.q_allow != nullptr ? ", regions (per-query masks, reference per row)" : "");
   if (bi) {   // the plan's cut; the name does not change with seg_mass (the output does not either)
     const IrAttnBiPlan pl = bi_plan_of(args, p);
     snprintf(name + n, sizeof(name) - n, " [batch-invariant: %d piece%s per %d-row item]", pl.pieces, pl.pieces > 1 ? "s" : "", pl.rows);

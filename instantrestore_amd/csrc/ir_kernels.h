@@ -78,6 +78,13 @@ struct AttnKParams {
   // 32-row kernel only (shared_attn_fwd_pipe_ragged.hip), when they run; appended, so no other kernel's arguments move
   const int32_t* ref_lens;
   int64_t rl_sb;
+  // region-restricted attention (ir_shared_attn_region_args): row i of entry b may attend key j iff key_region[b * kg_sb + j] is in
+  // [0, 31] and bit key_region[..] of q_allow[b * qa_sb + i] is set; one rule for all heads.  nullptr (both): none.  Read by the REGION
+  // forms of the 32-row kernel only (shared_attn_fwd_pipe_region.hip), when they run; appended, so no other kernel's arguments move
+  const uint32_t* q_allow;
+  int64_t qa_sb;
+  const int32_t* key_region;
+  int64_t kg_sb;
 };
 
 // The base address (head 0, token 0) of a reference segment from `at` = k_ref + b * kr_sb + n * kr_sn: `at` itself in the dense
@@ -183,6 +190,7 @@ hipError_t ir_launch_shared_attn_fwd(const AttnKParams& p, int dtype, int varian
 hipError_t ir_launch_shared_attn_fwd_pipe(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s);
 hipError_t ir_launch_shared_attn_fwd_pipe_bias(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s);   // key_bias: PRESC / EARLYQK (shared_attn_fwd_pipe_bias.hip)
 hipError_t ir_launch_shared_attn_fwd_pipe_ragged(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s);   // ref_lens: PRESC / EARLYQK (shared_attn_fwd_pipe_ragged.hip)
+hipError_t ir_launch_shared_attn_fwd_pipe_region(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s);   // q_allow / key_region: PRESC / EARLYQK (shared_attn_fwd_pipe_region.hip)
 hipError_t ir_launch_shared_attn_combine(const AttnKParams& p, int dtype, int qb, int rem, hipStream_t s);
 hipError_t ir_launch_shared_attn_fwd_w64(const AttnKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_shared_attn_fwd_w64x8(const AttnKParams& p, int dtype, hipStream_t s);

@@ -494,7 +494,7 @@ __global__ void __launch_bounds__(256) seg_mass_finish_kernel(float* __restrict_
   if (r >= rows) return;
   float* c = cum + r * S;
   const float tot = c[S - 1];
-  if (tot == -INFINITY) {   // key bias: every key of the row masked - no mass anywhere (c - tot would not be a number)
+  if (tot == -INFINITY) {   // key bias / regions: every key of the row masked - no mass anywhere (c - tot would not be a number)
     for (int s = 0; s < S; ++s) c[s] = 0.f;
     return;
   }
@@ -517,8 +517,8 @@ hipError_t ir_launch_seg_mass_finish(const AttnKParams& p, hipStream_t s) {
 // split of the last round of workgroup slots) and process state (IR_ATTN_W128); this one reads per-item parameters only:
 //   kernel: the 128-row kernel (its FORMS instantiation, which carries valid_refs and seg_mass at run time) for pre-scaled Q, whole
 //           tiles and Lq >= 4096; the 8-wave 64-row kernel for other Lq >= 4096 calls; the pipelined 32-row kernel below that
-//           (and at every Lq when a key bias or per-reference counts are given - one more per-entry parameter each: only that
-//           kernel has the BIAS and RAGGED forms);
+//           (and at every Lq when a key bias, per-reference counts or regions are given - one more per-entry parameter each: only
+//           that kernel has the BIAS, RAGGED and REGION forms);
 //   pieces: every item of a call WITH references (n_refs > 0: the shared layers, whose batch is the identities) is cut into k
 //           K/V-range pieces (tile boundaries from the item's own tile count) merged by the combine kernel in piece order;
 //           k = ceil(256 / items of ONE batch entry) - one entry fills the 256 CUs of an MI355X (a constant, not the device's count) -
@@ -529,6 +529,7 @@ hipError_t ir_launch_seg_mass_finish(const AttnKParams& p, hipStream_t s) {
 IrAttnChoice ir_attn_choose_bi(const AttnKParams& p) {
   if (p.key_bias != nullptr) return {IR_FAM_PIPE32, p.q_prescaled ? IR_PIPE_PRESC : IR_PIPE_EARLYQK};   // key bias: the 32-row kernel's BIAS forms, at every Lq
   if (p.ref_lens != nullptr) return {IR_FAM_PIPE32, p.q_prescaled ? IR_PIPE_PRESC : IR_PIPE_EARLYQK};   // ref_lens: its RAGGED forms, at every Lq
+  if (p.q_allow != nullptr) return {IR_FAM_PIPE32, p.q_prescaled ? IR_PIPE_PRESC : IR_PIPE_EARLYQK};    // regions: its REGION forms, at every Lq
   if (p.Lq >= 4096) return {p.q_prescaled && ir_attn_w128_supports(p) ? IR_FAM_W128_FORMS : IR_FAM_W64X8, IR_PIPE_NONE};
   return {IR_FAM_PIPE32, p.q_prescaled ? IR_PIPE_PRESC : IR_PIPE_EARLYQK};
 }
@@ -565,6 +566,8 @@ IrAttnChoice ir_attn_choose(const AttnKParams& p, int tuning) {
   if (p.key_bias != nullptr) return {IR_FAM_PIPE32, p.q_prescaled || v->form == IR_PIPE_PRESC ? IR_PIPE_PRESC : IR_PIPE_EARLYQK};
   // per-reference counts: its RAGGED forms, by the same rule (c_abi.hip admits the same three tuning values)
   if (p.ref_lens != nullptr) return {IR_FAM_PIPE32, p.q_prescaled || v->form == IR_PIPE_PRESC ? IR_PIPE_PRESC : IR_PIPE_EARLYQK};
+  // regions: its REGION forms, by the same rule (c_abi.hip admits the same three tuning values)
+  if (p.q_allow != nullptr) return {IR_FAM_PIPE32, p.q_prescaled || v->form == IR_PIPE_PRESC ? IR_PIPE_PRESC : IR_PIPE_EARLYQK};
   IrAttnChoice c = {v->family, v->form};
   if (v->id == IR_TUNE_DEFAULT) {
     if (p.q_prescaled && ir_attn_default_is_w128(p)) c = {IR_FAM_W128, IR_PIPE_NONE};
@@ -596,6 +599,7 @@ static hipError_t launch_choice(const AttnKParams& p, int dtype, IrAttnChoice c,
     case IR_FAM_PIPE32:
       if (p.key_bias != nullptr) return ir_launch_shared_attn_fwd_pipe_bias(p, dtype, c.form, s);
       if (p.ref_lens != nullptr) return ir_launch_shared_attn_fwd_pipe_ragged(p, dtype, c.form, s);
+      if (p.q_allow != nullptr) return ir_launch_shared_attn_fwd_pipe_region(p, dtype, c.form, s);
       return ir_launch_shared_attn_fwd_pipe(p, dtype, c.form, s);
     default: return hipErrorInvalidValue;
   }

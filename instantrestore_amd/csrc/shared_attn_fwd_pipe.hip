@@ -15,10 +15,10 @@
 // staged one tile further ahead than V: K ring of 2, V ring of 3 (one prefetch stream, tiles
 // arrive as (K[j], V[j]) pairs two iterations ahead of their PV, by LDS-DMA issued from asm).
 //
-// One kernel body, nine product forms: how the running reference of the softmax is kept (exact,
+// One kernel body, eleven product forms: how the running reference of the softmax is kept (exact,
 // lazy max, pre-scaled Q with the reference through the MFMA C operand, that with the reference
 // checked after the exponentials), whether the next tile's QK^T is issued before the row max, and
-// the two extensions - an additive key bias, per-reference key counts - of the two default forms.
+// the three extensions - an additive key bias, per-reference key counts, per-query region masks - of the two default forms.
 // The Form... structs below name them; the body reads those names and nothing else.
 //
 // VALU diet (D = 64 is VALU-issue bound): row sums as packed v_pk_add_f32 into two 2-wide
@@ -51,27 +51,30 @@ struct FormExact {                               // rescale whenever some row's 
   static constexpr bool post_check = false;      // no row max on ordinary tiles: the reference is checked after the exponentials
   static constexpr bool key_bias = false;        // ir_shared_attn_bias_args.key_bias
   static constexpr bool ref_counts = false;      // ir_shared_attn_ragged_args.ref_lens
+  static constexpr bool regions = false;         // ir_shared_attn_region_args.q_allow / key_region
 };
 struct FormLazy : FormExact { static constexpr bool lazy_max = true; };
 struct FormPresc : FormLazy { static constexpr bool presc_q = true; };
 struct FormEarlyQK : FormLazy { static constexpr bool early_qk = true; };
 struct FormPostCheck : FormPresc { static constexpr bool post_check = true; };
-// the two extensions, each instantiated in a translation unit of its own
+// the three extensions, each instantiated in a translation unit of its own
 template <typename F> struct WithKeyBias : F { static constexpr bool key_bias = true; };       // shared_attn_fwd_pipe_bias.hip
 template <typename F> struct WithRefCounts : F { static constexpr bool ref_counts = true; };   // shared_attn_fwd_pipe_ragged.hip
+template <typename F> struct WithRegions : F { static constexpr bool regions = true; };         // shared_attn_fwd_pipe_region.hip
 template <typename F> using NoExtension = F;
 
 template <typename F>
 constexpr bool form_is_legal() {
   static_assert(!F::post_check || F::presc_q, "the check after the exponentials needs scores that already carry the reference");
-  static_assert(!(F::key_bias || F::ref_counts) || (F::lazy_max && !F::post_check && F::presc_q != F::early_qk),
-                "the key bias and the per-reference counts are built into the PRESC and EARLYQK forms only");
+  static_assert(!(F::key_bias || F::ref_counts || F::regions) || (F::lazy_max && !F::post_check && F::presc_q != F::early_qk),
+                "the key bias, the per-reference counts and the regions are built into the PRESC and EARLYQK forms only");
   static_assert(!(F::key_bias && F::ref_counts), "counts together with a bias: not built (the public header names it as a follow-up)");
+  static_assert(!(F::regions && (F::key_bias || F::ref_counts)), "regions together with a bias or with counts: not built (the public header names it as a follow-up)");
   return true;
 }
-// a row may have no key at all (key bias: every key masked; counts: no self block and every count 0): exact zeros, lse = -inf,
+// a row may have no key at all (key bias: every key masked; counts: no self block and every count 0; regions: no allowed key): exact zeros, lse = -inf,
 // in the kernel's epilogue and in the combine kernel that merges its pieces
-template <typename F> constexpr bool kRowMayHaveNoKey = F::key_bias || F::ref_counts;
+template <typename F> constexpr bool kRowMayHaveNoKey = F::key_bias || F::ref_counts || F::regions;
 
 // F: the form (above).  FOLD: the AdaIN affine is folded in per segment.
 // MASS (ABI v9 seg_mass): also store the cumulative log-sum-exp at every segment boundary - a separate instantiation of the two
@@ -99,6 +102,14 @@ __global__ void __launch_bounds__(NT, 2) shared_attn_fwd_pipe_kernel(const AttnK
   // behind it and the ragged-tail -inf of step (1) masks them), and the step to the next segment, which passes over c_n == 0
   // without a descriptor, a load or a fold.  The counts come through the constant address space, as table entries do.
   constexpr bool RAGGED = F::ref_counts;
+  // REGION (ir_shared_attn_region_args; the PRESC and EARLYQK forms, instantiated in shared_attn_fwd_pipe_region.hip): the BIAS mechanism
+  // with a query axis.  A lane holds ONE query row (S^T = K Q^T: the lane's 32 S registers are 32 keys of row lq), so it keeps that
+  // row's q_allow word in a register; the int32 regions of its 32 keys per tile come through the bias stream as it stands (same
+  // descriptor shape, same b128 loads into the free S registers one tile ahead) and each becomes the C operand in place: the
+  // reference where bit `region` of the word is set, -inf elsewhere (region outside [0, 31]: nobody's).  Everything BIAS decides
+  // wave-uniformly "because the bias has no query axis" is per ROW here: `started`, the adoption of the first live tile's max, the
+  // rescale factor of a row whose reference is still -inf, and what fold_segment and the piece store do with an unstarted row.
+  constexpr bool REGION = F::regions;
   constexpr int KRING = CHK ? 3 : 2;
   constexpr int K_OFF = 0;                       // K ring: 2 tiles (3 with CHK)
   constexpr int V_OFF = KRING * TILE_BYTES;      // V ring: 3 tiles
@@ -261,6 +272,12 @@ __global__ void __launch_bounds__(NT, 2) shared_attn_fwd_pipe_kernel(const AttnK
   // + 4 hi of the tile (c1: + 32): eight groups of four consecutive keys, starting at key 8 g + 4 hi - no alignment beyond 4 bytes.
   __amdgpu_buffer_rsrc_t brs;
   if (BIAS) brs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.key_bias + (int64_t)b * p.kb_sb + (int64_t)h * p.kb_sh), 0, p.lkv * 4, 0x00020000);
+  // REGION: the same stream over the Lkv int32 regions of this batch entry (one rule for all heads).  A load past the end returns 0 -
+  // region 0, which a row may well be allowed: only the ragged-tail -inf of step (1) keeps those slots out, as it does for BIAS
+  if (REGION) brs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.key_region + (int64_t)b * p.kg_sb), 0, p.lkv * 4, 0x00020000);
+  // REGION: the regions this lane's row may attend; a padding row past len_q may attend nothing (it stays unstarted and is never stored)
+  uint32_t qa = 0;
+  if (REGION) qa = qrow < p.Lq ? p.q_allow[(int64_t)b * p.qa_sb + qrow] : 0u;
   auto bias_load = [&](f32x16& a0, f32x16& a1) {   // raw bias of the tile at the prefetch stream's position (seg, t0) -> a0, a1
     const int key0 = ((p.include_self && seg == 0) ? 0 : p.include_self * p.Ls + (seg - p.include_self) * p.Lr) + t0 * KVB;
     const unsigned vo = (unsigned)(key0 * 4) + (unsigned)(hi * 16);
@@ -285,9 +302,11 @@ __global__ void __launch_bounds__(NT, 2) shared_attn_fwd_pipe_kernel(const AttnK
   // LAZYMAX: score growth that forces a rescale.  BIAS: none - the reference follows every growth of a row's max, so the key that
   // carries a row has probability exactly 1 and takes no 16-bit rounding of its own (with the lazy reference two of 118 bf16
   // comparisons of tests/test_gpu_key_bias.py left the regression bound: 1.01 and 1.06 of it, 0.53 with the exact reference)
-  const float lazy_thr = BIAS ? 0.f : (PRESC ? 6.0f : 6.0f / c2);
+  // REGION: the same exact reference, for the same reason (a row restricted to a few keys is the case where one key carries it)
+  const float lazy_thr = (BIAS || REGION) ? 0.f : (PRESC ? 6.0f : 6.0f / c2);
   float cum_last = -INFINITY;               // RAGGED + MASS: the cumulative value stored last - an absent reference repeats it
   bool started = false;                     // BIAS + PRESC: a tile with an unmasked key has set the reference (wave-uniform: the bias has no query axis)
+                                            // REGION + PRESC: the same PER ROW (this lane's row has met an allowed key)
   // BIAS: loaded bias -> exponent units of the scores as they leave the matrix pipe (PRESC: exp2 domain; else raw scores, scaled by c2 later)
   const float kb_mul = PRESC ? 1.4426950408889634f : 1.4426950408889634f / c2;
   f32x16 mneg;                              // PRESC: -m_run in every register: C operand of the first QK^T MFMA
@@ -337,6 +356,22 @@ __global__ void __launch_bounds__(NT, 2) shared_attn_fwd_pipe_kernel(const AttnK
       for (int r = 0; r < 16; ++r) {
         s0[r] = s0[r] <= IR_KEY_BIAS_MASKED ? -INFINITY : __builtin_fmaf(s0[r], kb_mul, ref);
         s1[r] = s1[r] <= IR_KEY_BIAS_MASKED ? -INFINITY : __builtin_fmaf(s1[r], kb_mul, ref);
+      }
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        s0 = Tr::mfma(kf0[ks], qf[ks], s0);
+        s1 = Tr::mfma(kf1[ks], qf[ks], s1);
+      }
+      return;
+    }
+    if constexpr (REGION) {   // s0, s1 arrive holding the regions of the tile's keys: C operand = (- the reference) where this row may attend the key, -inf elsewhere
+      // (`if constexpr`: qa must not become a capture in the other instantiations - their code is to stay as it was)
+      const float ref = PRESC ? -m_run : 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const uint32_t g0 = __float_as_uint(s0[r]), g1 = __float_as_uint(s1[r]);
+        s0[r] = (g0 < 32u && ((qa >> (g0 & 31u)) & 1u) != 0u) ? ref : -INFINITY;
+        s1[r] = (g1 < 32u && ((qa >> (g1 & 31u)) & 1u) != 0u) ? ref : -INFINITY;
       }
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
@@ -395,18 +430,23 @@ __global__ void __launch_bounds__(NT, 2) shared_attn_fwd_pipe_kernel(const AttnK
   auto fold_segment = [&]() {
     // BIAS: every key so far masked - nothing is accumulated (all zeros) and the reference is not set: 2^(m_ot - m_run) would be
     // 2^(-inf - -inf), or a huge factor once a first unmasked tile far below the start value adopts its max.  m_ot stays -inf.
-    if (BIAS && (PRESC ? !started : !__any(m_run > -INFINITY))) {
+    // REGION: the same when no row of the wave has met an allowed key; otherwise per row (below)
+    if ((BIAS && (PRESC ? !started : !__any(m_run > -INFINITY))) || (REGION && (PRESC ? !__any(started) : !__any(m_run > -INFINITY)))) {
       if (MASS) cum_store(cseg, -INFINITY);
       return;
     }
+    // REGION: rows of one wave start at different tiles.  A row that has not started holds zeros everywhere and no reference: it keeps
+    // m_ot = -inf (its later first fold then takes f = 2^-inf = 0, not 2^(start value - adopted max)) and takes the factor 0 on totals
+    // that are 0; its cumulative value is log2(0) = -inf by the ordinary expression
+    const bool row_live = !REGION || (PRESC ? started : m_run > -INFINITY);
     float lseg = (la[0] + la[1]) + (lb[0] + lb[1]);
     {
       const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(lseg), __float_as_uint(lseg), false, false);
       lseg = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
     }
-    const float f = fast_exp2(PRESC ? (m_ot - m_run) : (m_ot - m_run) * c2);  // m_ot = -inf the first time: f = 0
+    const float f = row_live ? fast_exp2(PRESC ? (m_ot - m_run) : (m_ot - m_run) * c2) : 0.f;  // m_ot = -inf the first time: f = 0
     l_tot = l_tot * f + lseg;
-    m_ot = m_run;
+    m_ot = row_live ? m_run : -INFINITY;
     if (MASS) cum_store(cseg, ref_log2() + __log2f(l_tot));   // l_tot: every segment so far, relative to m_run
     const bool is_ref = !(p.include_self && cseg == 0);
     const int n = cseg - p.include_self;
@@ -491,9 +531,18 @@ __global__ void __launch_bounds__(NT, 2) shared_attn_fwd_pipe_kernel(const AttnK
         adopt = live && !started;
         started = started || live;
       }
+      // REGION: per row - a row adopts the max of ITS first tile with an allowed key, whenever that is; a row still without one has
+      // mx = -inf, is not adopting and takes d = 0, alpha = 1 (never d = -inf), as does a started row whose tile is all masked
+      bool adopt_row = adopt;
+      if (REGION) {
+        const bool live = mx > -INFINITY;
+        adopt_row = live && !started;
+        started = started || live;
+        adopt = __any(adopt_row);
+      }
       if (adopt || __any(mx > lazy_thr)) {
-        const float d = adopt ? mx : (mx > 0.f ? mx : 0.f);
-        const float alpha = adopt ? 1.f : fast_exp2(-d);
+        const float d = adopt_row ? mx : (mx > 0.f ? mx : 0.f);
+        const float alpha = adopt_row ? 1.f : fast_exp2(-d);
 #pragma unroll
         for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; c0[r] -= d; c1[r] -= d; }
         la *= alpha;
@@ -509,16 +558,18 @@ __global__ void __launch_bounds__(NT, 2) shared_attn_fwd_pipe_kernel(const AttnK
     constexpr bool LAZYMAX = F::lazy_max;
     if (PRESC) {   // (CHK: nothing here - the check comes after the exponentials)
     } else if (LAZYMAX ? __any(mx > m_run + lazy_thr) : __any(m_new != m_run)) {
-      const float alpha = fast_exp2((m_run - m_new) * c2);
+      // (REGION: a row whose reference stays -inf while a neighbour's moves - (-inf - -inf) is not a number; its accumulators are zeros)
+      const float alpha = (REGION && !(m_new > -INFINITY)) ? 1.f : fast_exp2((m_run - m_new) * c2);
 #pragma unroll
       for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
       la *= alpha;
       lb *= alpha;
       m_run = m_new;
     }
-    // (BIAS: no unmasked key yet - the reference is still -inf and every score of the tile is: fma(-inf, c2, +inf) would be NaN)
+    // (BIAS: no unmasked key yet - the reference is still -inf and every score of the tile is: fma(-inf, c2, +inf) would be NaN.
+    //  The guard is per row, which is what REGION needs)
     const float m_sub = LAZYMAX ? m_run : m_new;
-    const float mc = (BIAS && !(m_sub > -INFINITY)) ? 0.f : m_sub * c2;
+    const float mc = ((BIAS || REGION) && !(m_sub > -INFINITY)) ? 0.f : m_sub * c2;
     // (4) the overlapped block: prefetch issue, S(t+1) on the matrix pipe, exp/pack on the VALU,
     //     PV(t) on the matrix pipe
     if (!EARLYQK && has2) issue_dma(ks_free, v_prev);  // K slot of tile t+2 (ring of 2: (t+2)&1; of 3: (vcur+2)%3), V slot (vcur+2)%3: free since the last barrier
@@ -594,7 +645,7 @@ __global__ void __launch_bounds__(NT, 2) shared_attn_fwd_pipe_kernel(const AttnK
     pk[0][1] = __builtin_convertvector(__builtin_shufflevector(c0, c0, 8, 9, 10, 11, 12, 13, 14, 15), v8);
     pk[1][0] = __builtin_convertvector(__builtin_shufflevector(c1, c1, 0, 1, 2, 3, 4, 5, 6, 7), v8);
     pk[1][1] = __builtin_convertvector(__builtin_shufflevector(c1, c1, 8, 9, 10, 11, 12, 13, 14, 15), v8);
-    if (BIAS && has2) bias_load(c0, c1);   // S(t) is packed: its registers take the bias of tile t+2 (the prefetch stream's position)
+    if ((BIAS || REGION) && has2) bias_load(c0, c1);   // S(t) is packed: its registers take the bias (REGION: the regions) of tile t+2 (the prefetch stream's position)
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
@@ -644,11 +695,11 @@ __global__ void __launch_bounds__(NT, 2) shared_attn_fwd_pipe_kernel(const AttnK
 #pragma unroll
     for (int r = 0; r < 16; ++r) { sa0[r] = 0.f; sa1[r] = 0.f; sb0[r] = 0.f; sb1[r] = 0.f; }
   } else {
-    if (BIAS) bias_load(sa0, sa1);
+    if (BIAS || REGION) bias_load(sa0, sa1);
     issue_dma(0, 0);
     advance();
     if (NTILES > 1) {
-      if (BIAS) bias_load(sb0, sb1);
+      if (BIAS || REGION) bias_load(sb0, sb1);
       issue_dma(1, 1);
       advance();
     }
@@ -791,8 +842,8 @@ __global__ void __launch_bounds__(NT, 2) shared_attn_fwd_pipe_kernel(const AttnK
       // pre-scaled forms start their reference at 0, and a 0 beside real pieces whose maxima lie below -126 exponent units
       // would flush every weight to zero
       const bool empty_piece = NTILES == 0 && !(nref < p.N && piece == npiece - 1);
-      // (BIAS: a piece whose keys are all masked holds nothing either; without PRESC its m_run is still -inf)
-      p.ws_ml[prow * 2] = (empty_piece || (BIAS && PRESC && !started)) ? -INFINITY : (PRESC ? m_run / c2 : m_run);
+      // (BIAS: a piece whose keys are all masked holds nothing either; without PRESC its m_run is still -inf.  REGION: per row)
+      p.ws_ml[prow * 2] = (empty_piece || ((BIAS || REGION) && PRESC && !started)) ? -INFINITY : (PRESC ? m_run / c2 : m_run);
       p.ws_ml[prow * 2 + 1] = l_fin;
     }
     return;
@@ -939,6 +990,11 @@ hipError_t ir_launch_shared_attn_fwd_pipe_ragged(const AttnKParams& p, int dtype
   if (p.ref_lens == nullptr || p.valid != nullptr || p.key_bias != nullptr || p.N <= 0) return hipErrorInvalidValue;
   return dtype == 1 ? launch_t<__bf16, WithRefCounts>(p, form, s) : launch_t<_Float16, WithRefCounts>(p, form, s);
 }
+#elif defined(IR_PIPE_REGION_TU)   // shared_attn_fwd_pipe_region.hip: the region instantiations and nothing else of this file
+hipError_t ir_launch_shared_attn_fwd_pipe_region(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s) {
+  if (p.q_allow == nullptr || p.key_region == nullptr || p.valid != nullptr || p.key_bias != nullptr || p.ref_lens != nullptr) return hipErrorInvalidValue;
+  return dtype == 1 ? launch_t<__bf16, WithRegions>(p, form, s) : launch_t<_Float16, WithRegions>(p, form, s);
+}
 #else
 // the combine of every kernel family (p must carry the final sk_* / ws_* fields)
 template <typename T, int QB>
@@ -959,4 +1015,4 @@ hipError_t ir_launch_shared_attn_combine(const AttnKParams& p, int dtype, int qb
 hipError_t ir_launch_shared_attn_fwd_pipe(const AttnKParams& p, int dtype, IrPipeForm form, hipStream_t s) {
   return dtype == 1 ? launch_t<__bf16, NoExtension>(p, form, s) : launch_t<_Float16, NoExtension>(p, form, s);
 }
-#endif  // IR_PIPE_BIAS_TU / IR_PIPE_RAGGED_TU
+#endif  // IR_PIPE_BIAS_TU / IR_PIPE_RAGGED_TU / IR_PIPE_REGION_TU

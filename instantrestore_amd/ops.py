@@ -248,10 +248,14 @@ def _is_table(t) -> bool:
 
 
 def _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, lse, split=True,
-               q_prescaled=False, valid_refs=None, batch_invariant=False, key_bias=None, ref_lens=None):
+               q_prescaled=False, valid_refs=None, batch_invariant=False, key_bias=None, ref_lens=None, q_allow=None, key_region=None):
     if ref_lens is not None:   # validated before anything else is touched
         _check_ref_lens(ref_lens, q, ref_k, valid_refs, key_bias)
-    a = _lib.SharedAttnRaggedArgs() if ref_lens is not None else _lib.SharedAttnBiasArgs() if key_bias is not None else _lib.SharedAttnTableArgs() if _is_table(ref_k) else _lib.SharedAttnArgs()
+    regions = q_allow is not None or key_region is not None
+    if regions:
+        lkv = (k_self.shape[1] if include_self else 0) + (ref_k.shape[1] * ref_k.shape[2] if ref_k is not None else 0)
+        _check_regions(q_allow, key_region, q, lkv, key_bias, ref_lens)
+    a = _lib.SharedAttnRegionArgs() if regions else _lib.SharedAttnRaggedArgs() if ref_lens is not None else _lib.SharedAttnBiasArgs() if key_bias is not None else _lib.SharedAttnTableArgs() if _is_table(ref_k) else _lib.SharedAttnArgs()
     a.struct_size = C.sizeof(a)
     a.dtype = _dtype_code(q)
     a.flags = (_lib.IR_FLAG_INCLUDE_SELF if include_self else 0) | (_lib.IR_FLAG_Q_PRESCALED if q_prescaled else 0)
@@ -294,6 +298,14 @@ def _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adai
     if ref_lens is not None:
         a.ref_lens, a.rl_sb = ref_lens.data_ptr(), ref_lens.stride(0)
         a._keeplens = ref_lens
+    if regions:
+        a.q_allow, a.qa_sb = q_allow.data_ptr(), q_allow.stride(0)
+        a.key_region, a.kg_sb = key_region.data_ptr(), key_region.stride(0)
+        a._keepregions = (q_allow, key_region)
+        if valid_refs is not None and _is_table(ref_k):
+            raise ValueError("q_allow / key_region with valid_refs on a RefKVTable call: slots n >= valid_refs[b] of the table are not readable, and the "
+                             "kernel with regions walks every reference (give those keys a region nobody may attend and fill the slots, or pass dense tensors)")
+        valid_refs = None   # dense: the promise is about the DATA (all-zero references) - walking the zeros gives the same numbers
     if valid_refs is not None and ref_k is not None:
         if valid_refs.dtype != torch.int32 or valid_refs.device != q.device or valid_refs.numel() != q.shape[0] or not valid_refs.is_contiguous():
             raise ValueError(f"valid_refs must be a contiguous int32 ({q.shape[0]},) tensor on {q.device}")
@@ -328,6 +340,80 @@ def _check_ref_lens(rl, q, ref_k, valid_refs=None, key_bias=None) -> None:
         raise ValueError("ref_lens with valid_refs: a count of 0 says the reference is absent, valid_refs says it is zero-filled - pass one of the two")
     if key_bias is not None:
         raise ValueError("ref_lens with key_bias: the bias indexes the packed uniform key axis; counts together with a bias are a follow-up")
+
+
+def _check_regions(q_allow, key_region, q, lkv: int, key_bias=None, ref_lens=None) -> None:
+    """``q_allow``: uint32 (or int32 storage of the same bits) ``(B, Lq)``; ``key_region``: int32 ``(B, Lkv)``; both on q's device, last
+    axis contiguous (the row strides go to the kernel as they are); both or neither; not together with ``key_bias`` or ``ref_lens``"""
+    if q_allow is None or key_region is None:
+        raise ValueError("q_allow and key_region must be given together")
+    if not isinstance(q_allow, torch.Tensor) or q_allow.dtype not in (torch.int32, torch.uint32):
+        raise ValueError(f"q_allow must be an int32 or uint32 tensor (one 32-bit word per query row), got {getattr(q_allow, 'dtype', type(q_allow))}")
+    if not isinstance(key_region, torch.Tensor) or key_region.dtype != torch.int32:
+        raise ValueError(f"key_region must be an int32 tensor, got {getattr(key_region, 'dtype', type(key_region))}")
+    B, Lq = q.shape[0], q.shape[1]
+    if tuple(q_allow.shape) != (B, Lq):
+        raise ValueError(f"q_allow must have shape (B, Lq) = {(B, Lq)}, got {tuple(q_allow.shape)}")
+    if tuple(key_region.shape) != (B, lkv):
+        raise ValueError(f"key_region must have shape (B, Lkv) = {(B, lkv)} over the extended key axis, got {tuple(key_region.shape)}")
+    for name, t in (("q_allow", q_allow), ("key_region", key_region)):
+        if t.device != q.device:
+            raise ValueError(f"{name} is on {t.device}, q on {q.device}")
+        if t.stride(-1) != 1 or t.stride(0) < t.shape[1]:
+            raise ValueError(f"{name}: the last axis must be contiguous (stride 1) and the rows at least its length apart")
+    if key_bias is not None:
+        raise ValueError("q_allow / key_region with key_bias: regions together with a bias are a follow-up (one C operand carries either)")
+    if ref_lens is not None:
+        raise ValueError("q_allow / key_region with ref_lens: key_region indexes the packed uniform key axis; regions together with counts are a follow-up")
+
+
+def region_masks(q_labels, key_labels, allow, *, self_len: int = 0, self_free: bool = True):
+    """The pair ``(q_allow, key_region)`` of :func:`shared_attention` from integer class labels and a rule.
+
+    ``q_labels`` ``(B, Lq)``, ``key_labels`` ``(B, Lkv)`` over the packed extended key axis: integer tensors (any integer dtype).
+    ``allow``: a ``(C, C)`` bool matrix - ``allow[c, d]``: a query of class ``c`` may attend keys of class ``d`` - or a ``(C,)``
+    integer tensor of bitmasks (bit ``d`` of ``allow[c]``).  ``C <= 32``.
+    ``self_free`` (with ``self_len`` > 0 leading keys of the query's own picture): those keys get region 31 whatever their label and
+    every row gets bit 31, so a token always sees its own picture; classes are then limited to 31 (region 31 is taken), and bit 31 of
+    a bitmask rule is dropped.
+    A key label outside ``[0, C)`` becomes region -1: nobody's.  A query label outside ``[0, C)`` gives a row that sees only what
+    ``self_free`` grants (nothing at all without it: zeros, ``lse = -inf``).
+    Returns ``q_allow`` int32 ``(B, Lq)`` (the storage of the 32-bit words) and ``key_region`` int32 ``(B, Lkv)``, on the labels'
+    device.  Plain torch elementwise work and one gather, no host sync."""
+    ql, kl = torch.as_tensor(q_labels), torch.as_tensor(key_labels)
+    for name, t in (("q_labels", ql), ("key_labels", kl)):
+        if t.dim() != 2 or t.dtype.is_floating_point or t.dtype == torch.bool or t.dtype.is_complex:
+            raise ValueError(f"{name} must be an integer (B, L) tensor, got {t.dtype} {tuple(t.shape)}")
+    if ql.shape[0] != kl.shape[0]:
+        raise ValueError(f"q_labels and key_labels differ in batch: {ql.shape[0]} vs {kl.shape[0]}")
+    dev = ql.device
+    kl = kl.to(dev)
+    rule = torch.as_tensor(allow).to(dev)
+    free = bool(self_free) and int(self_len) > 0
+    if not 0 <= int(self_len) <= kl.shape[1]:
+        raise ValueError(f"self_len {self_len} outside [0, Lkv = {kl.shape[1]}]")
+    C_ = rule.shape[0]
+    most = _lib.IR_REGION_MAX - 1 if free else _lib.IR_REGION_MAX
+    if C_ < 1 or C_ > most:
+        raise ValueError(f"allow has {C_} classes: 1 .. {most} fit{' (self_free takes region 31)' if free else ''}")
+    if rule.dim() == 2:
+        if rule.dtype != torch.bool or rule.shape[1] != C_:
+            raise ValueError(f"allow must be a (C, C) bool matrix or a (C,) tensor of bitmasks, got {rule.dtype} {tuple(rule.shape)}")
+        words = (rule.to(torch.int64) << torch.arange(C_, device=dev, dtype=torch.int64)).sum(dim=1)
+    elif rule.dim() == 1 and not (rule.dtype.is_floating_point or rule.dtype == torch.bool):
+        words = rule.to(torch.int64) & ((1 << C_) - 1)   # bits of classes that do not exist (and bit 31 under self_free) are dropped
+    else:
+        raise ValueError(f"allow must be a (C, C) bool matrix or a (C,) tensor of bitmasks, got {rule.dtype} {tuple(rule.shape)}")
+    ql64 = ql.to(torch.int64)
+    q_ok = (ql64 >= 0) & (ql64 < C_)
+    qa = torch.where(q_ok, words[ql64.clamp(0, C_ - 1)], torch.zeros((), dtype=torch.int64, device=dev))
+    kl64 = kl.to(torch.int64)
+    kr = torch.where((kl64 >= 0) & (kl64 < C_), kl64, torch.full((), -1, dtype=torch.int64, device=dev))
+    if free:
+        qa = qa | (1 << 31)
+        kr[:, :int(self_len)] = _lib.IR_REGION_MAX - 1
+    qa = torch.where(qa >= (1 << 31), qa - (1 << 32), qa)   # the same 32 bits as int32 storage
+    return qa.to(torch.int32).contiguous(), kr.to(torch.int32).contiguous()
 
 
 def _check_key_bias(kb, q, heads: int, lkv: int) -> None:
@@ -504,7 +590,8 @@ def shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, s
                      return_lse: bool = False, split: bool = True, q_prescaled: bool = False,
                      out_dtype: Optional[torch.dtype] = None, valid_refs: Optional[torch.Tensor] = None,
                      return_mass: bool = False, batch_invariant: bool = False, key_bias: Optional[torch.Tensor] = None,
-                     ref_lens: Optional[torch.Tensor] = None):
+                     ref_lens: Optional[torch.Tensor] = None, q_allow: Optional[torch.Tensor] = None,
+                     key_region: Optional[torch.Tensor] = None):
     """Fused extended self-attention (``ir_shared_attn_fwd``).
 
     Returns ``out`` (B, Lq, H*64) in q's dtype [, ``lse`` (B, H, Lq) fp32] [, ``mass`` (B, H, Lq, include_self + N) fp32:
@@ -544,6 +631,14 @@ def shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, s
     Raises with ``valid_refs`` (absent is not zero-filled) and with ``key_bias`` (the bias indexes the uniform key axis: a
     follow-up); the C ABI refuses ``n_refs == 0`` and tunings other than the default and the two 32-row forms, and
     :func:`attn_probs`, :func:`attn_segment_mass` and :func:`attn_rows` take no counts (``return_mass`` honours them).
+    ``q_allow`` / ``key_region`` (``ir_shared_attn_region_args``, both or neither; :func:`region_masks` builds them from labels):
+    per-QUERY masks in compact form.  ``key_region`` int32 ``(B, Lkv)`` gives every key of the packed extended key axis a region,
+    ``q_allow`` int32 / uint32 ``(B, Lq)`` gives every query row the 32-bit set of regions it may attend (bit g = region g); one rule
+    for all heads.  A pair that is not allowed has probability exactly 0; a key with a region outside ``[0, 31]`` is nobody's; a row
+    with no allowed key gives zeros, ``lse = -inf`` and zero masses.  ``lse`` and the masses are over the allowed keys.  Read when
+    the kernel runs (a captured call follows in-place updates); always the 32-row kernel, every tile walked.  With ``valid_refs``: a
+    dense call drops the promise and walks the zeros; a table call raises.  Raises with ``key_bias`` and with ``ref_lens`` (regions
+    together with a bias or with counts are a follow-up); the read-outs take no regions (``return_mass`` honours them).
     """
     q, k_self, v_self, ref_k, ref_v = _prep(q, k_self, v_self, ref_k, ref_v, heads, include_self, adain)
     if out_dtype not in (None, q.dtype, torch.float32):
@@ -551,7 +646,7 @@ def shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, s
     out = torch.empty((q.shape[0], q.shape[1], heads * HEAD_DIM), dtype=out_dtype or q.dtype, device=q.device)
     lse = torch.empty((q.shape[0], heads, q.shape[1]), dtype=torch.float32, device=q.device) if return_lse else None
     args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, lse, split, q_prescaled, valid_refs,
-                      batch_invariant, key_bias, ref_lens)
+                      batch_invariant, key_bias, ref_lens, q_allow, key_region)
     mass = None
     if return_mass:
         nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
@@ -577,13 +672,14 @@ def time_shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: i
                           include_self: bool = True, adain=None, iters: int = 10, split: bool = True,
                           q_prescaled: bool = False, valid_refs: Optional[torch.Tensor] = None, return_mass: bool = False,
                           batch_invariant: bool = False, key_bias: Optional[torch.Tensor] = None,
-                          ref_lens: Optional[torch.Tensor] = None) -> float:
+                          ref_lens: Optional[torch.Tensor] = None, q_allow: Optional[torch.Tensor] = None,
+                          key_region: Optional[torch.Tensor] = None) -> float:
     """Average ms per launch measured with HIP events on the launch stream (``bench.py``); ``valid_refs`` / ``return_mass`` /
     ``batch_invariant`` as in :func:`shared_attention` (the masses' finishing kernel is part of the timed launch)."""
     q, k_self, v_self, ref_k, ref_v = _prep(q, k_self, v_self, ref_k, ref_v, heads, include_self, adain)
     out = torch.empty((q.shape[0], q.shape[1], heads * HEAD_DIM), dtype=q.dtype, device=q.device)
     args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, None, split, q_prescaled, valid_refs,
-                      batch_invariant, key_bias, ref_lens)
+                      batch_invariant, key_bias, ref_lens, q_allow, key_region)
     if return_mass:
         nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
         mass = torch.empty((q.shape[0], heads, q.shape[1], nseg), dtype=torch.float32, device=q.device)
@@ -616,14 +712,15 @@ def shared_attention_kernel_name(q, k_self, v_self, ref_k=None, ref_v=None, *, h
                                  include_self: bool = True, adain=None, q_prescaled: bool = False,
                                  valid_refs: Optional[torch.Tensor] = None, return_mass: bool = False,
                                  batch_invariant: bool = False, key_bias: Optional[torch.Tensor] = None,
-                                 ref_lens: Optional[torch.Tensor] = None) -> str:
+                                 ref_lens: Optional[torch.Tensor] = None, q_allow: Optional[torch.Tensor] = None,
+                                 key_region: Optional[torch.Tensor] = None) -> str:
     """which kernel the dispatcher launches for these tensors (reporting only; ``valid_refs`` / ``return_mass`` as in
     :func:`shared_attention` - they decide the 128-row kernel's form and whether the default rule takes it;
     ``batch_invariant``: the kernel and pieces of the batch-invariant plan)"""
     q, k_self, v_self, ref_k, ref_v = _prep(q, k_self, v_self, ref_k, ref_v, heads, include_self, adain)
     out = torch.empty((q.shape[0], q.shape[1], heads * HEAD_DIM), dtype=q.dtype, device=q.device)
     args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, None, True, q_prescaled, valid_refs,
-                      batch_invariant, key_bias, ref_lens)
+                      batch_invariant, key_bias, ref_lens, q_allow, key_region)
     if return_mass:   # never written: the name is all this call computes
         nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
         mass = torch.empty((q.shape[0], heads, q.shape[1], nseg), dtype=torch.float32, device=q.device)
@@ -635,13 +732,14 @@ def shared_attention_plan(batch: int, len_q: int, heads: int, *, len_self: int =
                           dtype: torch.dtype = torch.bfloat16, include_self: bool = True, adain: bool = False,
                           q_prescaled: bool = False, valid_refs: bool = False, return_mass: bool = False,
                           out_dtype: Optional[torch.dtype] = None, workspace_bytes: Optional[int] = None, key_bias: bool = False,
-                          ref_lens: bool = False) -> dict:
+                          ref_lens: bool = False, regions: bool = False) -> dict:
     """the batch-invariant plan of a :func:`shared_attention` call of these sizes (``ir_shared_attn_plan``; host only - no tensor,
     no device): ``kernel`` (``IR_TUNE_*``), ``rows_per_item``, ``items_per_batch``, ``pieces_per_item``, ``workspace_bytes`` (the
     scratch of one launch over the batch, what :func:`shared_attention` allocates per call) and ``batch_per_launch`` - the entries
     one launch covers with a workspace of ``workspace_bytes`` bytes (default: the plan's own size).  ``ref_lens``: the call carries
-    per-reference counts (the pieces are planned for full references)"""
-    a = _lib.SharedAttnRaggedArgs() if ref_lens else _lib.SharedAttnBiasArgs() if key_bias else _lib.SharedAttnArgs()   # key_bias: one more per-entry parameter (the 32-row kernel at every len_q)
+    per-reference counts (the pieces are planned for full references); ``regions``: it carries ``q_allow`` / ``key_region`` (the
+    32-row kernel at every len_q, cut as the bias form is)"""
+    a = _lib.SharedAttnRegionArgs() if regions else _lib.SharedAttnRaggedArgs() if ref_lens else _lib.SharedAttnBiasArgs() if key_bias else _lib.SharedAttnArgs()   # key_bias: one more per-entry parameter (the 32-row kernel at every len_q)
     a.struct_size = C.sizeof(a)
     a.dtype = _DT[dtype]
     a.flags = _lib.IR_FLAG_BATCH_INVARIANT | (_lib.IR_FLAG_INCLUDE_SELF if include_self else 0) | \
@@ -676,6 +774,9 @@ def shared_attention_plan(batch: int, len_q: int, heads: int, *, len_self: int =
         a.key_bias = dummy
     if ref_lens:
         a.ref_lens, a.rl_sb = dummy, int(n_refs)
+    if regions:
+        a.q_allow, a.qa_sb = dummy, int(len_q)
+        a.key_region, a.kg_sb = dummy, (int(len_self) if include_self else 0) + int(n_refs) * int(len_ref)
     L = _lib.lib()
     if workspace_bytes is None:
         workspace_bytes = int(L.ir_shared_attn_workspace_bytes_for(C.byref(a)))
