@@ -86,6 +86,11 @@ def main(argv=None):
                     help="keep a centred elliptical region of that area of every reference (e.g. 0.5): the kept tokens are packed to the "
                          "front of their segments once (ops.compact_refs) and the shared layers walk the counts (ref_lens); prints the top "
                          "shared layer's attention masses with and without")
+    ap.add_argument("--adain-keep", type=float, default=None, metavar="FRACTION",
+                    help="mask-aware AdaIN (adain_weights): the statistics behind the affine are taken over a centred elliptical region of "
+                         "that area of every reference and of the image alone; prints the largest change of the affine (a, b) and of the "
+                         "output against the unmasked run.  With --compact-refs the packed references carry kept-token statistics "
+                         "(ops.token_stats_weighted(packed_v, lens=lens)) instead of those of the full references")
     ap.add_argument("--regions", action="store_true",
                     help="one more cached frame under a per-query restriction by region labels (region_labels / region_allow): synthetic label "
                          "pictures - a 4 x 4 grid of classes, shifted by n cells on reference n - and the rule \"own class only, self "
@@ -237,6 +242,49 @@ def main(argv=None):
             for b in range(B):
                 print(f"identity {b}: mass [self?] ++ references  full {fmt(m0[b])}  |  {kept} of {ck[8].shape[2]} tokens kept: {fmt(m1[b])}")
             assert bool(torch.isfinite(zc).all()) and float((m1.sum(-1) - 1).abs().max()) < 2e-3
+        # "Renormalise the face with the FACE's statistics": the AdaIN affine comes from the statistics over the tokens of a centred
+        # region of the image and of every reference alone (adain_weights: a weight picture per side, sampled by every shared layer
+        # at its own token centres) - the background no longer pollutes mean and std.  The affine is an input of the attention,
+        # so this composes with the compacted references above: their statistics are then taken over the packed rows.
+        if args.adain_keep is not None:
+            import math
+            frac = float(args.adain_keep)
+            assert 0.0 < frac <= 1.0, "--adain-keep needs a fraction in (0, 1]"
+            a = 64 * math.sqrt(frac / (1.25 * math.pi))
+            yy, xx = torch.meshgrid(torch.arange(64) + 0.5 - 32, torch.arange(64) + 0.5 - 32, indexing="ij")
+            region = ((xx / a) ** 2 + (yy / (1.25 * a)) ** 2 <= 1.0).to(dev)
+            self_w, ref_w = region.expand(B, 64, 64).contiguous(), region.expand(B, N, 64, 64).contiguous()
+            affines, real = [], ops.shared_attention
+
+            def recording(*a_, **kw_):          # the affine every shared layer hands the attention, in layer order
+                if kw_.get("adain") is not None:
+                    affines.append(kw_["adain"])
+                return real(*a_, **kw_)
+            ops.shared_attention = recording
+            try:
+                kw = {"ref_keys": ck, "ref_values": cv, "ref_stats": cs}
+                z0 = unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1), cross_attention_kwargs=kw).sample
+                plain, affines = affines, []
+                zm = unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1),
+                          cross_attention_kwargs={"ref_keys": ck, "ref_values": cv, "adain_weights": (self_w, ref_w)}).sample
+                masked, affines = affines, []
+                da = max(float((m[0] - p[0]).abs().max()) for m, p in zip(masked, plain))
+                db = max(float((m[1] - p[1]).abs().max()) for m, p in zip(masked, plain))
+                print(f"--adain-keep {frac}: {int(region.sum())} of 4096 map pixels kept; largest change of a {da:.3f}, of b {db:.3f}, of the "
+                      f"output {float((zm.float() - z0.float()).abs().max()):.3f} (max|output| {float(z0.float().abs().max()):.3f})")
+                assert bool(torch.isfinite(zm).all()) and len(masked) == len(plain) == 9
+                if args.compact_refs is not None:
+                    # the compacted call of --compact-refs with kept-token statistics: one counted pass over the packed V per layer
+                    kept_stats = [ops.token_stats_weighted(t[1], heads=t[1].shape[-1] // 64, lens=t[2]) for t in packed]
+                    zk = unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1),
+                              cross_attention_kwargs={"ref_keys": [t[0] for t in packed], "ref_values": [t[1] for t in packed],
+                                                      "ref_stats": kept_stats, "ref_lens": [t[2] for t in packed],
+                                                      "adain_weights": (self_w, None)}).sample
+                    print(f"  with --compact-refs {args.compact_refs}: kept-token statistics of the packed references; largest change of the "
+                          f"output against the compacted call with full-reference statistics {float((zk.float() - zc.float()).abs().max()):.3f}")
+                    assert bool(torch.isfinite(zk).all())
+            finally:
+                ops.shared_attention = real
         # "Eye tokens draw from eye tokens of the references, mouth from mouth, the picture itself is free": a per-QUERY restriction.
         # Label pictures (a face parsing map; here a coarse grid of classes) and a class-by-class rule go in once; every shared layer
         # samples the labels at its own token centres and hands the kernel one 32-bit word per query row and one small integer per

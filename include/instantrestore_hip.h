@@ -198,7 +198,8 @@ typedef struct ir_shared_attn_table_args {
  * 4-byte quantities (any float pointer, any element strides >= 0); segment starts need no alignment, len_self and len_ref are arbitrary.
  * Nothing outside the Lkv floats of a (b, h) row is used.
  * AdaIN is unchanged by a bias: the affine comes from the statistics over ALL reference tokens, masked or not (the reference's adain()
- * knows no mask); a masked reference merely takes no attention.
+ * knows no mask); a masked reference merely takes no attention.  Statistics over the kept tokens alone are an opt-in of their own:
+ * ir_token_stats_weighted + ir_adain_affine_from_stats make the affine, which is an input here.
  * Per-reference weights are a special case: weight w_n on reference n is the bias log(w_n) on every key of its segment (w_n = 0:
  * masked), with seg_mass as the read-back.  Masked is not zeroed: a zero-filled reference (valid_refs) keeps exp(0) per key.
  *
@@ -667,6 +668,54 @@ int ir_adain_stats_cached(int32_t dtype, int32_t batch, int32_t heads, int32_t l
 int ir_token_stats(int32_t dtype, int32_t batch, int32_t heads, int32_t n_mats, int32_t len,
                    const void* x, int64_t x_sb, int64_t x_sn, int64_t x_sl, int64_t x_sh,
                    float* mean, float* std, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * ir_token_stats_weighted - ir_token_stats over WEIGHTED or COUNTED tokens (mask-aware AdaIN statistics).
+ *
+ * Per (b, m, head, channel), with the effective weight of token t   w_t = (t < c[b,m]) ? w[b,m,t] : 0:
+ *      W = sum w_t,   W2 = sum w_t^2,   mean = sum w_t x_t / W,   M2 = sum w_t (x_t - mean)^2,   std = sqrt(M2 / (W - W2 / W))
+ * - the unbiased estimator under reliability weights.  For 0/1 weights the divisor is count - 1: mean(dim=1) / std(dim=1)
+ * (attn_processors.py:9-10) over the kept tokens alone.
+ *   x (B, M, len, H, 64) strides x_* (the 16-byte rule of ir_token_stats);  mean, std: fp32 (B, M, H, 64), std WITHOUT eps
+ *   weights: fp32, w[b,m,t] = weights[b * w_sb + m * w_sn + t] >= 0 (w_sb = 0: one set shared by the batch), or NULL (= 1).
+ *            Negative, NaN or Inf weights: undefined.
+ *   lens:    int32, c[b,m] = clamp(lens[b * ln_sb + m], 0, len), or NULL (= len)
+ *   wsum:    optional fp32 (B, M): W, the effective token count; NULL = off
+ *   workspace >= ir_token_stats_weighted_workspace_bytes(batch, heads, n_mats, len)  (chunks x heads x matrices; > 0 for len >= 1)
+ * Zero-weight tokens: a token with w_t == 0 contributes nothing whatever its bytes, NaN and Inf included - it is selected
+ * away, never multiplied by 0; rows at or behind a count are never used; nothing outside the `len` floats of a weights row or the
+ * n_mats ints of a lens row is read.
+ * Never NaN: W == 0 gives mean 0, std 0 (the statistics of a zero-filled reference); W - W2 / W <= 0 (one effective token)
+ * gives that token's value as the mean and std 0 (so len == 1 gives (x, 0) where ir_token_stats gives NaN).
+ * Bit for bit: for 2 <= len < 2^24, weights == NULL && lens == NULL, weights of all 1.0f, and lens == len each produce the bytes
+ * of ir_token_stats on the same tensor (same row slots, same shifted sums, same Chan merge over ascending 256-row chunks).
+ * Order: the order of evaluation is a function of len only - a (b, m) result does not depend on the batch, its position, its
+ * neighbours, the grid or the stream.  No atomics, one writer per output, two launches, asynchronous and capturable; weights
+ * and lens are read when the kernel RUNS: a replayed hipGraph follows in-place updates of them.
+ * Checked in this order, before any launch, no device pointer dereferenced: IR_ERR_UNSUPPORTED: dtype; IR_ERR_INVALID_ARG:
+ * a size <= 0, NULL x, NULL mean, NULL std, NULL workspace; IR_ERR_UNSUPPORTED: x not 16-byte aligned or an x stride that is
+ * negative or no multiple of 8; IR_ERR_INVALID_ARG (with weights): w_sn < len, w_sb < 0; (with lens): ln_sb < n_mats;
+ * IR_ERR_UNSUPPORTED: weights, lens, mean, std, wsum not 4-byte aligned, batch * n_mats or heads > 65535; IR_ERR_WORKSPACE: a
+ * workspace that is too small.
+ */
+size_t ir_token_stats_weighted_workspace_bytes(int32_t batch, int32_t heads, int32_t n_mats, int32_t len);
+int ir_token_stats_weighted(int32_t dtype, int32_t batch, int32_t heads, int32_t n_mats, int32_t len,
+                            const void* x, int64_t x_sb, int64_t x_sn, int64_t x_sl, int64_t x_sh,
+                            const float* weights, int64_t w_sb, int64_t w_sn, const int32_t* lens, int64_t ln_sb,
+                            float* mean, float* std, float* wsum, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * ir_adain_affine_from_stats - the AdaIN affine from FINISHED statistics (whoever made them, with whatever weights).
+ *
+ *   style_mean, style_std: fp32 (B, H, 64);  content_mean, content_std: fp32 (B, N, H, 64);  a, b: fp32 (B, N, H, 64); std WITHOUT eps
+ *      sd_v = style_std + eps,   a = sd_v / (content_std + eps),   b = style_mean - content_mean * a
+ * with the constant-content rule of the other AdaIN entry points (content_std == 0: a = 2^-24 sd_v).  The expression of
+ * ir_adain_stats_cached: ir_token_stats(v_self) followed by this call gives its (a, b) bit for bit.  One launch, asynchronous,
+ * capturable.  IR_ERR_INVALID_ARG: a size <= 0, a NULL pointer; IR_ERR_UNSUPPORTED: a pointer that is not 4-byte aligned.
+ */
+int ir_adain_affine_from_stats(int32_t batch, int32_t heads, int32_t n_refs,
+                               const float* style_mean, const float* style_std, const float* content_mean, const float* content_std,
+                               float eps, float* a, float* b, void* stream);
 
 /*
  * ir_adain_apply - standalone AdaIN application  y = x * a + b  (fp32 math, stored in dtype).

@@ -119,6 +119,10 @@ SYMBOLS = {
                                  f32, vp, vp, vp, C.c_size_t, vp]),
     "ir_adain_stats_cached": (C.c_int, [i32, i32, i32, i32, i32, vp, i64, i64, i64, vp, vp, f32, vp, vp, vp, C.c_size_t, vp]),
     "ir_token_stats": (C.c_int, [i32, i32, i32, i32, i32, vp, i64, i64, i64, i64, vp, vp, vp, C.c_size_t, vp]),
+    "ir_token_stats_weighted_workspace_bytes": (C.c_size_t, [i32, i32, i32, i32]),
+    "ir_token_stats_weighted": (C.c_int, [i32, i32, i32, i32, i32, vp, i64, i64, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp,
+                                          C.c_size_t, vp]),
+    "ir_adain_affine_from_stats": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp]),
     "ir_adain_apply": (C.c_int, [i32, i32, i32, i32, i32, vp, i64, i64, i64, i64, vp, vp,
                                  vp, i64, i64, i64, i64, vp]),
     "ir_tensor2im_u8": (C.c_int, [i32, i32, i32, i32, i32, vp, i64, i64, i64, i64, vp, vp]),

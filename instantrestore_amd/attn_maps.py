@@ -169,6 +169,40 @@ def token_labels(label_image, side: int):
     return picked.reshape(img.shape[0], -1).contiguous()
 
 
+def token_weights(weight_image, side: int):
+    """per-token AdaIN weights from a weight picture (a soft face mask, a confidence map): float or bool ``(B, Hpx, Wpx)`` ->
+    fp32 ``(B, side * side)``, or ``(B, N, Hpx, Wpx)`` -> ``(B, N, side * side)`` (one row per reference: the shape
+    ``ops.token_stats_weighted`` takes), row-major on the ``side x side`` token grid.  A weight is SAMPLED at the token's centre
+    exactly as :func:`token_labels` samples a label - so a 0/1 picture keeps the tokens whose label picture says 1 - never
+    averaged: a token is in or out (or carries the picture's own soft value).  Index arithmetic on the picture's device, no sync."""
+    import torch
+    img = torch.as_tensor(weight_image)
+    if img.dim() not in (3, 4) or img.dtype.is_complex:
+        raise ValueError(f"token_weights: weight_image must be a real (B, Hpx, Wpx) or (B, N, Hpx, Wpx) tensor, got {img.dtype} {tuple(img.shape)}")
+    side = int(side)
+    hpx, wpx = int(img.shape[-2]), int(img.shape[-1])
+    if side < 1 or hpx < 1 or wpx < 1:
+        raise ValueError(f"token_weights: side {side} and picture {hpx} x {wpx} must be >= 1")
+    t = torch.arange(side, device=img.device, dtype=torch.int64)
+    py = torch.div((2 * t + 1) * hpx, 2 * side, rounding_mode="floor")
+    px = torch.div((2 * t + 1) * wpx, 2 * side, rounding_mode="floor")
+    picked = img.index_select(-2, py).index_select(-1, px)          # (..., side, side)
+    return picked.reshape(*img.shape[:-2], side * side).to(torch.float32).contiguous()
+
+
+def weights_from_keep(keep):
+    """a ``keep`` mask of ``ops.compact_refs`` / ``ref_token_keep`` - bool ``(B, N, len_ref)`` or ``(B, N, S, S)`` - as the fp32
+    ``(B, N, len_ref)`` weights of ``ops.token_stats_weighted`` / ``adain_weights``: 1 on a kept token, 0 on a dropped one, so the
+    AdaIN statistics are those of the tokens the attention still sees."""
+    import torch
+    k = torch.as_tensor(keep)
+    if k.dim() == 4:
+        k = k.reshape(k.shape[0], k.shape[1], -1)
+    if k.dim() != 3:
+        raise ValueError(f"weights_from_keep: keep must be (B, N, len_ref) or (B, N, S, S), got {tuple(k.shape)}")
+    return (k != 0).to(torch.float32).contiguous()
+
+
 def soft_match_field(sums, mass, rows, side: int):
     """``(sums, mass)`` of ``ops.attn_transfer`` with :func:`coordinate_payload` - ``sums`` ``(..., R, S, 2)``, ``mass`` ``(..., R, S)``,
     torch tensors - -> ``(pos, disp, conf)``: the expected ``(y, x)`` of every (row, segment), ``sums / mass``, fp32

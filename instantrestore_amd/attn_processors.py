@@ -192,6 +192,54 @@ def _region_pair(region_labels, region_allow, batch: int, len_q: int, len_self: 
     return pair
 
 
+# (self weights, reference weights) of ``adain_weights``, sampled once per (kwargs identity and version, layer geometry) the way
+# _REGION_PAIRS caches region pairs
+_ADAIN_WEIGHTS: dict = {}
+_ADAIN_WEIGHTS_MAX = 8
+
+
+def _weights_on_grid(weights, length: int, refs: bool, device):
+    """a weight picture ``(B, [N,] Hpx, Wpx)`` or per-token weights ``(B, [N,] L)`` (the row-major picture of their own square grid),
+    float or bool, sampled at the token centres of the square grid of ``length`` tokens (``attn_maps.token_weights``) -> fp32
+    ``(B, [N,] length)`` on ``device``"""
+    from . import attn_maps as _maps
+    what = "adain_weights: the reference weights" if refs else "adain_weights: the self weights"
+    t = torch.as_tensor(weights)
+    pictures = 4 if refs else 3
+    if t.dim() == pictures - 1:      # per-token weights
+        if t.shape[-1] == length:
+            return t.to(device=device, dtype=torch.float32).contiguous()
+        s = _maps._square_side(t.shape[-1], f"{what}' length")
+        t = t.reshape(*t.shape[:-1], s, s)
+    if t.dim() != pictures:
+        raise ValueError(f"{what} must be a weight picture {'(B, N, Hpx, Wpx)' if refs else '(B, Hpx, Wpx)'} or per-token weights, "
+                         f"got {tuple(torch.as_tensor(weights).shape)}")
+    return _maps.token_weights(t, _maps._square_side(length, what)).to(device)
+
+
+def _adain_weight_pair(adain_weights, batch: int, len_self: int, n_refs: int, len_ref: int, device):
+    if not isinstance(adain_weights, (tuple, list)) or len(adain_weights) != 2:
+        raise ValueError("adain_weights must be the pair (self_weights, ref_weights); either may be None")
+    self_w, ref_w = adain_weights
+    ver = lambda t: (id(t), getattr(t, "_version", None)) if t is not None else None
+    key = (ver(self_w), ver(ref_w), batch, len_self, n_refs, len_ref, str(device))
+    hit = _ADAIN_WEIGHTS.get(key)
+    if hit is not None and hit[0] is self_w and hit[1] is ref_w:
+        return hit[2]
+    sw = None if self_w is None else _weights_on_grid(self_w, len_self, False, device)
+    rw = None if ref_w is None else _weights_on_grid(ref_w, len_ref, True, device)
+    if sw is not None and tuple(sw.shape) != (batch, len_self):
+        raise ValueError(f"adain_weights: self weights of {tuple(sw.shape)} tokens for a batch of {batch} with {len_self} tokens")
+    if rw is not None and tuple(rw.shape) != (batch, n_refs, len_ref):
+        raise ValueError(f"adain_weights: reference weights of {tuple(rw.shape)} tokens for a batch of {batch} with {n_refs} references "
+                         f"of {len_ref} tokens")
+    pair = (sw, rw)
+    while len(_ADAIN_WEIGHTS) >= _ADAIN_WEIGHTS_MAX:
+        _ADAIN_WEIGHTS.pop(next(iter(_ADAIN_WEIGHTS)))
+    _ADAIN_WEIGHTS[key] = (self_w, ref_w, pair)
+    return pair
+
+
 def _kv_source(attn, st: _Prepared) -> torch.Tensor:
     if st.encoder is None:
         return st.hidden
@@ -444,6 +492,8 @@ class AttnProcessor(nn.Module):
         self.v_part = None                # ... or (round 4) the partials the q/k/v GEMM left behind (ops.ColumnStats): merged
                                           # by the shared layer's affine kernel, or into (mean, std) on demand
         self.batch_invariant = False      # ABI v10 (plain attribute; set_batch_invariant): batch-invariant GEMMs and attention
+        self.capture_stats_weights = None   # kv_harvest.enable_ref_stats(..., weights=): the statistics above over WEIGHTED tokens -
+                                            # a weight picture (B, N, Hpx, Wpx) or per-token weights (B, N, L), float or bool
 
     def reset(self):
         self.keys, self.values = None, None
@@ -459,7 +509,15 @@ class AttnProcessor(nn.Module):
         every shared layer of every frame.  ``vstats``: the partials the q/k/v GEMM left behind (round 4: no pass over V,
         one 64-thread-per-(set, head) merge); without them ``ir_token_stats`` reads V."""
         self.v_mean, self.v_std, self.v_part = None, None, None     # never hand a later harvest the statistics of an earlier capture
-        if self.capture_stats and self.values.is_cuda:
+        weights = getattr(self, "capture_stats_weights", None)
+        if self.capture_stats and self.values.is_cuda and weights is not None:
+            # mask-aware statistics: one weighted pass over V (the GEMM's partials are unweighted); the pair travels like any other
+            w = _weights_on_grid(weights, self.values.shape[1], True, self.values.device)
+            if w.shape[0] * w.shape[1] != self.values.shape[0]:
+                raise ValueError(f"capture_stats_weights of {tuple(w.shape)} tokens for {self.values.shape[0]} captured references")
+            m, sd = _ops.token_stats_weighted(self.values.unsqueeze(1), heads=attn.heads, weights=w.reshape(-1, 1, w.shape[-1]))
+            self.v_mean, self.v_std = m[:, 0], sd[:, 0]
+        elif self.capture_stats and self.values.is_cuda:
             if vstats is not None:
                 self.v_part = vstats       # merged where they are consumed (kv_harvest / SharedAttnProcessor): no launch here
             else:
@@ -474,8 +532,8 @@ class AttnProcessor(nn.Module):
                 self.ready.record(self.stream)
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
-                ref_weights=None, ref_token_keep=None, ref_lens=None, region_labels=None, region_allow=None):
-        # ref_weights / ref_token_keep / ref_lens / region_labels / region_allow: accepted and ignored (no references here), like ref_valid elsewhere
+                ref_weights=None, ref_token_keep=None, ref_lens=None, region_labels=None, region_allow=None, adain_weights=None):
+        # ref_weights / ref_token_keep / ref_lens / region_labels / region_allow / adain_weights: accepted and ignored (no references here), like ref_valid elsewhere
         st = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
         self.is_self_attn = encoder_hidden_states is None
         group = self.stop_after_capture
@@ -487,7 +545,8 @@ class AttnProcessor(nn.Module):
             self._mark_ready()
             raise ReferenceCaptureComplete()
         bi = bool(self.batch_invariant)
-        query, key, value, presc, vstats = _project_qkv(attn, st, want_stats=bool(self.capture_stats), bi=bi)
+        query, key, value, presc, vstats = _project_qkv(
+            attn, st, want_stats=bool(self.capture_stats) and getattr(self, "capture_stats_weights", None) is None, bi=bi)
         self.keys, self.values = key, value  # consumed in place by the shared layers: no copies
         self._stash_stats(attn, vstats)
         self._mark_ready()
@@ -523,8 +582,8 @@ class FaceIDAttnProcessor(nn.Module):
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                 ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None, ref_weights=None, ref_token_keep=None,
-                ref_lens=None, region_labels=None, region_allow=None):
-        # ref_* / region_* accepted and ignored, like the reference: the host forwards ONE cross_attention_kwargs dict to every processor
+                ref_lens=None, region_labels=None, region_allow=None, adain_weights=None):
+        # ref_* / region_* / adain_weights accepted and ignored, like the reference: the host forwards ONE cross_attention_kwargs dict to every processor
         # (unet.py / diffusers), so whatever the harvest hands SharedAttnProcessor (ref_valid included) arrives here too
         st = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
         self.is_self_attn = encoder_hidden_states is None
@@ -638,12 +697,12 @@ class SharedAttnProcessor(nn.Module):
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                 ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None, ref_weights=None, ref_token_keep=None,
-                ref_lens=None, region_labels=None, region_allow=None):
+                ref_lens=None, region_labels=None, region_allow=None, adain_weights=None):
         """``attention_mask``: additive, ``(B, Lkv)``, ``(B, 1, Lkv)`` or ``(B * H, 1, Lkv)`` over this layer's key axis (with references: the
         extended one) - the fused kernel's key bias.  ``ref_weights`` ``(B, N)`` >= 0 and ``ref_token_keep`` (bool ``(B, N, len_ref)`` or
         ``(B, N, S, S)``), shared layers only (ignored elsewhere, as ``ref_valid`` is): ``ops.key_bias`` turns them into the bias -
         ``log w`` on a reference's keys, 0 / dropped tokens MASKED (no attention at all, unlike a zero-filled reference).  AdaIN
-        statistics stay those of every reference token.  ``save_attention_mass`` reads the effect back; ``save_self_attentions`` /
+        statistics stay those of every reference token unless ``adain_weights`` (below) says otherwise.  ``save_attention_mass`` reads the effect back; ``save_self_attentions`` /
         ``attention_rows_index`` with a bias raise (the read-out kernels do not take the bias yet).
         ``ref_valid`` (optional, round 5): int32 ``(B,)`` device tensor from the harvest (``kv_harvest`` ``with_valid``) when
         it zero-filled references ``n >= valid[b]`` (pix2pix_turbo.py:269-273): the kernel then closes those all-zero segments
@@ -654,8 +713,9 @@ class SharedAttnProcessor(nn.Module):
         existing keys alone (``ir_shared_attn_ragged_args``).  Raises with ``ref_valid`` (absent is not zero-filled), with a mask /
         ``ref_weights`` / ``ref_token_keep`` (counts with a key bias are a follow-up; ``ref_token_keep`` alone keeps running the bias
         path), with ``save_self_attentions`` and ``attention_rows_index`` (the read-out kernels would walk the tails);
-        ``save_attention_mass`` works.  With ``use_adain`` it needs ``ref_stats``: the content statistics are those of the FULL
-        reference, taken before compaction - the rule of the bias path, so a compacted call and a masked call agree.
+        ``save_attention_mass`` works.  With ``use_adain`` it needs ``ref_stats``: by default the content statistics of the FULL
+        reference, taken before compaction - the rule of the bias path, so a compacted call and a masked call agree - or, with
+        ``adain_weights``, kept-token statistics (``ops.token_stats_weighted(packed_v, heads=H, lens=lens)``).
         ``region_labels = (query_labels, ref_labels)`` with ``region_allow`` (optional), shared layers only (ignored elsewhere, as
         ``ref_valid`` is): a per-QUERY restriction by class labels - "eye tokens draw from eye tokens of the references".  The labels
         are integer label pictures (``(B, Hpx, Wpx)`` of this image, ``(B, N, Hpx, Wpx)`` of its references: a face parsing map) or
@@ -663,10 +723,22 @@ class SharedAttnProcessor(nn.Module):
         (``attn_maps.token_labels``).  ``region_allow`` is the rule of ``ops.region_masks``: a ``(C, C)`` bool matrix (row = query class,
         column = key class) or ``(C,)`` bitmasks, at most 31 classes.  With ``train_input`` the self keys carry the query labels and
         every token sees its own picture whatever the rule (``self_free``).  The pair ``(q_allow, key_region)`` is built
-        once per key-axis geometry and cached by tensor identity and version.  AdaIN is unchanged; ``save_attention_mass`` honours the
+        once per key-axis geometry and cached by tensor identity and version.  AdaIN is unchanged (see ``adain_weights``); ``save_attention_mass`` honours the
         regions.  Raises, before anything is launched, with an attention mask, ``ref_weights``, ``ref_token_keep`` or ``ref_lens``
         (regions with a key bias or with counts are a follow-up) and with ``save_self_attentions`` or any read-out attribute (the
-        read-out kernels do not take regions yet); with ``ref_valid`` a dense call walks the zero-filled references, a table call raises."""
+        read-out kernels do not take regions yet); with ``ref_valid`` a dense call walks the zero-filled references, a table call raises.
+        ``adain_weights = (self_weights, ref_weights)`` (optional; either may be ``None``), shared layers with ``use_adain`` only
+        (accepted and ignored elsewhere, as ``ref_valid`` is): mask-aware AdaIN - the statistics behind the affine are taken over
+        weighted tokens (``ops.token_stats_weighted``: weight 0 drops a token, 0/1 weights give the statistics of the kept tokens
+        alone).  Each element is a weight picture (``(B, Hpx, Wpx)`` of this image, ``(B, N, Hpx, Wpx)`` of its references) or
+        per-token weights of a square grid (``(B, L)`` / ``(B, N, L)``), float or bool; every layer samples them at its own token
+        centres (``attn_maps.token_weights``), once per geometry, cached by tensor identity and version.  The style statistics are
+        one weighted pass over this layer's V (the GEMM's statistics tail is not used: its partials are unweighted).  The content
+        statistics are ``ref_stats`` of this layer when given - finished by the caller with the weights they wanted, e.g.
+        ``ops.token_stats_weighted(packed_v, lens=lens)`` after a compaction; the pair's reference weights are then not consulted -
+        otherwise one weighted pass over the dense reference V; a ``RefKVTable`` without ``ref_stats`` raises as without the
+        kwarg, and so does ``ref_lens`` without ``ref_stats``.  The affine comes from ``ops.adain_affine`` and enters the
+        attention as any other: masks, ``ref_weights``, ``ref_token_keep``, regions and the batch-invariant mode work with it."""
         st = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
         shared = self.self_attn_idx is not None and ref_keys is not None and ref_values is not None
         regions = shared and region_labels is not None
@@ -689,7 +761,8 @@ class SharedAttnProcessor(nn.Module):
         # precomputed (``ref_stats``): without them ir_adain_stats reads every V anyway and would throw the partials away
         have_cstats = bool(shared and ref_stats is not None and ref_stats[self.self_attn_idx] is not None)
         bi = bool(getattr(self, "batch_invariant", False))
-        query, key, value, presc, vstats = _project_qkv(attn, st, want_stats=bool(self.use_adain and have_cstats), bi=bi)
+        weighted = bool(shared and self.use_adain and adain_weights is not None)    # mask-aware AdaIN: a branch of its own below
+        query, key, value, presc, vstats = _project_qkv(attn, st, want_stats=bool(self.use_adain and have_cstats and not weighted), bi=bi)
 
         ref_k = ref_v = None
         include_self = True
@@ -750,7 +823,24 @@ class SharedAttnProcessor(nn.Module):
                 # only V_self is read here - 1/(N+1) of the bytes, the same (a, b) bit for bit
                 # Round 4: the style statistics arrive as the partials this layer's own q/k/v GEMM left behind (``vstats``):
                 # with them and the content statistics nothing of V is read here at all - one small launch
-                if hasattr(cstats, "finished"):
+                if weighted:
+                    # mask-aware AdaIN: the style statistics over this layer's weighted tokens; the content statistics as the
+                    # caller finished them (``ref_stats``), else over the dense references' weighted tokens
+                    self_w, ref_w = _adain_weight_pair(adain_weights, value.shape[0], value.shape[1], ref_v.shape[1], ref_v.shape[2], value.device)
+                    if hasattr(cstats, "finished"):
+                        content = cstats.finished()
+                    elif cstats is not None:
+                        content = cstats
+                    elif isinstance(ref_v, _RefKVTable):
+                        raise ValueError("use_adain with RefKVTable references needs ref_stats: cache the identities with their AdaIN content "
+                                         "statistics (get_conditioning_keys_values(..., with_stats=True[, stats_weights=...])) and pass the "
+                                         "stats of ReferenceKVCache.assemble_tables")
+                    else:
+                        content = _ops.token_stats_weighted(ref_v, heads=attn.heads, weights=ref_w)
+                    style = _ops.token_stats_weighted(value.unsqueeze(1), heads=attn.heads,
+                                                      weights=None if self_w is None else self_w.unsqueeze(1))
+                    affine = _ops.adain_affine(style, content)
+                elif hasattr(cstats, "finished"):
                     if vstats is not None:    # both sides as partials: ONE launch merges them into the affine
                         affine = _ops.adain_affine_from_partials(vstats, value.shape[0], value.shape[1], ref_v.shape[1], ref_v.shape[2],
                                                                  content=cstats.part, valid=cstats.valid)

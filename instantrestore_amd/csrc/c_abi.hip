@@ -670,6 +670,71 @@ int ir_token_stats(int32_t dtype, int32_t batch, int32_t heads, int32_t n_mats, 
   return IR_OK;
 }
 
+static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+size_t ir_token_stats_weighted_workspace_bytes(int32_t batch, int32_t heads, int32_t n_mats, int32_t len) {
+  if (batch <= 0 || heads <= 0 || n_mats <= 0 || len <= 0) return 0;
+  return (size_t)batch * (size_t)n_mats * (size_t)heads * (size_t)adain_nchunk(len, len) * IR_ADAIN_W_STRIDE * sizeof(float);
+}
+
+// Checked in this order (the header states it): dtype, sizes, NULL x / mean / std / workspace, the 16-byte rule of x, the
+// weights' strides, the counts' stride, the 4-byte alignments, the grid, the workspace
+int ir_token_stats_weighted(int32_t dtype, int32_t batch, int32_t heads, int32_t n_mats, int32_t len,
+                            const void* x, int64_t x_sb, int64_t x_sn, int64_t x_sl, int64_t x_sh,
+                            const float* weights, int64_t w_sb, int64_t w_sn, const int32_t* lens, int64_t ln_sb,
+                            float* mean, float* std, float* wsum, void* workspace, size_t workspace_bytes, void* stream) {
+  if (dtype != IR_DTYPE_F16 && dtype != IR_DTYPE_BF16) return fail(IR_ERR_UNSUPPORTED, "dtype %d: only fp16 (0) and bf16 (1) are implemented", dtype);
+  if (batch <= 0 || heads <= 0 || n_mats <= 0 || len <= 0)
+    return fail(IR_ERR_INVALID_ARG, "batch %d, heads %d, n_mats %d and len %d must be > 0", batch, heads, n_mats, len);
+  if (x == nullptr) return fail(IR_ERR_INVALID_ARG, "x is NULL");
+  if (mean == nullptr) return fail(IR_ERR_INVALID_ARG, "mean is NULL");
+  if (std == nullptr) return fail(IR_ERR_INVALID_ARG, "std is NULL");
+  if (workspace == nullptr) return fail(IR_ERR_INVALID_ARG, "workspace is NULL");
+  if (!aligned16(x)) return fail(IR_ERR_UNSUPPORTED, "x must be 16-byte aligned");
+  const int64_t st[] = {x_sb, x_sn, x_sl, x_sh};
+  for (int64_t s : st) if (!stride_ok(s)) return fail(IR_ERR_UNSUPPORTED, "x stride %lld must be a non-negative multiple of 8", (long long)s);
+  if (weights != nullptr) {
+    if (w_sn < len) return fail(IR_ERR_INVALID_ARG, "weights matrix stride w_sn %lld must be >= len %d", (long long)w_sn, len);
+    if (w_sb < 0) return fail(IR_ERR_INVALID_ARG, "weights batch stride w_sb %lld must be >= 0", (long long)w_sb);
+  }
+  if (lens != nullptr && ln_sb < n_mats) return fail(IR_ERR_INVALID_ARG, "lens row stride ln_sb %lld must be >= n_mats %d", (long long)ln_sb, n_mats);
+  if (!aligned4(weights)) return fail(IR_ERR_UNSUPPORTED, "weights must be 4-byte aligned");
+  if (!aligned4(lens)) return fail(IR_ERR_UNSUPPORTED, "lens must be 4-byte aligned");
+  if (!aligned4(mean)) return fail(IR_ERR_UNSUPPORTED, "mean must be 4-byte aligned");
+  if (!aligned4(std)) return fail(IR_ERR_UNSUPPORTED, "std must be 4-byte aligned");
+  if (!aligned4(wsum)) return fail(IR_ERR_UNSUPPORTED, "wsum must be 4-byte aligned");
+  if ((int64_t)batch * n_mats > 65535 || heads > 65535) return fail(IR_ERR_UNSUPPORTED, "grid too large: batch * n_mats and heads must be <= 65535");
+  const size_t need = ir_token_stats_weighted_workspace_bytes(batch, heads, n_mats, len);
+  if (workspace_bytes < need) return fail(IR_ERR_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, need);
+  TokenStatsWKParams p;
+  memset(&p, 0, sizeof(p));
+  p.x = x; p.x_sb = x_sb; p.x_sn = x_sn; p.x_sl = x_sl; p.x_sh = x_sh;
+  p.weights = weights; p.w_sb = w_sb; p.w_sn = w_sn;
+  p.lens = lens; p.ln_sb = ln_sb;
+  p.ws = (float*)workspace; p.mean = mean; p.std = std; p.wsum = wsum;
+  p.B = batch; p.M = n_mats; p.H = heads; p.len = len;
+  p.nchunk = adain_nchunk(len, len);
+  const hipError_t e = ir_launch_token_stats_weighted(p, dtype, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "token_stats_weighted launch: %s", hipGetErrorString(e));
+  return IR_OK;
+}
+
+int ir_adain_affine_from_stats(int32_t batch, int32_t heads, int32_t n_refs,
+                               const float* style_mean, const float* style_std, const float* content_mean, const float* content_std,
+                               float eps, float* a, float* b, void* stream) {
+  if (batch <= 0 || heads <= 0 || n_refs <= 0) return fail(IR_ERR_INVALID_ARG, "batch %d, heads %d and n_refs %d must be > 0", batch, heads, n_refs);
+  if (style_mean == nullptr || style_std == nullptr) return fail(IR_ERR_INVALID_ARG, "style_mean / style_std is NULL");
+  if (content_mean == nullptr || content_std == nullptr) return fail(IR_ERR_INVALID_ARG, "content_mean / content_std is NULL");
+  if (a == nullptr || b == nullptr) return fail(IR_ERR_INVALID_ARG, "a / b is NULL");
+  if (!aligned4(style_mean) || !aligned4(style_std) || !aligned4(content_mean) || !aligned4(content_std) || !aligned4(a) || !aligned4(b))
+    return fail(IR_ERR_UNSUPPORTED, "style_mean, style_std, content_mean, content_std, a and b must be 4-byte aligned");
+  if ((int64_t)batch * n_refs * heads > (0x7fffffffLL / 64) * 256) return fail(IR_ERR_UNSUPPORTED, "grid too large");
+  const hipError_t e = ir_launch_adain_affine_from_stats(style_mean, style_std, content_mean, content_std, eps, a, b, batch, n_refs, heads,
+                                                         (hipStream_t)stream);
+  if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "adain_affine_from_stats launch: %s", hipGetErrorString(e));
+  return IR_OK;
+}
+
 int ir_adain_apply(int32_t dtype, int32_t batch, int32_t heads, int32_t n_refs, int32_t len,
                    const void* x, int64_t x_sb, int64_t x_sn, int64_t x_sl, int64_t x_sh,
                    const float* a, const float* b,

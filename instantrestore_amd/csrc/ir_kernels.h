@@ -8,6 +8,7 @@
 
 #define IR_KV_TILE 64          // keys per K/V tile
 #define IR_ADAIN_ROWS 256      // token rows per AdaIN partial-statistics workgroup
+#define IR_ADAIN_W_STRIDE 136  // floats per chunk partial of the weighted statistics: mean[64] | M2[64] | W, W2, 6 of padding
 
 // Parameter block of the fused attention kernels (passed by value as the kernel argument).
 struct AttnKParams {
@@ -265,6 +266,23 @@ hipError_t ir_launch_attn_key_match(const AttnKParams& p, int dtype, int reduce,
 hipError_t ir_launch_adain_stats(const AdainKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_token_stats(const AdainKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_adain_stats_cached(const AdainKParams& p, int dtype, hipStream_t s);
+// adain_weighted.hip: token statistics over weighted / counted tokens (ir_token_stats_weighted), the affine from finished statistics
+struct TokenStatsWKParams {
+  const void* x;             // (B, M, len, H, 64), strides in elements
+  int64_t x_sb, x_sn, x_sl, x_sh;
+  const float* weights;      // w[b, m, t] = weights[b * w_sb + m * w_sn + t], or nullptr (= 1)
+  int64_t w_sb, w_sn;
+  const int32_t* lens;       // c[b, m] = clamp(lens[b * ln_sb + m], 0, len), or nullptr (= len)
+  int64_t ln_sb;
+  float* ws;                 // chunk partials: [B*M][H][nchunk][IR_ADAIN_W_STRIDE]
+  float* mean;               // fp32 (B, M, H, 64)
+  float* std;
+  float* wsum;               // fp32 (B, M), or nullptr
+  int B, M, H, len, nchunk;
+};
+hipError_t ir_launch_token_stats_weighted(const TokenStatsWKParams& p, int dtype, hipStream_t s);
+hipError_t ir_launch_adain_affine_from_stats(const float* smean, const float* sstd, const float* cmean, const float* cstd, float eps,
+                                             float* a, float* b, int B, int N, int H, hipStream_t s);
 // round 4: the affine / the plain token statistics from the partials the projection GEMMs leave behind (ir_colstats.h)
 struct AdainPartialsKParams {
   const float* style_ws;     // partials of V_self: [(b * Ls / style_rows + c)][H][128]

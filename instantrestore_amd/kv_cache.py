@@ -104,6 +104,27 @@ class ReferenceKVCache:
             rows.append(c)
         self._lens[identity] = rows
 
+    def set_ref_stats(self, identity: Hashable, stats) -> None:
+        """replace the AdaIN content statistics of a cached identity: a per-layer list of ``(mean, std)`` fp32 ``(1, N, H, 64)``
+        pairs (or ``None`` for a layer without).  For statistics taken with other weights than the capture's - after
+        ``ops.compact_refs`` the kept-token statistics are ``ops.token_stats_weighted(packed_v, heads=H, lens=lens)`` - which
+        :meth:`assemble` / :meth:`assemble_tables` / :meth:`refill_tables` then carry as they carry any others.  The pairs are
+        cloned; an entry cached without statistics gains them."""
+        entry = self._store[identity]
+        if len(stats) != len(entry[0]):
+            raise ValueError(f"set_ref_stats(): {len(entry[0])} layers are cached, got statistics for {len(stats)}")
+        new = []
+        for l, st in enumerate(stats):
+            if st is None:
+                new.append(None)
+                continue
+            n, heads = int(entry[1][l].shape[1]), int(entry[1][l].shape[3]) // 64
+            if not (isinstance(st, (tuple, list)) and len(st) == 2 and
+                    all(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == (1, n, heads, 64) for t in st)):
+                raise ValueError(f"set_ref_stats(): layer {l} needs a (mean, std) pair of fp32 (1, {n}, {heads}, 64) tensors")
+            new.append((st[0].detach().clone(), st[1].detach().clone()))
+        self._store[identity] = (entry[0], entry[1], new)
+
     def _count_rows(self, identities, entries, counts, n_refs: int):
         """host side of the per-layer ``(B, N)`` counts: an identity's own counts, the capacity for one without, 0 for a slot it does
         not have"""

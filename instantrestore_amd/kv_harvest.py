@@ -120,13 +120,18 @@ def finished_stats(stats):
     return [st.finished() if hasattr(st, "finished") else st for st in stats]
 
 
-def enable_ref_stats(original_unet, enabled: bool = True) -> None:
+def enable_ref_stats(original_unet, enabled: bool = True, weights=None) -> None:
     """make every K/V-capturing processor also stash the AdaIN content statistics of its V (``AttnProcessor.v_mean`` /
     ``v_std``): they are computed once per reference, on the stream the reference UNet runs on, and
-    :func:`harvest_reference_kv` ``(with_stats=True)`` hands them to the main UNet"""
+    :func:`harvest_reference_kv` ``(with_stats=True)`` hands them to the main UNet.
+
+    ``weights`` (``AttnProcessor.capture_stats_weights``; ``None``: every token, weight 1): a weight picture ``(B, N, Hpx, Wpx)``
+    or per-token weights ``(B, N, L)`` of the references, float or bool - the statistics are then those of the weighted tokens
+    (``ops.token_stats_weighted``: one pass over V instead of the capture GEMM's partials), sampled per layer at its token centres"""
     for p in original_unet.attn_processors.values():
         if type(p) in [_ap.AttnProcessor]:
             p.capture_stats = bool(enabled)
+            p.capture_stats_weights = weights if enabled else None
 
 
 def enable_stream_overlap(original_unet, enabled: bool = True) -> None:
@@ -140,7 +145,7 @@ def enable_stream_overlap(original_unet, enabled: bool = True) -> None:
 
 def get_conditioning_keys_values(original_unet, model_input: torch.Tensor, timestep, encoder_hidden_states,
                                  n_refs: int, valid_indices: Sequence[int], early_exit: bool = False,
-                                 with_stats: bool = False, with_valid: bool = False):
+                                 with_stats: bool = False, with_valid: bool = False, stats_weights=None):
     """Run the frozen reference UNet on the (already encoded and noised) reference latents
     ``(B*N, 4, S, S)`` and harvest.  VAE encode/decode, the scheduler and the caption encoder
     around it (pix2pix_turbo.py:244-257, 277-278) are stock PyTorch and out of scope.
@@ -148,15 +153,24 @@ def get_conditioning_keys_values(original_unet, model_input: torch.Tensor, times
     ``early_exit`` (off by default): the reference UNet's own output is
     thrown away by the inference caller (``inference/test.py:100`` keeps only the K/V lists), so its
     forward can stop at the last K/V-capturing layer - after ``to_k`` / ``to_v`` of that layer, before its
-    attention, its out projection and everything downstream.  The harvested lists are identical."""
+    attention, its out projection and everything downstream.  The harvested lists are identical.
+
+    ``stats_weights`` (with ``with_stats``; ``None``: whatever :func:`enable_ref_stats` set): the references' AdaIN weights for
+    THIS call - a weight picture ``(B, N, Hpx, Wpx)`` or per-token weights ``(B, N, L)`` - so the harvested statistics are
+    those of the weighted tokens; restored afterwards, like ``capture_stats``."""
     procs = [p for p in original_unet.attn_processors.values() if type(p) in [_ap.AttnProcessor]]
     if not procs:
         raise RuntimeError("no AttnProcessor on this UNet: call register_attention_processor_kv_unet first")
+    if stats_weights is not None and not with_stats:
+        raise ValueError("stats_weights needs with_stats=True")
     # the capture layers compute the content statistics for THIS call iff it asks for them; whatever the caller had set
     # with enable_ref_stats comes back afterwards (a with_stats=True call must not leave every later capture paying for them)
     saved_stats = [p.capture_stats for p in procs]
+    saved_weights = [getattr(p, "capture_stats_weights", None) for p in procs]
     for p in procs:
         p.capture_stats = bool(with_stats) or p.capture_stats
+        if stats_weights is not None:
+            p.capture_stats_weights = stats_weights
     try:
         if not early_exit:
             original_unet(model_input, timestep, encoder_hidden_states=encoder_hidden_states)
@@ -175,8 +189,9 @@ def get_conditioning_keys_values(original_unet, model_input: torch.Tensor, times
                 p.stop_after_capture = None
         return harvest_reference_kv(original_unet, n_refs, valid_indices, with_stats=with_stats, with_valid=with_valid)
     finally:
-        for p, flag in zip(procs, saved_stats):
+        for p, flag, w in zip(procs, saved_stats, saved_weights):
             p.capture_stats = flag
+            p.capture_stats_weights = w
 
 
 # ------------------------------------------------------------------------------------------------------------------------

@@ -1193,6 +1193,81 @@ def token_stats(x: torch.Tensor, *, heads: int):
 
 
 @_on_tensor_device
+def token_stats_weighted(x: torch.Tensor, *, heads: int, weights: Optional[torch.Tensor] = None,
+                         lens: Optional[torch.Tensor] = None, return_wsum: bool = False):
+    """:func:`token_stats` over weighted or counted tokens (``ir_token_stats_weighted``): the mask-aware AdaIN statistics.
+
+    ``x`` is ``(B, M, L, H*64)`` as for :func:`token_stats`.  ``weights`` is ``(B, M, L)`` fp32 >= 0 (or bool, converted once
+    here; a batch dimension of size 1 is shared by the batch), ``lens`` int32 ``(B, M)``: token ``t`` of matrix ``(b, m)`` counts
+    with ``w = weights[b, m, t]`` if ``t < lens[b, m]`` and not at all otherwise.  Returns the weighted mean and the unbiased std
+    under reliability weights, two fp32 ``(B, M, H, 64)`` tensors (std without eps) - for a 0/1 mask the ``mean(dim=1)`` /
+    ``std(dim=1)`` of the kept tokens alone - and with ``return_wsum`` the effective token count ``W`` as fp32 ``(B, M)``.
+    A token of weight 0 or behind its count is never used, whatever its bytes; no token gives ``(0, 0)``, one token
+    ``(x, 0)``.  With neither ``weights`` nor ``lens`` (or all-ones / ``lens == L``) the bytes of :func:`token_stats`."""
+    _need_gpu(x, weights, lens)
+    _forward_only(x, weights)
+    x = _ref(x, heads, "x")
+    B, M, Lx, _ = x.shape
+    w_ptr, w_sb, w_sn = None, 0, 0
+    if weights is not None:
+        if weights.dim() != 3 or tuple(weights.shape[1:]) != (M, Lx) or weights.shape[0] not in (1, B):
+            raise ValueError(f"weights: expected ({B}, {M}, {Lx}) (or a batch of 1), got {tuple(weights.shape)}")
+        if weights.dtype == torch.bool:
+            weights = weights.to(torch.float32)
+        if weights.dtype != torch.float32:
+            raise TypeError(f"weights must be float32 or bool, got {weights.dtype}")
+        if weights.stride(2) != 1 or weights.stride(1) < Lx or weights.stride(0) < 0:
+            weights = weights.contiguous()
+        w_ptr, w_sn = weights.data_ptr(), weights.stride(1)
+        w_sb = 0 if weights.shape[0] == 1 else weights.stride(0)
+    l_ptr, ln_sb = None, 0
+    if lens is not None:
+        if lens.dtype != torch.int32:
+            raise TypeError(f"lens must be int32, got {lens.dtype}")
+        if tuple(lens.shape) != (B, M):
+            raise ValueError(f"lens: expected ({B}, {M}), got {tuple(lens.shape)}")
+        if lens.stride(1) != 1 or lens.stride(0) < M:
+            lens = lens.contiguous()
+        l_ptr, ln_sb = lens.data_ptr(), lens.stride(0)
+    L = _lib.lib()
+    nbytes = L.ir_token_stats_weighted_workspace_bytes(B, heads, M, Lx)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    mean = torch.empty((B, M, heads, HEAD_DIM), dtype=torch.float32, device=x.device)
+    std = torch.empty_like(mean)
+    wsum = torch.empty((B, M), dtype=torch.float32, device=x.device) if return_wsum else None
+    rc = L.ir_token_stats_weighted(_dtype_code(x), B, heads, M, Lx,
+                                   x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), HEAD_DIM,
+                                   w_ptr, w_sb, w_sn, l_ptr, ln_sb, mean.data_ptr(), std.data_ptr(),
+                                   wsum.data_ptr() if return_wsum else None, ws.data_ptr(), nbytes, _stream())
+    _lib.check(rc, "ir_token_stats_weighted")
+    return (mean, std, wsum) if return_wsum else (mean, std)
+
+
+@_on_tensor_device
+def adain_affine(style, content, *, eps: float = ADAIN_EPS):
+    """The AdaIN affine from FINISHED statistics (``ir_adain_affine_from_stats``): ``style = (mean, std)`` of the degraded
+    image's V - fp32 ``(B, H, 64)`` (or the ``(B, 1, H, 64)`` that :func:`token_stats` returns for one matrix) - and
+    ``content = (mean, std)`` of the reference V's, fp32 ``(B, N, H, 64)``, both std without eps.  Returns ``(a, b)`` in the shape
+    :func:`adain_stats` returns; ``token_stats(v_self)`` followed by this gives the bits of :func:`adain_stats_cached`."""
+    (s_mean, s_std), (c_mean, c_std) = style, content
+    _need_gpu(s_mean, s_std, c_mean, c_std)
+    if c_mean.dim() != 4 or c_mean.shape[-1] != HEAD_DIM or c_mean.shape != c_std.shape:
+        raise ValueError(f"content statistics must be two (B, N, H, 64) tensors, got {tuple(c_mean.shape)} / {tuple(c_std.shape)}")
+    B, N, H, _ = c_mean.shape
+    if s_mean.shape != s_std.shape or tuple(s_mean.shape) not in ((B, H, HEAD_DIM), (B, 1, H, HEAD_DIM)):
+        raise ValueError(f"style statistics must be two ({B}, {H}, 64) tensors, got {tuple(s_mean.shape)} / {tuple(s_std.shape)}")
+    for t in (s_mean, s_std, c_mean, c_std):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("statistics must be contiguous fp32")
+    a = torch.empty((B, N, H, HEAD_DIM), dtype=torch.float32, device=c_mean.device)
+    b = torch.empty_like(a)
+    rc = _lib.lib().ir_adain_affine_from_stats(B, H, N, s_mean.data_ptr(), s_std.data_ptr(), c_mean.data_ptr(), c_std.data_ptr(),
+                                               float(eps), a.data_ptr(), b.data_ptr(), _stream())
+    _lib.check(rc, "ir_adain_affine_from_stats")
+    return a, b
+
+
+@_on_tensor_device
 def adain_apply(x: torch.Tensor, a: torch.Tensor, b: torch.Tensor, *, heads: int) -> torch.Tensor:
     """``y = x*a + b`` over (B, N, L, H*64) (``ir_adain_apply``; op-level parity, ``adain()``)."""
     _need_gpu(x, a, b)
