@@ -91,6 +91,11 @@ def main(argv=None):
                          "that area of every reference and of the image alone; prints the largest change of the affine (a, b) and of the "
                          "output against the unmasked run.  With --compact-refs the packed references carry kept-token statistics "
                          "(ops.token_stats_weighted(packed_v, lens=lens)) instead of those of the full references")
+    ap.add_argument("--adain-regions", type=int, default=None, metavar="R",
+                    help="per-region AdaIN (adain_regions / adain_n_regions): a synthetic parsing map of R classes (1 ... 32; horizontal bands, "
+                         "shifted by one band on every further reference); every shared layer renormalises a reference token with the "
+                         "statistics of ITS class on both sides.  Prints how far the affine table's regional slots lie from the whole-face "
+                         "affine and the largest change of the output against plain AdaIN")
     ap.add_argument("--regions", action="store_true",
                     help="one more cached frame under a per-query restriction by region labels (region_labels / region_allow): synthetic label "
                          "pictures - a 4 x 4 grid of classes, shifted by n cells on reference n - and the rule \"own class only, self "
@@ -285,6 +290,39 @@ def main(argv=None):
                     assert bool(torch.isfinite(zk).all())
             finally:
                 ops.shared_attention = real
+        # "Renormalise eye tokens with eye statistics, skin with skin": one affine per (reference, class) instead of one per reference.
+        # A parsing map per side goes in once (the one region_labels takes); every shared layer samples it at its own token centres,
+        # takes the statistics of every class in one pass over V (ops.token_stats_regions), builds the (B, N, R + 1, H, 64) table
+        # (ops.adain_affine_regions: a class too small on either side falls back to the whole-face affine) and forms the renormalised
+        # V once (ops.adain_apply_regions); the attention then runs without an affine.
+        if args.adain_regions is not None:
+            R, px = int(args.adain_regions), 64
+            assert 1 <= R <= 32, "--adain-regions needs 1 ... 32 classes"
+            band = (torch.arange(px, device=dev) * R // px)[:, None].expand(px, px)            # (px, px): class = horizontal band
+            q_labels = band.expand(B, px, px).contiguous()
+            ref_labels = torch.stack([torch.roll(band, shifts=n * max(1, px // R), dims=0) for n in range(N)]).expand(B, N, px, px).contiguous()
+            tables, real = [], ops.adain_affine_regions
+
+            def recording(*a_, **kw_):          # the table every shared layer builds, in layer order
+                tables.append(real(*a_, **kw_))
+                return tables[-1]
+            ops.adain_affine_regions = recording
+            try:
+                kw = {"ref_keys": ck, "ref_values": cv, "ref_stats": cs}
+                z0 = unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1), cross_attention_kwargs=kw).sample
+                zr = unet(vae.encode(x), None, encoder_hidden_states=caption.expand(B, -1, -1),
+                          cross_attention_kwargs={"ref_keys": ck, "ref_values": cv, "adain_regions": (q_labels, ref_labels),
+                                                  "adain_n_regions": R}).sample
+            finally:
+                ops.adain_affine_regions = real
+            da = max(float((a_[:, :, :R] - a_[:, :, R:]).abs().max()) for a_, _ in tables)
+            db = max(float((b_[:, :, :R] - b_[:, :, R:]).abs().max()) for _, b_ in tables)
+            regional = sum(int(((a_[:, :, :R] != a_[:, :, R:]).flatten(3).any(-1)).sum()) for a_, _ in tables)
+            print(f"--adain-regions {R}: {len(tables)} shared layers, {regional} of {sum(a_[:, :, :R, 0, 0].numel() for a_, _ in tables)} "
+                  f"(reference, class) slots carry regional statistics; largest distance of a regional slot from the whole-face affine: a {da:.3f}, "
+                  f"b {db:.3f}; largest change of the output {float((zr.float() - z0.float()).abs().max()):.3f} "
+                  f"(max|output| {float(z0.float().abs().max()):.3f})")
+            assert bool(torch.isfinite(zr).all()) and len(tables) == 9
         # "Eye tokens draw from eye tokens of the references, mouth from mouth, the picture itself is free": a per-QUERY restriction.
         # Label pictures (a face parsing map; here a coarse grid of classes) and a class-by-class rule go in once; every shared layer
         # samples the labels at its own token centres and hands the kernel one 32-bit word per query row and one small integer per

@@ -731,6 +731,64 @@ int ir_adain_apply(int32_t dtype, int32_t batch, int32_t heads, int32_t n_refs, 
                    void* y, int64_t y_sb, int64_t y_sn, int64_t y_sl, int64_t y_sh, void* stream);
 
 /*
+ * ir_token_stats_labelled - ir_token_stats per REGION label, every region in one pass over x (per-region AdaIN statistics).
+ *
+ * Token t of matrix (b, m) carries the label  l = labels[b * lb_sb + m * lb_sn + t].  Per (b, region r, m, head, channel) the
+ * outputs are the mean and the UNBIASED std over the tokens with l == r: mean(dim=1) / std(dim=1) (attn_processors.py:9-10)
+ * over x[:, labels == r] - what ir_token_stats_weighted gives with the weights (l == r), for every r < n_regions, while x is
+ * read once.
+ *   x (B, M, len, H, 64) strides x_* (the 16-byte rule of ir_token_stats)
+ *   labels: int32; lb_sb = 0 shares one set across the batch; lb_sn >= len
+ *   n_regions: 1 ... IR_ADAIN_REGIONS_MAX (the range of IR_REGION_MAX: one parsing map serves the region masks and these)
+ *   mean, std: fp32 (B, n_regions, M, H, 64) contiguous, std WITHOUT eps.  Region-major: (B * n_regions) is then the batch of
+ *              ir_adain_affine_from_stats as it stands
+ *   count:   optional fp32 (B, n_regions, M): the tokens of the region, an exact integer; NULL = off
+ *   workspace >= ir_token_stats_labelled_workspace_bytes(batch, heads, n_mats, len, n_regions)
+ * A token whose label lies outside [0, n_regions) belongs to no region: it is selected away whatever its bytes, NaN and Inf
+ * included.  Nothing outside the `len` rows of x and the `len` ints of a label row is read.
+ * Never NaN: a region with no token gives mean 0, std 0, count 0; a region with one token gives (x, 0), count 1.
+ * Bit for bit: for every r the outputs are the bytes of ir_token_stats_weighted on the same x with the fp32 weights (l == r)
+ * (same row slots, same shifted sums, same Chan merge over the row slots and over ascending 256-row chunks; count == its wsum).
+ * Order: the order of evaluation is a function of len and n_regions only - a (b, m) result does not depend on the batch, its
+ * position, its neighbours, the grid or the stream.  No atomics, one writer per output, two launches, asynchronous and
+ * capturable; labels are read when the kernel RUNS: a replayed hipGraph follows in-place updates of them.
+ * Checked in this order, before any launch, no device pointer dereferenced: IR_ERR_UNSUPPORTED: dtype; IR_ERR_INVALID_ARG:
+ * a size <= 0, n_regions outside [1, IR_ADAIN_REGIONS_MAX], NULL x, NULL labels, NULL mean, NULL std, NULL workspace;
+ * IR_ERR_UNSUPPORTED: x not 16-byte aligned or an x stride that is negative or no multiple of 8; IR_ERR_INVALID_ARG:
+ * lb_sn < len, lb_sb < 0; IR_ERR_UNSUPPORTED: labels, mean, std, count not 4-byte aligned, batch * n_mats or heads > 65535 (or
+ * batch * n_mats * n_regions * heads >= 2^31); IR_ERR_WORKSPACE: a workspace that is too small.
+ */
+#define IR_ADAIN_REGIONS_MAX 32
+size_t ir_token_stats_labelled_workspace_bytes(int32_t batch, int32_t heads, int32_t n_mats, int32_t len, int32_t n_regions);
+int ir_token_stats_labelled(int32_t dtype, int32_t batch, int32_t heads, int32_t n_mats, int32_t len, int32_t n_regions,
+                           const void* x, int64_t x_sb, int64_t x_sn, int64_t x_sl, int64_t x_sh,
+                           const int32_t* labels, int64_t lb_sb, int64_t lb_sn,
+                           float* mean, float* std, float* count, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * ir_adain_apply_labelled - ir_adain_apply with the affine chosen PER TOKEN by its region label.
+ *
+ *   y[b,n,t,h,:] = fma(x[b,n,t,h,:], a[b,n,s,h,:], b[b,n,s,h,:]),   s = (unsigned)label[b,n,t] < n_regions ? label[b,n,t] : n_regions
+ * fp32 math, one rounding to dtype: the expression of ir_adain_apply, so a token of region r gets the bytes ir_adain_apply gives
+ * it with slot r's affine.
+ *   x, y (B, N, len, H, 64) with strides x_* / y_* (16-byte aligned, strides non-negative multiples of 8); y may be a view into
+ *        a wider buffer: only the 64-element head rows of y are written
+ *   a, b: fp32 (B, N, n_regions + 1, H, 64) contiguous; the LAST slot is the affine of the tokens without a region
+ *   labels: int32, label[b,n,t] = labels[b * lb_sb + n * lb_sn + t]  (lb_sb = 0: shared by the batch; lb_sn >= len), read when
+ *        the kernel RUNS, once per token and group of four heads (shared by the 8 sixteen-byte pieces of each of its head rows)
+ * y == x with identical strides (in place) is allowed: every 16-byte piece is read and then written by one thread.  Any other
+ * overlap of x and y is undefined.  One launch, asynchronous, capturable, batch-invariant.
+ * Checked in this order, before any launch: IR_ERR_UNSUPPORTED: dtype; IR_ERR_INVALID_ARG: a size <= 0, n_regions outside
+ * [1, IR_ADAIN_REGIONS_MAX], NULL x, NULL y, NULL a / b, NULL labels; IR_ERR_UNSUPPORTED: x / y not 16-byte aligned, a stride
+ * that is negative or no multiple of 8; IR_ERR_INVALID_ARG: lb_sn < len, lb_sb < 0; IR_ERR_UNSUPPORTED: labels, a, b not
+ * 4-byte aligned.
+ */
+int ir_adain_apply_labelled(int32_t dtype, int32_t batch, int32_t heads, int32_t n_refs, int32_t len, int32_t n_regions,
+                           const void* x, int64_t x_sb, int64_t x_sn, int64_t x_sl, int64_t x_sh,
+                           const int32_t* labels, int64_t lb_sb, int64_t lb_sn, const float* a, const float* b,
+                           void* y, int64_t y_sb, int64_t y_sn, int64_t y_sl, int64_t y_sh, void* stream);
+
+/*
  * ir_zero_invalid_refs - zero the K and V of references n >= valid[b] in place.
  *
  * Replaces the Python double loop of Pix2Pix_Turbo.get_conditioning_keys_values

@@ -19,6 +19,7 @@ IR_DTYPE_F16, IR_DTYPE_BF16 = 0, 1
 IR_FLAG_INCLUDE_SELF, IR_FLAG_Q_PRESCALED, IR_FLAG_OUT_F32 = 1, 2, 4
 IR_FLAG_BATCH_INVARIANT = 8   # ABI v10
 IR_KEY_BIAS_MASKED = -1.0e4   # a key whose bias is -inf or <= this is masked (probability exactly 0)
+IR_ADAIN_REGIONS_MAX = 32   # regions of ir_token_stats_labelled / ir_adain_apply_labelled: the range of IR_REGION_MAX
 IR_REGION_MAX = 32   # regions of ir_shared_attn_region_args: key_region in [0, 31], one bit of q_allow each
 IR_ROWS_NONE, IR_ROWS_HEAD_MEAN, IR_ROWS_MAP = 0, 1, 2   # the `reduce` argument of ir_attn_rows
 IR_MATCH_PER_HEAD, IR_MATCH_HEAD_MEAN = 0, 1   # the `reduce` argument of ir_attn_match
@@ -123,6 +124,11 @@ SYMBOLS = {
     "ir_token_stats_weighted": (C.c_int, [i32, i32, i32, i32, i32, vp, i64, i64, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp,
                                           C.c_size_t, vp]),
     "ir_adain_affine_from_stats": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp]),
+    "ir_token_stats_labelled_workspace_bytes": (C.c_size_t, [i32, i32, i32, i32, i32]),
+    "ir_token_stats_labelled": (C.c_int, [i32, i32, i32, i32, i32, i32, vp, i64, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp,
+                                         C.c_size_t, vp]),
+    "ir_adain_apply_labelled": (C.c_int, [i32, i32, i32, i32, i32, i32, vp, i64, i64, i64, i64, vp, i64, i64, vp, vp,
+                                         vp, i64, i64, i64, i64, vp]),
     "ir_adain_apply": (C.c_int, [i32, i32, i32, i32, i32, vp, i64, i64, i64, i64, vp, vp,
                                  vp, i64, i64, i64, i64, vp]),
     "ir_tensor2im_u8": (C.c_int, [i32, i32, i32, i32, i32, vp, i64, i64, i64, i64, vp, vp]),

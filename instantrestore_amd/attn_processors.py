@@ -240,6 +240,53 @@ def _adain_weight_pair(adain_weights, batch: int, len_self: int, n_refs: int, le
     return pair
 
 
+# (self labels, reference labels) of ``adain_regions``, sampled once per (kwargs identity and version, layer geometry) the way
+# _REGION_PAIRS caches region pairs: int32 (B, len_self) / (B, N, len_ref), the label rows of ops.token_stats_regions
+_ADAIN_REGION_LABELS: dict = {}
+_ADAIN_REGION_LABELS_MAX = 8
+
+
+def _adain_labels_on_grid(labels, length: int, refs: bool, device):
+    """integer label pictures ``(B, [N,] Hpx, Wpx)`` or per-token labels ``(B, [N,] L)`` (the row-major picture of their own square
+    grid) sampled at the token centres of the square grid of ``length`` tokens (``attn_maps.token_labels``) -> int32
+    ``(B, [N,] length)`` on ``device``"""
+    from . import attn_maps as _maps
+    what = "adain_regions: the reference labels" if refs else "adain_regions: the query labels"
+    t = torch.as_tensor(labels)
+    pictures = 4 if refs else 3
+    if t.dim() == pictures - 1:      # per-token labels
+        if t.shape[-1] == length:
+            return t.to(device=device, dtype=torch.int32).contiguous()
+        s = _maps._square_side(t.shape[-1], f"{what}' length")
+        t = t.reshape(*t.shape[:-1], s, s)
+    if t.dim() != pictures:
+        raise ValueError(f"{what} must be label pictures {'(B, N, Hpx, Wpx)' if refs else '(B, Hpx, Wpx)'} or per-token labels, "
+                         f"got {tuple(torch.as_tensor(labels).shape)}")
+    picked = _maps.token_labels(t, _maps._square_side(length, what))         # (B, [N *] length)
+    return picked.reshape(*t.shape[:-2], length).to(device=device, dtype=torch.int32).contiguous()
+
+
+def _adain_region_labels(adain_regions, batch: int, len_self: int, n_refs: int, len_ref: int, device):
+    if not isinstance(adain_regions, (tuple, list)) or len(adain_regions) != 2 or adain_regions[0] is None or adain_regions[1] is None:
+        raise ValueError("adain_regions must be the pair (query_labels, ref_labels)")
+    q_lab, r_lab = adain_regions
+    ver = lambda t: (id(t), getattr(t, "_version", None))
+    key = (ver(q_lab), ver(r_lab), batch, len_self, n_refs, len_ref, str(device))
+    hit = _ADAIN_REGION_LABELS.get(key)
+    if hit is not None and hit[0] is q_lab and hit[1] is r_lab:
+        return hit[2]
+    ql = _adain_labels_on_grid(q_lab, len_self, False, device)
+    rl = _adain_labels_on_grid(r_lab, len_ref, True, device)
+    if tuple(ql.shape) != (batch, len_self) or tuple(rl.shape) != (batch, n_refs, len_ref):
+        raise ValueError(f"adain_regions: labels of {tuple(ql.shape)} query and {tuple(rl.shape)} reference tokens for a batch of {batch} "
+                         f"with {len_self} tokens and {n_refs} references of {len_ref} tokens")
+    pair = (ql, rl)
+    while len(_ADAIN_REGION_LABELS) >= _ADAIN_REGION_LABELS_MAX:
+        _ADAIN_REGION_LABELS.pop(next(iter(_ADAIN_REGION_LABELS)))
+    _ADAIN_REGION_LABELS[key] = (q_lab, r_lab, pair)
+    return pair
+
+
 def _kv_source(attn, st: _Prepared) -> torch.Tensor:
     if st.encoder is None:
         return st.hidden
@@ -532,8 +579,10 @@ class AttnProcessor(nn.Module):
                 self.ready.record(self.stream)
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
-                ref_weights=None, ref_token_keep=None, ref_lens=None, region_labels=None, region_allow=None, adain_weights=None):
-        # ref_weights / ref_token_keep / ref_lens / region_labels / region_allow / adain_weights: accepted and ignored (no references here), like ref_valid elsewhere
+                ref_weights=None, ref_token_keep=None, ref_lens=None, region_labels=None, region_allow=None, adain_weights=None,
+                adain_regions=None, adain_n_regions=None, adain_region_min_tokens=None):
+        # ref_weights / ref_token_keep / ref_lens / region_labels / region_allow / adain_weights / adain_regions / adain_n_regions /
+        # adain_region_min_tokens: accepted and ignored (no references here), like ref_valid elsewhere
         st = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
         self.is_self_attn = encoder_hidden_states is None
         group = self.stop_after_capture
@@ -582,8 +631,9 @@ class FaceIDAttnProcessor(nn.Module):
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                 ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None, ref_weights=None, ref_token_keep=None,
-                ref_lens=None, region_labels=None, region_allow=None, adain_weights=None):
-        # ref_* / region_* / adain_weights accepted and ignored, like the reference: the host forwards ONE cross_attention_kwargs dict to every processor
+                ref_lens=None, region_labels=None, region_allow=None, adain_weights=None,
+                adain_regions=None, adain_n_regions=None, adain_region_min_tokens=None):
+        # ref_* / region_* / adain_weights / adain_regions (with its two settings) accepted and ignored, like the reference: the host forwards ONE cross_attention_kwargs dict to every processor
         # (unet.py / diffusers), so whatever the harvest hands SharedAttnProcessor (ref_valid included) arrives here too
         st = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
         self.is_self_attn = encoder_hidden_states is None
@@ -697,7 +747,8 @@ class SharedAttnProcessor(nn.Module):
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                 ref_keys=None, ref_values=None, ref_events=None, ref_stats=None, ref_valid=None, ref_weights=None, ref_token_keep=None,
-                ref_lens=None, region_labels=None, region_allow=None, adain_weights=None):
+                ref_lens=None, region_labels=None, region_allow=None, adain_weights=None,
+                adain_regions=None, adain_n_regions=None, adain_region_min_tokens=None):
         """``attention_mask``: additive, ``(B, Lkv)``, ``(B, 1, Lkv)`` or ``(B * H, 1, Lkv)`` over this layer's key axis (with references: the
         extended one) - the fused kernel's key bias.  ``ref_weights`` ``(B, N)`` >= 0 and ``ref_token_keep`` (bool ``(B, N, len_ref)`` or
         ``(B, N, S, S)``), shared layers only (ignored elsewhere, as ``ref_valid`` is): ``ops.key_bias`` turns them into the bias -
@@ -738,7 +789,24 @@ class SharedAttnProcessor(nn.Module):
         ``ops.token_stats_weighted(packed_v, lens=lens)`` after a compaction; the pair's reference weights are then not consulted -
         otherwise one weighted pass over the dense reference V; a ``RefKVTable`` without ``ref_stats`` raises as without the
         kwarg, and so does ``ref_lens`` without ``ref_stats``.  The affine comes from ``ops.adain_affine`` and enters the
-        attention as any other: masks, ``ref_weights``, ``ref_token_keep``, regions and the batch-invariant mode work with it."""
+        attention as any other: masks, ``ref_weights``, ``ref_token_keep``, regions and the batch-invariant mode work with it.
+        ``adain_regions = (query_labels, ref_labels)`` with ``adain_n_regions`` (required: inferring it would need a sync) and the
+        optional ``adain_region_min_tokens`` (default 8), shared layers with ``use_adain`` only (accepted and ignored elsewhere):
+        per-REGION AdaIN - eye tokens of a reference are renormalised with eye statistics, skin with skin.  The labels are
+        integer label pictures (``(B, Hpx, Wpx)`` / ``(B, N, Hpx, Wpx)``: a face parsing map, the one ``region_labels`` takes) or
+        per-token labels of a square grid (``(B, L)`` / ``(B, N, L)``), sampled by every layer at its own token centres
+        (``attn_maps.token_labels``), once per geometry, cached by tensor identity and version.  A label outside
+        ``[0, adain_n_regions)`` is "no region": such a token takes the whole-face affine.  The fold cannot carry an affine per key,
+        so this is the apply-to-V branch: the GEMM's statistics tail is off; style and content statistics are
+        ``ops.token_stats`` + ``ops.token_stats_regions`` over this layer's V and over the dense reference V; the table comes from
+        ``ops.adain_affine_regions`` (a region with fewer than ``adain_region_min_tokens`` tokens on either side falls back to the
+        whole-face affine); ``ops.adain_apply_regions`` forms the renormalised V once and the attention runs on it WITHOUT an affine
+        and without ``ref_valid`` (a zero-filled reference's V is the style mean now: its tiles are walked).  Masks, ``ref_weights``,
+        ``ref_token_keep``, ``region_labels``, ``save_attention_mass``, the read-outs and the batch-invariant mode see an ordinary
+        call.  ``ref_stats`` is not consulted.  Raises, before anything is launched: without ``adain_n_regions`` (ValueError); with
+        ``adain_weights`` (regional statistics over weighted tokens are a follow-up), with ``ref_lens`` (the labels index the
+        uncompacted token axis; a follow-up) and with ``RefKVTable`` references (cached per-identity regional statistics are the
+        follow-up) - NotImplementedError."""
         st = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
         shared = self.self_attn_idx is not None and ref_keys is not None and ref_values is not None
         regions = shared and region_labels is not None
@@ -762,7 +830,20 @@ class SharedAttnProcessor(nn.Module):
         have_cstats = bool(shared and ref_stats is not None and ref_stats[self.self_attn_idx] is not None)
         bi = bool(getattr(self, "batch_invariant", False))
         weighted = bool(shared and self.use_adain and adain_weights is not None)    # mask-aware AdaIN: a branch of its own below
-        query, key, value, presc, vstats = _project_qkv(attn, st, want_stats=bool(self.use_adain and have_cstats and not weighted), bi=bi)
+        regional = bool(shared and self.use_adain and adain_regions is not None)    # per-region AdaIN: applied to V, a branch of its own below
+        if regional:    # refused before anything is launched
+            if adain_n_regions is None:
+                raise ValueError("adain_regions needs adain_n_regions (1 ... 32): inferring it from the labels would need a device sync")
+            if adain_weights is not None:
+                raise NotImplementedError("adain_regions together with adain_weights: regional statistics over weighted tokens are a follow-up")
+            if ref_lens is not None and ref_lens[self.self_attn_idx] is not None:
+                raise NotImplementedError("adain_regions together with ref_lens: the labels index the uncompacted token axis; regions "
+                                          "over compacted references are a follow-up")
+            if isinstance(ref_values[self.self_attn_idx], _RefKVTable):
+                raise NotImplementedError("adain_regions with RefKVTable references: the regional statistics and the renormalised V need "
+                                          "dense references; cached per-identity regional statistics are the follow-up")
+        query, key, value, presc, vstats = _project_qkv(attn, st, want_stats=bool(self.use_adain and have_cstats and not weighted and not regional),
+                                                        bi=bi)
 
         ref_k = ref_v = None
         include_self = True
@@ -823,7 +904,22 @@ class SharedAttnProcessor(nn.Module):
                 # only V_self is read here - 1/(N+1) of the bytes, the same (a, b) bit for bit
                 # Round 4: the style statistics arrive as the partials this layer's own q/k/v GEMM left behind (``vstats``):
                 # with them and the content statistics nothing of V is read here at all - one small launch
-                if weighted:
+                if regional:
+                    # per-region AdaIN: one affine per (reference, region) cannot ride the fold (it applies a * sum(p v) + b * sum(p)
+                    # once per segment), so the renormalised V is formed here - the reference's own order of operations - and
+                    # the attention below runs without an affine
+                    R = int(adain_n_regions)
+                    q_lab, r_lab = _adain_region_labels(adain_regions, value.shape[0], value.shape[1], ref_v.shape[1], ref_v.shape[2], value.device)
+                    v1 = value.unsqueeze(1)
+                    style_g = _ops.token_stats(v1, heads=attn.heads)
+                    style_r = _ops.token_stats_regions(v1, q_lab.unsqueeze(1), heads=attn.heads, n_regions=R, return_count=True)
+                    content_g = _ops.token_stats(ref_v, heads=attn.heads)
+                    content_r = _ops.token_stats_regions(ref_v, r_lab, heads=attn.heads, n_regions=R, return_count=True)
+                    table = _ops.adain_affine_regions(style_r, content_r, style_g, content_g,
+                                                      min_tokens=FOLD_MIN_REF_TOKENS if adain_region_min_tokens is None else adain_region_min_tokens)
+                    ref_v = _ops.adain_apply_regions(ref_v, r_lab, table[0], table[1], heads=attn.heads)
+                    ref_valid = None       # a zero-filled reference's V is the style mean now, not zero: its tiles are walked
+                elif weighted:
                     # mask-aware AdaIN: the style statistics over this layer's weighted tokens; the content statistics as the
                     # caller finished them (``ref_stats``), else over the dense references' weighted tokens
                     self_w, ref_w = _adain_weight_pair(adain_weights, value.shape[0], value.shape[1], ref_v.shape[1], ref_v.shape[2], value.device)

@@ -6,7 +6,7 @@ HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="${IR_OUT:-${HERE}/../libinstantrestore_hip.so}"
 BUILD_DIR="${IR_BUILD_DIR:-build}"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
-SRCS=(linear_tiled.hip shared_attn_fwd.hip shared_attn_fwd_pipe.hip shared_attn_fwd_pipe_bias.hip shared_attn_fwd_pipe_ragged.hip shared_attn_fwd_pipe_region.hip shared_attn_fwd_w64.hip shared_attn_fwd_w128.hip shared_attn_fwd_w128_forms.hip attn_probs.hip attn_rows.hip attn_match.hip attn_transfer.hip attn_received.hip attn_topk.hip attn_key_match.hip adain.hip adain_weighted.hip compact_refs.hip image_io.hip linear_skinny.hip bench_hooks.hip c_abi.hip)
+SRCS=(linear_tiled.hip shared_attn_fwd.hip shared_attn_fwd_pipe.hip shared_attn_fwd_pipe_bias.hip shared_attn_fwd_pipe_ragged.hip shared_attn_fwd_pipe_region.hip shared_attn_fwd_w64.hip shared_attn_fwd_w128.hip shared_attn_fwd_w128_forms.hip attn_probs.hip attn_rows.hip attn_match.hip attn_transfer.hip attn_received.hip attn_topk.hip attn_key_match.hip adain.hip adain_weighted.hip adain_regions.hip compact_refs.hip image_io.hip linear_skinny.hip bench_hooks.hip c_abi.hip)
 cd "${HERE}"
 # the hand-placed instruction stream of the 128-row attention kernel is generated (committed; regenerated here so it cannot go stale)
 python3 "${HERE}/w128/gen.py"

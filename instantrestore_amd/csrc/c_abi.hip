@@ -735,6 +735,85 @@ int ir_adain_affine_from_stats(int32_t batch, int32_t heads, int32_t n_refs,
   return IR_OK;
 }
 
+size_t ir_token_stats_labelled_workspace_bytes(int32_t batch, int32_t heads, int32_t n_mats, int32_t len, int32_t n_regions) {
+  if (batch <= 0 || heads <= 0 || n_mats <= 0 || len <= 0 || n_regions <= 0 || n_regions > IR_ADAIN_REGIONS_MAX) return 0;
+  return (size_t)batch * (size_t)n_mats * (size_t)n_regions * (size_t)heads * (size_t)adain_nchunk(len, len) * IR_ADAIN_W_STRIDE * sizeof(float);
+}
+
+// Checked in this order (the header states it): dtype, sizes, n_regions, NULL x / labels / mean / std / workspace, the 16-byte
+// rule of x, the labels' strides, the 4-byte alignments, the grid, the workspace
+int ir_token_stats_labelled(int32_t dtype, int32_t batch, int32_t heads, int32_t n_mats, int32_t len, int32_t n_regions,
+                           const void* x, int64_t x_sb, int64_t x_sn, int64_t x_sl, int64_t x_sh,
+                           const int32_t* labels, int64_t lb_sb, int64_t lb_sn,
+                           float* mean, float* std, float* count, void* workspace, size_t workspace_bytes, void* stream) {
+  if (dtype != IR_DTYPE_F16 && dtype != IR_DTYPE_BF16) return fail(IR_ERR_UNSUPPORTED, "dtype %d: only fp16 (0) and bf16 (1) are implemented", dtype);
+  if (batch <= 0 || heads <= 0 || n_mats <= 0 || len <= 0)
+    return fail(IR_ERR_INVALID_ARG, "batch %d, heads %d, n_mats %d and len %d must be > 0", batch, heads, n_mats, len);
+  if (n_regions < 1 || n_regions > IR_ADAIN_REGIONS_MAX)
+    return fail(IR_ERR_INVALID_ARG, "n_regions %d must be in [1, %d]", n_regions, IR_ADAIN_REGIONS_MAX);
+  if (x == nullptr) return fail(IR_ERR_INVALID_ARG, "x is NULL");
+  if (labels == nullptr) return fail(IR_ERR_INVALID_ARG, "labels is NULL");
+  if (mean == nullptr) return fail(IR_ERR_INVALID_ARG, "mean is NULL");
+  if (std == nullptr) return fail(IR_ERR_INVALID_ARG, "std is NULL");
+  if (workspace == nullptr) return fail(IR_ERR_INVALID_ARG, "workspace is NULL");
+  if (!aligned16(x)) return fail(IR_ERR_UNSUPPORTED, "x must be 16-byte aligned");
+  const int64_t st[] = {x_sb, x_sn, x_sl, x_sh};
+  for (int64_t s : st) if (!stride_ok(s)) return fail(IR_ERR_UNSUPPORTED, "x stride %lld must be a non-negative multiple of 8", (long long)s);
+  if (lb_sn < len) return fail(IR_ERR_INVALID_ARG, "labels matrix stride lb_sn %lld must be >= len %d", (long long)lb_sn, len);
+  if (lb_sb < 0) return fail(IR_ERR_INVALID_ARG, "labels batch stride lb_sb %lld must be >= 0", (long long)lb_sb);
+  if (!aligned4(labels)) return fail(IR_ERR_UNSUPPORTED, "labels must be 4-byte aligned");
+  if (!aligned4(mean)) return fail(IR_ERR_UNSUPPORTED, "mean must be 4-byte aligned");
+  if (!aligned4(std)) return fail(IR_ERR_UNSUPPORTED, "std must be 4-byte aligned");
+  if (!aligned4(count)) return fail(IR_ERR_UNSUPPORTED, "count must be 4-byte aligned");
+  if ((int64_t)batch * n_mats > 65535 || heads > 65535 || (int64_t)batch * n_mats * n_regions * heads > 0x7fffffffLL)
+    return fail(IR_ERR_UNSUPPORTED, "grid too large: batch * n_mats and heads must be <= 65535, batch * n_mats * n_regions * heads < 2^31");
+  const size_t need = ir_token_stats_labelled_workspace_bytes(batch, heads, n_mats, len, n_regions);
+  if (workspace_bytes < need) return fail(IR_ERR_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, need);
+  TokenStatsRKParams p;
+  memset(&p, 0, sizeof(p));
+  p.x = x; p.x_sb = x_sb; p.x_sn = x_sn; p.x_sl = x_sl; p.x_sh = x_sh;
+  p.labels = labels; p.lb_sb = lb_sb; p.lb_sn = lb_sn;
+  p.ws = (float*)workspace; p.mean = mean; p.std = std; p.count = count;
+  p.B = batch; p.M = n_mats; p.H = heads; p.len = len; p.R = n_regions;
+  p.nchunk = adain_nchunk(len, len);
+  const hipError_t e = ir_launch_token_stats_regions(p, dtype, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "token_stats_regions launch: %s", hipGetErrorString(e));
+  return IR_OK;
+}
+
+// Checked in this order (the header states it): dtype, sizes, n_regions, NULL x / y / a / b / labels, the 16-byte rule of x and
+// y, the labels' strides, the 4-byte alignments
+int ir_adain_apply_labelled(int32_t dtype, int32_t batch, int32_t heads, int32_t n_refs, int32_t len, int32_t n_regions,
+                           const void* x, int64_t x_sb, int64_t x_sn, int64_t x_sl, int64_t x_sh,
+                           const int32_t* labels, int64_t lb_sb, int64_t lb_sn, const float* a, const float* b,
+                           void* y, int64_t y_sb, int64_t y_sn, int64_t y_sl, int64_t y_sh, void* stream) {
+  if (dtype != IR_DTYPE_F16 && dtype != IR_DTYPE_BF16) return fail(IR_ERR_UNSUPPORTED, "dtype %d: only fp16 (0) and bf16 (1) are implemented", dtype);
+  if (batch <= 0 || heads <= 0 || n_refs <= 0 || len <= 0)
+    return fail(IR_ERR_INVALID_ARG, "batch %d, heads %d, n_refs %d and len %d must be > 0", batch, heads, n_refs, len);
+  if (n_regions < 1 || n_regions > IR_ADAIN_REGIONS_MAX)
+    return fail(IR_ERR_INVALID_ARG, "n_regions %d must be in [1, %d]", n_regions, IR_ADAIN_REGIONS_MAX);
+  if (x == nullptr) return fail(IR_ERR_INVALID_ARG, "x is NULL");
+  if (y == nullptr) return fail(IR_ERR_INVALID_ARG, "y is NULL");
+  if (a == nullptr || b == nullptr) return fail(IR_ERR_INVALID_ARG, "a / b is NULL");
+  if (labels == nullptr) return fail(IR_ERR_INVALID_ARG, "labels is NULL");
+  if (!aligned16(x) || !aligned16(y)) return fail(IR_ERR_UNSUPPORTED, "x / y must be 16-byte aligned");
+  const int64_t st[] = {x_sb, x_sn, x_sl, x_sh, y_sb, y_sn, y_sl, y_sh};
+  for (int64_t s : st) if (!stride_ok(s)) return fail(IR_ERR_UNSUPPORTED, "stride %lld must be a non-negative multiple of 8", (long long)s);
+  if (lb_sn < len) return fail(IR_ERR_INVALID_ARG, "labels matrix stride lb_sn %lld must be >= len %d", (long long)lb_sn, len);
+  if (lb_sb < 0) return fail(IR_ERR_INVALID_ARG, "labels batch stride lb_sb %lld must be >= 0", (long long)lb_sb);
+  if (!aligned4(labels) || !aligned4(a) || !aligned4(b)) return fail(IR_ERR_UNSUPPORTED, "labels, a and b must be 4-byte aligned");
+  AdainApplyRKParams p;
+  memset(&p, 0, sizeof(p));
+  p.x = x; p.y = y; p.a = a; p.b = b;
+  p.labels = labels; p.lb_sb = lb_sb; p.lb_sn = lb_sn;
+  p.x_sb = x_sb; p.x_sn = x_sn; p.x_sl = x_sl; p.x_sh = x_sh;
+  p.y_sb = y_sb; p.y_sn = y_sn; p.y_sl = y_sl; p.y_sh = y_sh;
+  p.B = batch; p.H = heads; p.N = n_refs; p.L = len; p.R = n_regions;
+  const hipError_t e = ir_launch_adain_apply_regions(p, dtype, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(IR_ERR_LAUNCH, "adain_apply_regions launch: %s", hipGetErrorString(e));
+  return IR_OK;
+}
+
 int ir_adain_apply(int32_t dtype, int32_t batch, int32_t heads, int32_t n_refs, int32_t len,
                    const void* x, int64_t x_sb, int64_t x_sn, int64_t x_sl, int64_t x_sh,
                    const float* a, const float* b,

@@ -283,6 +283,31 @@ struct TokenStatsWKParams {
 hipError_t ir_launch_token_stats_weighted(const TokenStatsWKParams& p, int dtype, hipStream_t s);
 hipError_t ir_launch_adain_affine_from_stats(const float* smean, const float* sstd, const float* cmean, const float* cstd, float eps,
                                              float* a, float* b, int B, int N, int H, hipStream_t s);
+// adain_regions.hip: token statistics per region label in one pass (ir_token_stats_labelled), the apply with a per-token affine slot
+struct TokenStatsRKParams {
+  const void* x;             // (B, M, len, H, 64), strides in elements
+  int64_t x_sb, x_sn, x_sl, x_sh;
+  const int32_t* labels;     // label[b, m, t] = labels[b * lb_sb + m * lb_sn + t]; outside [0, R): no region
+  int64_t lb_sb, lb_sn;
+  float* ws;                 // chunk partials: [B*M][R][H][nchunk][IR_ADAIN_W_STRIDE]
+  float* mean;               // fp32 (B, R, M, H, 64)
+  float* std;
+  float* count;              // fp32 (B, R, M), or nullptr
+  int B, M, H, len, R, nchunk;
+};
+struct AdainApplyRKParams {
+  const void* x;
+  void* y;
+  const float* a;            // fp32 (B, N, R + 1, H, 64); slot R: tokens of no region
+  const float* b;
+  const int32_t* labels;     // label[b, n, t] = labels[b * lb_sb + n * lb_sn + t]
+  int64_t lb_sb, lb_sn;
+  int64_t x_sb, x_sn, x_sl, x_sh;
+  int64_t y_sb, y_sn, y_sl, y_sh;
+  int B, H, N, L, R;
+};
+hipError_t ir_launch_token_stats_regions(const TokenStatsRKParams& p, int dtype, hipStream_t s);
+hipError_t ir_launch_adain_apply_regions(const AdainApplyRKParams& p, int dtype, hipStream_t s);
 // round 4: the affine / the plain token statistics from the partials the projection GEMMs leave behind (ir_colstats.h)
 struct AdainPartialsKParams {
   const float* style_ws;     // partials of V_self: [(b * Ls / style_rows + c)][H][128]

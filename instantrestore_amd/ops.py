@@ -1282,6 +1282,129 @@ def adain_apply(x: torch.Tensor, a: torch.Tensor, b: torch.Tensor, *, heads: int
     return y
 
 
+def _region_labels(labels, B: int, M: int, Lx: int, n_regions: int):
+    """int32 ``(B or 1, M, L)`` labels -> (tensor kept alive, pointer, lb_sb, lb_sn) of the C ABI's label rows"""
+    n_regions = int(n_regions)
+    if not 1 <= n_regions <= _lib.IR_ADAIN_REGIONS_MAX:
+        raise ValueError(f"n_regions must be in [1, {_lib.IR_ADAIN_REGIONS_MAX}], got {n_regions}")
+    if labels.dtype != torch.int32:
+        raise TypeError(f"labels must be int32, got {labels.dtype}")
+    if labels.dim() != 3 or tuple(labels.shape[1:]) != (M, Lx) or labels.shape[0] not in (1, B):
+        raise ValueError(f"labels: expected ({B}, {M}, {Lx}) (or a batch of 1), got {tuple(labels.shape)}")
+    if labels.stride(2) != 1 or labels.stride(1) < Lx or labels.stride(0) < 0:
+        labels = labels.contiguous()
+    return labels, labels.data_ptr(), (0 if labels.shape[0] == 1 else labels.stride(0)), labels.stride(1)
+
+
+@_on_tensor_device
+def token_stats_regions(x: torch.Tensor, labels: torch.Tensor, *, heads: int, n_regions: int, return_count: bool = False):
+    """:func:`token_stats` per REGION label, every region in one pass over ``x`` (``ir_token_stats_labelled``): the per-region AdaIN
+    statistics.
+
+    ``x`` is ``(B, M, L, H*64)`` as for :func:`token_stats`, ``labels`` int32 ``(B, M, L)`` (a batch dimension of size 1 is shared
+    by the batch; read in place, so a captured graph follows in-place updates).  Returns the mean and the unbiased std over the
+    tokens of every region, two fp32 ``(B, n_regions, M, H, 64)`` tensors (std without eps; region-major, so
+    ``(B * n_regions)`` is a batch of :func:`adain_affine`), and with ``return_count`` the token count as fp32
+    ``(B, n_regions, M)``.  Region ``r`` holds the bytes of ``token_stats_weighted(x, weights=(labels == r))``.  A token whose
+    label lies outside ``[0, n_regions)`` belongs to no region, whatever its bytes; an empty region gives ``(0, 0)`` and count 0,
+    one token ``(x, 0)`` and count 1."""
+    _need_gpu(x, labels)
+    _forward_only(x)
+    x = _ref(x, heads, "x")
+    B, M, Lx, _ = x.shape
+    labels, l_ptr, lb_sb, lb_sn = _region_labels(labels, B, M, Lx, n_regions)
+    R = int(n_regions)
+    L = _lib.lib()
+    nbytes = L.ir_token_stats_labelled_workspace_bytes(B, heads, M, Lx, R)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    mean = torch.empty((B, R, M, heads, HEAD_DIM), dtype=torch.float32, device=x.device)
+    std = torch.empty_like(mean)
+    count = torch.empty((B, R, M), dtype=torch.float32, device=x.device) if return_count else None
+    rc = L.ir_token_stats_labelled(_dtype_code(x), B, heads, M, Lx, R,
+                                  x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), HEAD_DIM,
+                                  l_ptr, lb_sb, lb_sn, mean.data_ptr(), std.data_ptr(),
+                                  count.data_ptr() if return_count else None, ws.data_ptr(), nbytes, _stream())
+    _lib.check(rc, "ir_token_stats_labelled")
+    return (mean, std, count) if return_count else (mean, std)
+
+
+@_on_tensor_device
+def adain_apply_regions(x: torch.Tensor, labels: torch.Tensor, a: torch.Tensor, b: torch.Tensor, *, heads: int,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``y = x*a + b`` over ``(B, N, L, H*64)`` with the affine chosen PER TOKEN by its label (``ir_adain_apply_labelled``).
+
+    ``a``, ``b``: fp32 ``(B, N, R + 1, H, 64)`` contiguous (:func:`adain_affine_regions`); token ``t`` of reference ``(b, n)`` takes
+    slot ``labels[b, n, t]`` if that lies in ``[0, R)`` and slot ``R`` otherwise.  ``labels`` int32 ``(B, N, L)`` (a batch of 1 is
+    shared).  ``out``: a ``(B, N, L, H*64)`` view to write (its own strides; a view into a wider buffer keeps the bytes around it),
+    ``out is x`` works in place; any other overlap is undefined.  A token of region ``r`` gets the bytes of
+    ``adain_apply(x, a[:, :, r], b[:, :, r])``."""
+    _need_gpu(x, labels, a, b, out)
+    _forward_only(x, a, b)
+    if out is not None and out is not x and out.data_ptr() == x.data_ptr() and out.stride() == x.stride():
+        out = x
+    xin = _ref(x, heads, "x")
+    if out is x and xin is not x:
+        raise ValueError("adain_apply_regions in place: x must be 16-byte aligned with a contiguous channel axis and strides that are multiples of 8")
+    B, N, Lx, _ = xin.shape
+    if a.dim() != 5 or a.shape != b.shape or a.shape[0] != B or a.shape[1] != N or tuple(a.shape[3:]) != (heads, HEAD_DIM) or a.shape[2] < 2:
+        raise ValueError(f"a, b: expected two ({B}, {N}, R + 1, {heads}, 64) tensors, got {tuple(a.shape)} / {tuple(b.shape)}")
+    for t in (a, b):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("a, b must be contiguous fp32")
+    R = a.shape[2] - 1
+    labels, l_ptr, lb_sb, lb_sn = _region_labels(labels, B, N, Lx, R)
+    if out is None:
+        y = torch.empty_like(xin, memory_format=torch.contiguous_format)
+    else:
+        y = xin if out is x else out
+        if y.shape != xin.shape or y.dtype != xin.dtype:
+            raise ValueError(f"out: expected {tuple(xin.shape)} {xin.dtype}, got {tuple(y.shape)} {y.dtype}")
+        if y.stride(-1) != 1 or any(y.stride(i) % 8 for i in range(3)) or y.data_ptr() % 16:
+            raise ValueError("out must be 16-byte aligned with a contiguous channel axis and strides that are multiples of 8")
+    rc = _lib.lib().ir_adain_apply_labelled(_dtype_code(xin), B, heads, N, Lx, R,
+                                           xin.data_ptr(), xin.stride(0), xin.stride(1), xin.stride(2), HEAD_DIM,
+                                           l_ptr, lb_sb, lb_sn, a.data_ptr(), b.data_ptr(),
+                                           y.data_ptr(), y.stride(0), y.stride(1), y.stride(2), HEAD_DIM, _stream())
+    _lib.check(rc, "ir_adain_apply_labelled")
+    return y
+
+
+def adain_affine_regions(style, content, style_global, content_global, *, min_tokens: int = 8, eps: float = ADAIN_EPS):
+    """The per-region AdaIN affine table ``(a, b)``, two fp32 ``(B, N, R + 1, H, 64)`` tensors for :func:`adain_apply_regions`.
+
+    ``style = (mean, std, count)`` of ``token_stats_regions(v_self.unsqueeze(1), ...)`` - ``(B, R, 1, H, 64)`` / ``(B, R, 1)`` -
+    ``content = (mean, std, count)`` of the references - ``(B, R, N, H, 64)`` / ``(B, R, N)`` - and the globals are what
+    :func:`token_stats` gives: ``style_global = (mean, std)`` ``(B, 1, H, 64)``, ``content_global`` ``(B, N, H, 64)``.
+    Slot ``(b, n, r)`` uses the regional pair when ``style_count[b, r] >= min_tokens`` AND ``content_count[b, r, n] >= min_tokens``;
+    otherwise BOTH sides take the global statistics (a ``torch.where`` on the device, no sync), so a fallen-back slot is the
+    ordinary affine bit for bit and an absent region never gives the ``a ~ eps / sigma`` of ``(0, 0)`` statistics.  Slot ``R``
+    (tokens of no region) is the ordinary affine.  Two :func:`adain_affine` calls."""
+    s_mean, s_std, s_cnt = style
+    c_mean, c_std, c_cnt = content
+    (sg_mean, sg_std), (cg_mean, cg_std) = style_global, content_global
+    if c_mean.dim() != 5 or c_mean.shape != c_std.shape or c_mean.shape[-1] != HEAD_DIM:
+        raise ValueError(f"content statistics must be two (B, R, N, H, 64) tensors, got {tuple(c_mean.shape)} / {tuple(c_std.shape)}")
+    B, R, N, H, _ = c_mean.shape
+    if tuple(s_mean.shape) != (B, R, 1, H, HEAD_DIM) or s_std.shape != s_mean.shape:
+        raise ValueError(f"style statistics must be two ({B}, {R}, 1, {H}, 64) tensors, got {tuple(s_mean.shape)} / {tuple(s_std.shape)}")
+    if tuple(s_cnt.shape) != (B, R, 1) or tuple(c_cnt.shape) != (B, R, N):
+        raise ValueError(f"counts must be ({B}, {R}, 1) and ({B}, {R}, {N}), got {tuple(s_cnt.shape)} / {tuple(c_cnt.shape)}")
+    if tuple(cg_mean.shape) != (B, N, H, HEAD_DIM) or cg_std.shape != cg_mean.shape:
+        raise ValueError(f"content_global must be two ({B}, {N}, {H}, 64) tensors, got {tuple(cg_mean.shape)} / {tuple(cg_std.shape)}")
+    if sg_mean.shape != sg_std.shape or tuple(sg_mean.shape) not in ((B, H, HEAD_DIM), (B, 1, H, HEAD_DIM)):
+        raise ValueError(f"style_global must be two ({B}, 1, {H}, 64) tensors, got {tuple(sg_mean.shape)} / {tuple(sg_std.shape)}")
+    sg_mean, sg_std = sg_mean.reshape(B, 1, 1, H, HEAD_DIM), sg_std.reshape(B, 1, 1, H, HEAD_DIM)
+    regional = ((s_cnt >= min_tokens) & (c_cnt >= min_tokens)).reshape(B, R, N, 1, 1)
+    # one (style, content) pair per (b, r, n): the fallback of a slot replaces both of its sides
+    pick = lambda reg, glob: torch.where(regional, reg, glob).reshape(B * R * N, H, HEAD_DIM).contiguous()
+    st = (pick(s_mean, sg_mean), pick(s_std, sg_std))
+    ct = (pick(c_mean, cg_mean.unsqueeze(1)).unsqueeze(1), pick(c_std, cg_std.unsqueeze(1)).unsqueeze(1))
+    ar, br = adain_affine(st, ct, eps=eps)                                                          # (B*R*N, 1, H, 64)
+    ag, bg = adain_affine((sg_mean.reshape(B, H, HEAD_DIM), sg_std.reshape(B, H, HEAD_DIM)), (cg_mean, cg_std), eps=eps)   # (B, N, H, 64)
+    table = lambda reg, glob: torch.cat([reg.reshape(B, R, N, H, HEAD_DIM).permute(0, 2, 1, 3, 4), glob.unsqueeze(2)], dim=2).contiguous()
+    return table(ar, ag), table(br, bg)
+
+
 @_on_tensor_device
 def zero_invalid_refs(k: torch.Tensor, v: torch.Tensor, valid_indices: torch.Tensor, *, heads: int) -> None:
     """In place: zero K and V of references ``n >= valid_indices[b]`` (``ir_zero_invalid_refs``;

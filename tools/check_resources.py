@@ -9,12 +9,13 @@ import re
 import subprocess
 import sys
 
-NO_SCRATCH = ("linear_tiled", "shared_attn_fwd_w128", "attn_rows_kernel", "attn_match_kernel", "attn_transfer_kernel", "attn_received_kernel", "attn_topk_kernel", "attn_key_match_kernel")     # mangled-name substrings: scratch / spills are a build error for these kernels
+NO_SCRATCH = ("linear_tiled", "shared_attn_fwd_w128", "attn_rows_kernel", "attn_match_kernel", "attn_transfer_kernel", "attn_received_kernel", "attn_topk_kernel", "attn_key_match_kernel", "token_stats_regions", "adain_apply_regions")     # mangled-name substrings: scratch / spills are a build error for these kernels
 # (attn_rows_kernel / attn_match_kernel hold up to 96 / 192 fp32 sums per lane across their head walk: a spill would put them in scratch memory;
 # attn_transfer_kernel keeps up to 27 running sums, 27 head totals and 48 probabilities beside its operands;
 # attn_received_kernel up to 128 running sums, and its head-mean form runs two waves per SIMD: 256 registers at the most;
 # attn_topk_kernel keeps attn_match_kernel's sums and up to 3 sorted lists of 8 (value, key) pairs per lane: a spilled list would be indexed in scratch;
-# attn_key_match_kernel keeps 32 (value, row) pairs per lane and, in its head-mean form, 32 head sums and two steps of K and Q fragments)
+# attn_key_match_kernel keeps 32 (value, row) pairs per lane and, in its head-mean form, 32 head sums and two steps of K and Q fragments;
+# token_stats_regions_partial_kernel keeps 8 rows of x and their labels in registers across its region loop: indexed from scratch they would be read R times)
 
 
 def demangle(name):
