@@ -22,6 +22,10 @@ fp16 ulp at 1.0 is 2.4e-4, at 4.0 it is 9.8e-4.)
 `factor` scales BOTH (e.g. tuning 11's extra rounding of Q: 2).  `reg_factor` scales the regression bound only and is given,
 with its reason, by the few callers whose inputs are outside N(0,1) activations (peaky logits, massive activations).
 
+Both bounds are max-norms over the tensor, calibrated on N(0, 1) activations.  The ELEMENT-WISE bound of the fp32 result on inputs that
+move the kernels' lazy softmax reference (the accumulator and AdaIN-fold rescale, the merge of K/V-range pieces) is tests/out_bounds.py,
+used by tests/test_gpu_out_walks.py; the LSE and the segment masses are held by tests/lse_bounds.py.
+
 IR_PARITY_LOG=<file> appends one JSON record per comparison (the distribution behind the constants above);
 IR_PARITY_SOFT=1 records regression-bound violations there without failing (calibration runs only - never set by the driver).
 """

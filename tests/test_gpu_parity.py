@@ -18,6 +18,7 @@ import torch
 
 from conftest import GOLDEN_MANIFEST
 from lse_bounds import check_lse, pack_keys, q_rounded_like_tuning_11, row_scale
+from out_bounds import check_out, oracle_out_and_scales
 from parity_bounds import check_before_rounding, check_parity
 from oracle import shared_attn_oracle as O
 
@@ -777,6 +778,13 @@ def test_massive_activation_channels(ops, dtype, variant):
     try:
         aff = ops.adain_stats(c(v), c(rv), heads=H)
         out = ops.shared_attention(c(q), c(k), c(v), c(rk), c(rv), heads=H, scale=0.125, include_self=True, adain=aff)
+        out32 = ops.shared_attention(c(q), c(k), c(v), c(rk), c(rv), heads=H, scale=0.125, include_self=True, adain=aff, out_dtype=torch.float32)
     finally:
         ops.set_attn_variant(0)
     _check(out, ref, dtype, "massive activations")
+    # the result before the output rounding, every element, to the element-wise bound of tests/out_bounds.py (the oracle on the
+    # launch's own fp32 affine); the 16-bit launch is that result rounded
+    assert torch.equal(out32.to(dtype), out)
+    ref_o = oracle_out_and_scales(_np64(q), pack_keys(k, rk, True), pack_keys(v, rv, True), H, 0.125, [L] * (N + 1),
+                                  affine=tuple(t.cpu().double().numpy().reshape(B, N, C) for t in aff))
+    print(f"out ratio {check_out(out32, ref_o, dtype, f'massive activations, tuning {variant}'):.3f}")

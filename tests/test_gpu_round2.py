@@ -7,6 +7,7 @@ import torch
 
 from oracle import shared_attn_oracle as O
 from lse_bounds import check_lse, pack_keys, row_scale
+from out_bounds import check_out, oracle_out_and_scales
 from parity_bounds import check_parity
 
 pytestmark = pytest.mark.gpu
@@ -320,10 +321,18 @@ def test_reference_checked_after_the_exponentials(variant, case, dtype):
                                         include_self=True, adain=aff, return_lse=True, q_prescaled=True)
         name = ops.shared_attention_kernel_name(qp.cuda(), k.cuda(), v.cuda(), rk.cuda(), rv.cuda(), heads=H, scale=0.125,
                                                 include_self=True, adain=aff, q_prescaled=True)
+        out32 = ops.shared_attention(qp.cuda(), k.cuda(), v.cuda(), rk.cuda(), rv.cuda(), heads=H, scale=0.125, include_self=True,
+                                     adain=aff, q_prescaled=True, out_dtype=torch.float32)
     finally:
         ops.set_attn_variant(0)
     assert {13: "w64", 11: "pipe", 18: "pipe", 16: "w128"}[variant] in name, name
     check_parity(out[:, rows], ref, dtype, f"reference checked after the exponentials ({name})")
+    # the result before the output rounding, every element of the sampled rows, to the element-wise bound of tests/out_bounds.py
+    # (the oracle on the launch's own fp32 affine); the 16-bit launch is that result rounded
+    assert torch.equal(out32.to(dtype), out)
+    ref_o = oracle_out_and_scales(q_equiv, pack_keys(k, rk, True), pack_keys(v, rv, True), H, 0.125, [L] + [Lr] * N,
+                                  affine=tuple(t.cpu().double().numpy().reshape(B, N, C) for t in aff))
+    print(f"out ratio {check_out(out32[:, rows], ref_o, dtype, f'reference checked after the exponentials ({name}, {case})', frame=True):.3f}")
     qh = O.head_to_batch_dim_np(q_equiv, H)
     ek, _ = O.extended_kv_np(f(k), f(v), f(rk), f(rv), H, False, True)
     sc = np.matmul(qh, ek.transpose(0, 2, 1)) * 0.125
