@@ -30,7 +30,7 @@ library's GEMMs do not cover, or one left to the module call (biased / unfoldabl
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 from torch import nn
@@ -121,47 +121,72 @@ def _mask_bias(mask, batch: int, heads: int, lkv: int, len_self: int, shared: bo
     return mask[:, 0] if mask.stride(1) == 0 else mask
 
 
-# bias rows of ``ref_weights`` / ``ref_token_keep``, built once per (kwargs identity and version, key-axis geometry): the nine shared
-# layers of a step have three geometries, so they build three rows.  In-place changes of the tensors bump their version.
-_BIAS_ROWS: dict = {}
-_BIAS_ROWS_MAX = 8
+class _IdentityCache(dict):
+    """what a shared layer builds from caller tensors, kept per (identity and version of every source, geometry): the nine shared
+    layers of a step have three geometries, so they build three values.  An in-place change of a source bumps its version; a
+    reused ``id`` is caught by the ``is`` check on the hit.  Bounded: the oldest entry leaves first."""
+
+    def __init__(self, limit: int):
+        super().__init__()
+        self.limit = limit
+
+    def cached(self, sources: tuple, geometry: tuple, build):
+        """the value of ``build()`` for these ``sources`` (any may be ``None``) on this ``geometry``"""
+        key = tuple(None if t is None else (id(t), getattr(t, "_version", None)) for t in sources) + geometry
+        hit = self.get(key)
+        if hit is not None and all(a is b for a, b in zip(hit[0], sources)):
+            return hit[1]
+        value = build()
+        while len(self) >= self.limit:
+            self.pop(next(iter(self)))
+        self[key] = (sources, value)
+        return value
+
+
+_BIAS_ROWS_MAX = _REGION_PAIRS_MAX = _ADAIN_WEIGHTS_MAX = _ADAIN_REGION_LABELS_MAX = 8
+_BIAS_ROWS = _IdentityCache(_BIAS_ROWS_MAX)                         # bias rows of ``ref_weights`` / ``ref_token_keep``
+_REGION_PAIRS = _IdentityCache(_REGION_PAIRS_MAX)                   # (q_allow, key_region) of ``region_labels`` / ``region_allow``
+_ADAIN_WEIGHTS = _IdentityCache(_ADAIN_WEIGHTS_MAX)                 # (self weights, reference weights) of ``adain_weights``
+_ADAIN_REGION_LABELS = _IdentityCache(_ADAIN_REGION_LABELS_MAX)     # (self labels, reference labels) of ``adain_regions``: int32 rows
+
+_GRID_DTYPE = {"region_labels": None, "adain_weights": torch.float32, "adain_regions": torch.int32}
+
+
+def _on_grid(values, length: int, refs: bool, device, kwarg: str):
+    """a picture ``(B, [N,] Hpx, Wpx)`` or per-token values ``(B, [N,] L)`` (the row-major picture of their own square grid) of
+    ``kwarg``, sampled at the token centres of the square grid of ``length`` tokens, on ``device``:
+
+    ``region_labels``: integer labels (``attn_maps.token_labels``) in their own dtype, ``(B, [N *] length)`` - the key axis lays the
+    references end to end; ``length`` must be a square up front and per-token labels always pass through their own grid.
+    ``adain_weights``: float or bool weights (``attn_maps.token_weights``) -> fp32 ``(B, [N,] length)``.  ``adain_regions``: integer
+    labels -> int32 ``(B, [N,] length)``.  Both take per-token values of exactly ``length`` as they are, square or not."""
+    from . import attn_maps as _maps
+    packed, weights, dtype = kwarg == "region_labels", kwarg == "adain_weights", _GRID_DTYPE[kwarg]
+    what = f"{kwarg}: the {'reference' if refs else 'self' if weights else 'query'} {'weights' if weights else 'labels'}"
+    len_name = what if not packed else "len_ref" if refs else "len_q"
+    side = _maps._square_side(length, len_name) if packed else None
+    t = torch.as_tensor(values)
+    pictures = 4 if refs else 3
+    if t.dim() == pictures - 1:      # per-token values
+        if not packed and t.shape[-1] == length:
+            return t.to(device=device, dtype=dtype).contiguous()
+        s = _maps._square_side(t.shape[-1], f"{len_name}: the per-token labels' length" if packed else f"{what}' length")
+        t = t.reshape(*t.shape[:-1], s, s)
+    if t.dim() != pictures:
+        raise ValueError(f"{what} must be {'a weight picture' if weights else 'label pictures'} {'(B, N, Hpx, Wpx)' if refs else '(B, Hpx, Wpx)'} "
+                         f"or per-token {'weights' if weights else 'labels'}, got {tuple(torch.as_tensor(values).shape)}")
+    picked = (_maps.token_weights if weights else _maps.token_labels)(t, side or _maps._square_side(length, len_name))
+    if not packed:
+        picked = picked.reshape(*t.shape[:-2], length)
+    return picked.to(device=device, dtype=dtype).contiguous()
 
 
 def _ref_bias_row(ref_weights, ref_token_keep, batch: int, len_self: int, n_refs: int, len_ref: int, include_self: bool, device):
     if ref_weights is None and ref_token_keep is None:
         return None
-    ver = lambda t: (id(t), getattr(t, "_version", None)) if t is not None else None
-    key = (ver(ref_weights), ver(ref_token_keep), batch, len_self, n_refs, len_ref, include_self, str(device))
-    hit = _BIAS_ROWS.get(key)
-    if hit is not None and hit[0] is ref_weights and hit[1] is ref_token_keep:
-        return hit[2]
-    row = _ops.key_bias(batch, len_self, n_refs, len_ref, include_self, ref_weights=ref_weights, ref_token_keep=ref_token_keep, device=device)
-    while len(_BIAS_ROWS) >= _BIAS_ROWS_MAX:
-        _BIAS_ROWS.pop(next(iter(_BIAS_ROWS)))
-    _BIAS_ROWS[key] = (ref_weights, ref_token_keep, row)
-    return row
-
-
-# (q_allow, key_region) of ``region_labels`` / ``region_allow``, built once per (kwargs identity and version, key-axis geometry) the way
-# _BIAS_ROWS caches bias rows: the nine shared layers of a step have three geometries, so they build three pairs
-_REGION_PAIRS: dict = {}
-_REGION_PAIRS_MAX = 8
-
-
-def _labels_on_grid(labels, length: int, what: str):
-    """label pictures ``(B, [N,] Hpx, Wpx)`` or per-token labels ``(B, [N,] L)`` (the row-major picture of their own square grid) sampled
-    at the token centres of the square grid of ``length`` tokens (``attn_maps.token_labels``) -> ``(B, [N *] length)``"""
-    from . import attn_maps as _maps
-    side = _maps._square_side(length, what)
-    t = torch.as_tensor(labels)
-    pictures = 3 if what == "len_q" else 4
-    if t.dim() == pictures - 1:      # per-token labels
-        s = _maps._square_side(t.shape[-1], f"{what}: the per-token labels' length")
-        t = t.reshape(*t.shape[:-1], s, s)
-    if t.dim() != pictures:
-        raise ValueError(f"region_labels: the {'query' if pictures == 3 else 'reference'} labels must be label pictures "
-                         f"{'(B, Hpx, Wpx)' if pictures == 3 else '(B, N, Hpx, Wpx)'} or per-token labels, got {tuple(torch.as_tensor(labels).shape)}")
-    return _maps.token_labels(t, side)
+    return _BIAS_ROWS.cached((ref_weights, ref_token_keep), (batch, len_self, n_refs, len_ref, include_self, str(device)),
+                             lambda: _ops.key_bias(batch, len_self, n_refs, len_ref, include_self, ref_weights=ref_weights,
+                                                   ref_token_keep=ref_token_keep, device=device))
 
 
 def _region_pair(region_labels, region_allow, batch: int, len_q: int, len_self: int, n_refs: int, len_ref: int,
@@ -171,120 +196,54 @@ def _region_pair(region_labels, region_allow, batch: int, len_q: int, len_self: 
     if region_allow is None:
         raise ValueError("region_labels needs region_allow: the (C, C) bool matrix or the (C,) bitmasks of ops.region_masks")
     q_lab, r_lab = region_labels
-    ver = lambda t: (id(t), getattr(t, "_version", None))
-    key = (ver(q_lab), ver(r_lab), ver(region_allow), batch, len_q, len_self, n_refs, len_ref, include_self, str(device))
-    hit = _REGION_PAIRS.get(key)
-    if hit is not None and hit[0] is q_lab and hit[1] is r_lab and hit[2] is region_allow:
-        return hit[3]
-    ql = _labels_on_grid(q_lab, len_q, "len_q").to(device)
-    rl = _labels_on_grid(r_lab, len_ref, "len_ref").to(device)
-    if ql.shape[0] != batch or rl.shape[0] != batch or rl.shape[1] != n_refs * len_ref:
-        raise ValueError(f"region_labels: labels of {tuple(ql.shape)} query and {tuple(rl.shape)} reference tokens for a batch of {batch} with "
-                         f"{n_refs} references of {len_ref} tokens")
-    parts = [rl.to(torch.int64)]
-    if include_self:     # the self keys are this picture's own tokens: the query labels on the self grid
-        parts.insert(0, (ql if len_self == len_q else _labels_on_grid(q_lab, len_self, "len_q").to(device)).to(torch.int64))
-    pair = _ops.region_masks(ql, torch.cat(parts, dim=1), torch.as_tensor(region_allow).to(device),
-                             self_len=len_self if include_self else 0, self_free=True)    # a token always sees its own picture
-    while len(_REGION_PAIRS) >= _REGION_PAIRS_MAX:
-        _REGION_PAIRS.pop(next(iter(_REGION_PAIRS)))
-    _REGION_PAIRS[key] = (q_lab, r_lab, region_allow, pair)
-    return pair
 
+    def build():
+        ql = _on_grid(q_lab, len_q, False, device, "region_labels")
+        rl = _on_grid(r_lab, len_ref, True, device, "region_labels")
+        if ql.shape[0] != batch or rl.shape[0] != batch or rl.shape[1] != n_refs * len_ref:
+            raise ValueError(f"region_labels: labels of {tuple(ql.shape)} query and {tuple(rl.shape)} reference tokens for a batch of {batch} with "
+                             f"{n_refs} references of {len_ref} tokens")
+        parts = [rl.to(torch.int64)]
+        if include_self:     # the self keys are this picture's own tokens: the query labels on the self grid
+            parts.insert(0, (ql if len_self == len_q else _on_grid(q_lab, len_self, False, device, "region_labels")).to(torch.int64))
+        return _ops.region_masks(ql, torch.cat(parts, dim=1), torch.as_tensor(region_allow).to(device),
+                                 self_len=len_self if include_self else 0, self_free=True)    # a token always sees its own picture
 
-# (self weights, reference weights) of ``adain_weights``, sampled once per (kwargs identity and version, layer geometry) the way
-# _REGION_PAIRS caches region pairs
-_ADAIN_WEIGHTS: dict = {}
-_ADAIN_WEIGHTS_MAX = 8
-
-
-def _weights_on_grid(weights, length: int, refs: bool, device):
-    """a weight picture ``(B, [N,] Hpx, Wpx)`` or per-token weights ``(B, [N,] L)`` (the row-major picture of their own square grid),
-    float or bool, sampled at the token centres of the square grid of ``length`` tokens (``attn_maps.token_weights``) -> fp32
-    ``(B, [N,] length)`` on ``device``"""
-    from . import attn_maps as _maps
-    what = "adain_weights: the reference weights" if refs else "adain_weights: the self weights"
-    t = torch.as_tensor(weights)
-    pictures = 4 if refs else 3
-    if t.dim() == pictures - 1:      # per-token weights
-        if t.shape[-1] == length:
-            return t.to(device=device, dtype=torch.float32).contiguous()
-        s = _maps._square_side(t.shape[-1], f"{what}' length")
-        t = t.reshape(*t.shape[:-1], s, s)
-    if t.dim() != pictures:
-        raise ValueError(f"{what} must be a weight picture {'(B, N, Hpx, Wpx)' if refs else '(B, Hpx, Wpx)'} or per-token weights, "
-                         f"got {tuple(torch.as_tensor(weights).shape)}")
-    return _maps.token_weights(t, _maps._square_side(length, what)).to(device)
+    return _REGION_PAIRS.cached((q_lab, r_lab, region_allow), (batch, len_q, len_self, n_refs, len_ref, include_self, str(device)), build)
 
 
 def _adain_weight_pair(adain_weights, batch: int, len_self: int, n_refs: int, len_ref: int, device):
     if not isinstance(adain_weights, (tuple, list)) or len(adain_weights) != 2:
         raise ValueError("adain_weights must be the pair (self_weights, ref_weights); either may be None")
     self_w, ref_w = adain_weights
-    ver = lambda t: (id(t), getattr(t, "_version", None)) if t is not None else None
-    key = (ver(self_w), ver(ref_w), batch, len_self, n_refs, len_ref, str(device))
-    hit = _ADAIN_WEIGHTS.get(key)
-    if hit is not None and hit[0] is self_w and hit[1] is ref_w:
-        return hit[2]
-    sw = None if self_w is None else _weights_on_grid(self_w, len_self, False, device)
-    rw = None if ref_w is None else _weights_on_grid(ref_w, len_ref, True, device)
-    if sw is not None and tuple(sw.shape) != (batch, len_self):
-        raise ValueError(f"adain_weights: self weights of {tuple(sw.shape)} tokens for a batch of {batch} with {len_self} tokens")
-    if rw is not None and tuple(rw.shape) != (batch, n_refs, len_ref):
-        raise ValueError(f"adain_weights: reference weights of {tuple(rw.shape)} tokens for a batch of {batch} with {n_refs} references "
-                         f"of {len_ref} tokens")
-    pair = (sw, rw)
-    while len(_ADAIN_WEIGHTS) >= _ADAIN_WEIGHTS_MAX:
-        _ADAIN_WEIGHTS.pop(next(iter(_ADAIN_WEIGHTS)))
-    _ADAIN_WEIGHTS[key] = (self_w, ref_w, pair)
-    return pair
 
+    def build():
+        sw = None if self_w is None else _on_grid(self_w, len_self, False, device, "adain_weights")
+        rw = None if ref_w is None else _on_grid(ref_w, len_ref, True, device, "adain_weights")
+        if sw is not None and tuple(sw.shape) != (batch, len_self):
+            raise ValueError(f"adain_weights: self weights of {tuple(sw.shape)} tokens for a batch of {batch} with {len_self} tokens")
+        if rw is not None and tuple(rw.shape) != (batch, n_refs, len_ref):
+            raise ValueError(f"adain_weights: reference weights of {tuple(rw.shape)} tokens for a batch of {batch} with {n_refs} references "
+                             f"of {len_ref} tokens")
+        return sw, rw
 
-# (self labels, reference labels) of ``adain_regions``, sampled once per (kwargs identity and version, layer geometry) the way
-# _REGION_PAIRS caches region pairs: int32 (B, len_self) / (B, N, len_ref), the label rows of ops.token_stats_regions
-_ADAIN_REGION_LABELS: dict = {}
-_ADAIN_REGION_LABELS_MAX = 8
-
-
-def _adain_labels_on_grid(labels, length: int, refs: bool, device):
-    """integer label pictures ``(B, [N,] Hpx, Wpx)`` or per-token labels ``(B, [N,] L)`` (the row-major picture of their own square
-    grid) sampled at the token centres of the square grid of ``length`` tokens (``attn_maps.token_labels``) -> int32
-    ``(B, [N,] length)`` on ``device``"""
-    from . import attn_maps as _maps
-    what = "adain_regions: the reference labels" if refs else "adain_regions: the query labels"
-    t = torch.as_tensor(labels)
-    pictures = 4 if refs else 3
-    if t.dim() == pictures - 1:      # per-token labels
-        if t.shape[-1] == length:
-            return t.to(device=device, dtype=torch.int32).contiguous()
-        s = _maps._square_side(t.shape[-1], f"{what}' length")
-        t = t.reshape(*t.shape[:-1], s, s)
-    if t.dim() != pictures:
-        raise ValueError(f"{what} must be label pictures {'(B, N, Hpx, Wpx)' if refs else '(B, Hpx, Wpx)'} or per-token labels, "
-                         f"got {tuple(torch.as_tensor(labels).shape)}")
-    picked = _maps.token_labels(t, _maps._square_side(length, what))         # (B, [N *] length)
-    return picked.reshape(*t.shape[:-2], length).to(device=device, dtype=torch.int32).contiguous()
+    return _ADAIN_WEIGHTS.cached((self_w, ref_w), (batch, len_self, n_refs, len_ref, str(device)), build)
 
 
 def _adain_region_labels(adain_regions, batch: int, len_self: int, n_refs: int, len_ref: int, device):
     if not isinstance(adain_regions, (tuple, list)) or len(adain_regions) != 2 or adain_regions[0] is None or adain_regions[1] is None:
         raise ValueError("adain_regions must be the pair (query_labels, ref_labels)")
     q_lab, r_lab = adain_regions
-    ver = lambda t: (id(t), getattr(t, "_version", None))
-    key = (ver(q_lab), ver(r_lab), batch, len_self, n_refs, len_ref, str(device))
-    hit = _ADAIN_REGION_LABELS.get(key)
-    if hit is not None and hit[0] is q_lab and hit[1] is r_lab:
-        return hit[2]
-    ql = _adain_labels_on_grid(q_lab, len_self, False, device)
-    rl = _adain_labels_on_grid(r_lab, len_ref, True, device)
-    if tuple(ql.shape) != (batch, len_self) or tuple(rl.shape) != (batch, n_refs, len_ref):
-        raise ValueError(f"adain_regions: labels of {tuple(ql.shape)} query and {tuple(rl.shape)} reference tokens for a batch of {batch} "
-                         f"with {len_self} tokens and {n_refs} references of {len_ref} tokens")
-    pair = (ql, rl)
-    while len(_ADAIN_REGION_LABELS) >= _ADAIN_REGION_LABELS_MAX:
-        _ADAIN_REGION_LABELS.pop(next(iter(_ADAIN_REGION_LABELS)))
-    _ADAIN_REGION_LABELS[key] = (q_lab, r_lab, pair)
-    return pair
+
+    def build():
+        ql = _on_grid(q_lab, len_self, False, device, "adain_regions")
+        rl = _on_grid(r_lab, len_ref, True, device, "adain_regions")
+        if tuple(ql.shape) != (batch, len_self) or tuple(rl.shape) != (batch, n_refs, len_ref):
+            raise ValueError(f"adain_regions: labels of {tuple(ql.shape)} query and {tuple(rl.shape)} reference tokens for a batch of {batch} "
+                             f"with {len_self} tokens and {n_refs} references of {len_ref} tokens")
+        return ql, rl
+
+    return _ADAIN_REGION_LABELS.cached((q_lab, r_lab), (batch, len_self, n_refs, len_ref, str(device)), build)
 
 
 def _kv_source(attn, st: _Prepared) -> torch.Tensor:
@@ -559,7 +518,7 @@ class AttnProcessor(nn.Module):
         weights = getattr(self, "capture_stats_weights", None)
         if self.capture_stats and self.values.is_cuda and weights is not None:
             # mask-aware statistics: one weighted pass over V (the GEMM's partials are unweighted); the pair travels like any other
-            w = _weights_on_grid(weights, self.values.shape[1], True, self.values.device)
+            w = _on_grid(weights, self.values.shape[1], True, self.values.device, "adain_weights")
             if w.shape[0] * w.shape[1] != self.values.shape[0]:
                 raise ValueError(f"capture_stats_weights of {tuple(w.shape)} tokens for {self.values.shape[0]} captured references")
             m, sd = _ops.token_stats_weighted(self.values.unsqueeze(1), heads=attn.heads, weights=w.reshape(-1, 1, w.shape[-1]))
@@ -645,6 +604,204 @@ class FaceIDAttnProcessor(nn.Module):
         kw = {"key_bias": bias} if bias is not None else {}
         tokens = _ops.shared_attention(query, key, value, heads=attn.heads, scale=attn.scale, include_self=True, **kw)
         return _epilogue(attn, st, tokens)
+
+
+# ------------------------------------------------------------------------------------------
+# the read-outs of a shared layer: one declaration each; refusals, validation, want_lse and the launches follow the table
+# ------------------------------------------------------------------------------------------
+class _Readout(NamedTuple):
+    switch: str                     # the attribute that switches it on: anything but None, on shared layers (see ``flag``)
+    entry: str                      # the C entry point, as the refusals name it
+    op: str                         # the ``_ops`` function: op(query, key, ref_k, lse, *args, heads=, scale=, include_self=, ...)
+    result: str                     # the attribute that receives what it returns
+    listed: int                     # its place among the names of the region refusal
+    args: Tuple[str, ...] = ()      # attributes handed on after ``lse``, in order
+    sentinel: Optional[str] = None  # the string the LAST of ``args`` may be instead of a tensor (handed on as None: every token)
+    takes: str = "an integer tensor"    # ... and what it is otherwise, for the message
+    reduce: Optional[str] = None    # its ``*_reduce`` attribute (default "head_mean"); the switch itself: validated here
+    extra: Tuple[Tuple[str, str, object], ...] = ()    # further (keyword, attribute, default)
+    flag: bool = False              # the switch is a bool instead, honoured on every layer (the dump)
+    paired: bool = False            # shares one message per rule with the other paired rows
+
+
+# in launch order: a captured step contains the launches in this order
+_READOUTS = (
+    _Readout("attention_rows_index", "ir_attn_rows", "attn_rows", "attention_rows", 1, args=("attention_rows_index",),
+             reduce="attention_rows_reduce", paired=True),
+    _Readout("attention_match_index", "ir_attn_match", "attn_match", "attention_match", 2, args=("attention_match_index",), sentinel="all",
+             reduce="attention_match_reduce"),
+    _Readout("attention_transfer_payload", "ir_attn_transfer", "attn_transfer", "attention_transfer", 4,
+             args=("attention_transfer_payload", "attention_transfer_index"), sentinel="all", reduce="attention_transfer_reduce"),
+    _Readout("attention_received_weights", "ir_attn_received", "attn_received", "attention_received", 5, args=("attention_received_weights",),
+             sentinel="ones", takes="an fp32 tensor", reduce="attention_received_reduce"),
+    _Readout("attention_topk_index", "ir_attn_topk", "attn_topk", "attention_topk", 3, args=("attention_topk_index",), sentinel="all",
+             reduce="attention_topk_reduce", extra=(("k", "attention_topk_k", 4),)),
+    _Readout("attention_key_match_reduce", "ir_attn_key_match", "attn_key_match", "attention_key_match", 6, reduce="attention_key_match_reduce"),
+    # (B, H, L, Lkv), columns [self?] ++ ref0 ++ ... ++ refN-1, in the compute dtype: launched last, refused and listed first
+    _Readout("save_self_attentions", "ir_attn_probs", "attn_probs", "attention_probs", 0, flag=True, paired=True),
+)
+_REDUCES = ("none", "head_mean")
+LN2 = 0.6931471805599453    # a pre-scaled query carries scale * log2(e): its scores are exponents, ln 2 turns them into the logits of the LSE
+
+
+_SWITCHES = tuple((r.switch, r.flag, r) for r in _READOUTS)     # (every call of every layer walks the switches: no field lookups)
+
+
+def _readouts_on(proc, shared: bool):
+    """the rows of the table that this call of ``proc`` launches, in launch order"""
+    if shared:
+        return [r for n, flag, r in _SWITCHES if (getattr(proc, n, None) if flag else getattr(proc, n, None) is not None)]
+    return [r for n, flag, r in _SWITCHES if flag and getattr(proc, n, None)]
+
+
+def _rule_text(row: _Readout, text: str) -> str:
+    """``text`` about ``row`` - or about the pair ``save_self_attentions / attention_rows_index``, which shares one"""
+    rows = sorted((r for r in _READOUTS if r.paired), key=lambda r: r.listed) if row.paired else [row]
+    text = text.format(names=" / ".join(r.switch for r in rows), entries=" and ".join(r.entry for r in rows))
+    return text.replace(" does not ", " do not ") if row.paired else text      # (two kernels: the plural)
+
+
+def _refuse(proc, on, *, biased: bool, counts, cstats, ref_v, ref_valid, region_labels, region_allow, adain_weights, adain_regions,
+            adain_n_regions) -> None:
+    """every refusal that the kwargs and the attributes decide, before anything is launched.  ``on``: the read-outs of this call;
+    ``biased``: a mask, ``ref_weights`` or ``ref_token_keep`` will make a key bias; ``counts`` / ``cstats`` / ``ref_v``: this layer's
+    entries of ``ref_lens`` / ``ref_stats`` / ``ref_values`` (``None`` on a layer that shares nothing, like the four kwargs)"""
+    first = next((r for r in on if r.paired), on[0]) if on else None     # the read-out a rule names: the pair's message leads
+    if region_labels is not None:
+        if region_allow is None:
+            raise ValueError("region_labels needs region_allow: the (C, C) bool matrix or the (C,) bitmasks of ops.region_masks")
+        if biased:
+            raise NotImplementedError("region_labels together with an attention mask, ref_weights or ref_token_keep: the kernel carries either "
+                                      "the key bias or the region test; regions with a key bias are a follow-up")
+        if counts is not None:
+            raise NotImplementedError("region_labels together with ref_lens: key_region indexes the packed uniform key axis; regions with "
+                                      "per-reference counts are a follow-up")
+        if on:
+            raise NotImplementedError(f"region_labels together with {', '.join(r.switch for r in sorted(on, key=lambda r: r.listed))}: "
+                                      "the read-out kernels do not take regions yet (their exp(s - lse) would count the pairs the forward "
+                                      "left out; follow-up); save_attention_mass honours the regions")
+    if adain_regions is not None:
+        if adain_n_regions is None:
+            raise ValueError("adain_regions needs adain_n_regions (1 ... 32): inferring it from the labels would need a device sync")
+        if adain_weights is not None:
+            raise NotImplementedError("adain_regions together with adain_weights: regional statistics over weighted tokens are a follow-up")
+        if counts is not None:
+            raise NotImplementedError("adain_regions together with ref_lens: the labels index the uncompacted token axis; regions "
+                                      "over compacted references are a follow-up")
+        if isinstance(ref_v, _RefKVTable):
+            raise NotImplementedError("adain_regions with RefKVTable references: the regional statistics and the renormalised V need "
+                                      "dense references; cached per-identity regional statistics are the follow-up")
+    if counts is not None:
+        if ref_valid is not None:
+            raise ValueError("ref_lens with ref_valid: a count of 0 says the reference is absent, ref_valid says it is zero-filled "
+                             "(its tokens keep exp(0)) - pass one of the two")
+        if biased:
+            raise NotImplementedError("ref_lens together with an attention mask, ref_weights or ref_token_keep: the key bias indexes the "
+                                      "packed uniform key axis; counts with a bias are a follow-up (compact the kept tokens instead)")
+        if first is not None:
+            raise NotImplementedError(_rule_text(first, "ref_lens together with {names}: {entries} would walk the tails behind the counts (follow-up)")
+                                      + ("; save_attention_mass honours the counts" if first.paired else ""))
+        if proc.use_adain and cstats is None:
+            raise ValueError("ref_lens with use_adain needs ref_stats: the AdaIN content statistics are those of the full reference, "
+                             "taken before compaction - computing them here would read the packed rows and whatever lies behind them")
+    for row in on:
+        if row.sentinel is not None:
+            v = getattr(proc, row.args[-1], None)
+            if isinstance(v, str) and v != row.sentinel:
+                raise ValueError(f"{row.args[-1]} must be None, \"{row.sentinel}\" or {row.takes}, got {v!r}")
+        if row.reduce == row.switch and getattr(proc, row.switch) not in _REDUCES:
+            raise ValueError(f"{row.switch} must be None, \"none\" or \"head_mean\", got {getattr(proc, row.switch)!r}")
+    if biased and first is not None:
+        raise NotImplementedError(_rule_text(first, "{names} together with an attention mask, ref_weights or ref_token_keep: "
+                                                       "{entries} does not take the key bias yet (follow-up)")
+                                  + ("; save_attention_mass honours it" if first.paired else ""))
+
+
+def _read_out(proc, on, query, key, ref_k, lse, **kw) -> None:
+    """launches the read-outs ``on`` from the LSE of the attention call, in the table's order, and leaves each result on ``proc``"""
+    for row in on:
+        args = [getattr(proc, n, None) for n in row.args]
+        if row.sentinel is not None and isinstance(args[-1], str):
+            args[-1] = None
+        rkw = dict(kw)
+        if row.reduce is not None:
+            rkw["reduce"] = getattr(proc, row.reduce, "head_mean")
+        for name, attribute, default in row.extra:
+            rkw[name] = getattr(proc, attribute, default)
+        setattr(proc, row.result, getattr(_ops, row.op)(query, key, ref_k, lse, *args, **rkw))
+
+
+def _adain_step(attn, value, ref_v, ref_valid, cstats, vstats, adain_weights, adain_regions, adain_n_regions, adain_region_min_tokens):
+    """AdaIN of a shared layer with ``use_adain`` -> ``(affine, ref_v, ref_valid)``: the affine ``(a, b)`` that the attention folds in,
+    or ``None`` beside a renormalised ``ref_v`` where the affine was applied to V here.
+
+    style = this image's own post-projection V; content = each reference V.  With the content statistics handed over
+    (``cstats``, from ``ref_stats``: computed once per identity by the K/V-capture layer, kv_harvest with_stats) only V_self is
+    read here - 1/(N+1) of the bytes, the same (a, b) bit for bit.  Round 4: the style statistics arrive as the partials this
+    layer's own q/k/v GEMM left behind (``vstats``): with them and the content statistics nothing of V is read here at all - one
+    small launch."""
+    affine = None
+    geometry = (value.shape[0], value.shape[1], ref_v.shape[1], ref_v.shape[2])
+    if adain_regions is not None:
+        # per-region AdaIN: one affine per (reference, region) cannot ride the fold (it applies a * sum(p v) + b * sum(p)
+        # once per segment), so the renormalised V is formed here - the reference's own order of operations - and
+        # the attention runs without an affine
+        R = int(adain_n_regions)
+        q_lab, r_lab = _adain_region_labels(adain_regions, *geometry, value.device)
+        v1 = value.unsqueeze(1)
+        style_g = _ops.token_stats(v1, heads=attn.heads)
+        style_r = _ops.token_stats_regions(v1, q_lab.unsqueeze(1), heads=attn.heads, n_regions=R, return_count=True)
+        content_g = _ops.token_stats(ref_v, heads=attn.heads)
+        content_r = _ops.token_stats_regions(ref_v, r_lab, heads=attn.heads, n_regions=R, return_count=True)
+        table = _ops.adain_affine_regions(style_r, content_r, style_g, content_g,
+                                          min_tokens=FOLD_MIN_REF_TOKENS if adain_region_min_tokens is None else adain_region_min_tokens)
+        # a zero-filled reference's V is the style mean now, not zero: its tiles are walked
+        return None, _ops.adain_apply_regions(ref_v, r_lab, table[0], table[1], heads=attn.heads), None
+    if adain_weights is not None:
+        # mask-aware AdaIN: the style statistics over this layer's weighted tokens; the content statistics as the
+        # caller finished them (``ref_stats``), else over the dense references' weighted tokens
+        self_w, ref_w = _adain_weight_pair(adain_weights, *geometry, value.device)
+        if hasattr(cstats, "finished"):
+            content = cstats.finished()
+        elif cstats is not None:
+            content = cstats
+        elif isinstance(ref_v, _RefKVTable):
+            raise ValueError("use_adain with RefKVTable references needs ref_stats: cache the identities with their AdaIN content "
+                             "statistics (get_conditioning_keys_values(..., with_stats=True[, stats_weights=...])) and pass the "
+                             "stats of ReferenceKVCache.assemble_tables")
+        else:
+            content = _ops.token_stats_weighted(ref_v, heads=attn.heads, weights=ref_w)
+        style = _ops.token_stats_weighted(value.unsqueeze(1), heads=attn.heads,
+                                          weights=None if self_w is None else self_w.unsqueeze(1))
+        affine = _ops.adain_affine(style, content)
+    elif hasattr(cstats, "finished"):
+        if vstats is not None:    # both sides as partials: ONE launch merges them into the affine
+            affine = _ops.adain_affine_from_partials(vstats, *geometry, content=cstats.part, valid=cstats.valid)
+        else:
+            affine = _stats_cached(value, cstats.finished(), attn.heads)
+    elif cstats is not None and vstats is not None:
+        affine = _ops.adain_affine_from_partials(vstats, *geometry, content_mean=cstats[0], content_std=cstats[1])
+    elif cstats is not None:
+        affine = _stats_cached(value, cstats, attn.heads)
+    elif isinstance(ref_v, _RefKVTable):
+        # the content statistics would need a pass over every reference V, and ir_adain_stats reads a dense tensor:
+        # a table is never densified behind the caller's back
+        raise ValueError("use_adain with RefKVTable references needs ref_stats: cache the identities with their AdaIN content "
+                         "statistics (get_conditioning_keys_values(..., with_stats=True)) and pass the stats of "
+                         "ReferenceKVCache.assemble_tables")
+    else:
+        affine = _ops.adain_stats(value, ref_v, heads=attn.heads)
+    if ref_v.shape[2] >= FOLD_MIN_REF_TOKENS:
+        return affine, ref_v, ref_valid
+    if isinstance(ref_v, _RefKVTable):
+        raise ValueError(f"RefKVTable references of fewer than {FOLD_MIN_REF_TOKENS} tokens with use_adain: this branch forms the "
+                         "renormalised V as a dense tensor; pass dense ref_values (the model's own axes never come here)")
+    # a handful of reference tokens: a channel whose few values lie ulps apart gets a ratio in the thousands, and the
+    # fold's a * sum(p~ v) + b * sum(p) would amplify the 16-bit rounding of P by a * |mean| (DESIGN section 2).  Here the
+    # renormalised V is formed once (ir_adain_apply, fp32 arithmetic, one rounding - what the reference's adain()
+    # does, attn_processors.py:7-18) and the attention runs without an affine.  Never taken by the model's own axes (>= 256).
+    # A zero-filled reference's V is the style mean now, not zero: its tiles are walked
+    return None, _ops.adain_apply(ref_v, affine[0], affine[1], heads=attn.heads), None
 
 
 # ------------------------------------------------------------------------------------------
@@ -754,19 +911,22 @@ class SharedAttnProcessor(nn.Module):
         ``(B, N, S, S)``), shared layers only (ignored elsewhere, as ``ref_valid`` is): ``ops.key_bias`` turns them into the bias -
         ``log w`` on a reference's keys, 0 / dropped tokens MASKED (no attention at all, unlike a zero-filled reference).  AdaIN
         statistics stay those of every reference token unless ``adain_weights`` (below) says otherwise.  ``save_attention_mass`` reads the effect back; ``save_self_attentions`` /
-        ``attention_rows_index`` with a bias raise (the read-out kernels do not take the bias yet).
+        ``attention_rows_index`` (and every other read-out) with a bias raise (the read-out kernels do not take the bias yet).
+
         ``ref_valid`` (optional, round 5): int32 ``(B,)`` device tensor from the harvest (``kv_harvest`` ``with_valid``) when
         it zero-filled references ``n >= valid[b]`` (pix2pix_turbo.py:269-273): the kernel then closes those all-zero segments
         analytically instead of walking them (ABI v8 ``valid_refs``).  Same output; the tokens keep their exp(0) weight.
+
         ``ref_lens`` (optional), shared layers only (ignored elsewhere, as ``ref_valid`` is): a list with one int32 ``(B, N)`` device
         tensor per shared layer (or ``None``) - the number of keys every reference HAS (``ops.compact_refs``,
         ``ReferenceKVCache.assemble_tables``); the reference tensors' token axis is then only their capacity, and the kernel walks the
         existing keys alone (``ir_shared_attn_ragged_args``).  Raises with ``ref_valid`` (absent is not zero-filled), with a mask /
         ``ref_weights`` / ``ref_token_keep`` (counts with a key bias are a follow-up; ``ref_token_keep`` alone keeps running the bias
-        path), with ``save_self_attentions`` and ``attention_rows_index`` (the read-out kernels would walk the tails);
+        path), with ``save_self_attentions`` and ``attention_rows_index`` (the read-out kernels would read on behind the counts);
         ``save_attention_mass`` works.  With ``use_adain`` it needs ``ref_stats``: by default the content statistics of the FULL
         reference, taken before compaction - the rule of the bias path, so a compacted call and a masked call agree - or, with
         ``adain_weights``, kept-token statistics (``ops.token_stats_weighted(packed_v, heads=H, lens=lens)``).
+
         ``region_labels = (query_labels, ref_labels)`` with ``region_allow`` (optional), shared layers only (ignored elsewhere, as
         ``ref_valid`` is): a per-QUERY restriction by class labels - "eye tokens draw from eye tokens of the references".  The labels
         are integer label pictures (``(B, Hpx, Wpx)`` of this image, ``(B, N, Hpx, Wpx)`` of its references: a face parsing map) or
@@ -778,6 +938,7 @@ class SharedAttnProcessor(nn.Module):
         regions.  Raises, before anything is launched, with an attention mask, ``ref_weights``, ``ref_token_keep`` or ``ref_lens``
         (regions with a key bias or with counts are a follow-up) and with ``save_self_attentions`` or any read-out attribute (the
         read-out kernels do not take regions yet); with ``ref_valid`` a dense call walks the zero-filled references, a table call raises.
+
         ``adain_weights = (self_weights, ref_weights)`` (optional; either may be ``None``), shared layers with ``use_adain`` only
         (accepted and ignored elsewhere, as ``ref_valid`` is): mask-aware AdaIN - the statistics behind the affine are taken over
         weighted tokens (``ops.token_stats_weighted``: weight 0 drops a token, 0/1 weights give the statistics of the kept tokens
@@ -790,6 +951,7 @@ class SharedAttnProcessor(nn.Module):
         otherwise one weighted pass over the dense reference V; a ``RefKVTable`` without ``ref_stats`` raises as without the
         kwarg, and so does ``ref_lens`` without ``ref_stats``.  The affine comes from ``ops.adain_affine`` and enters the
         attention as any other: masks, ``ref_weights``, ``ref_token_keep``, regions and the batch-invariant mode work with it.
+
         ``adain_regions = (query_labels, ref_labels)`` with ``adain_n_regions`` (required: inferring it would need a sync) and the
         optional ``adain_region_min_tokens`` (default 8), shared layers with ``use_adain`` only (accepted and ignored elsewhere):
         per-REGION AdaIN - eye tokens of a reference are renormalised with eye statistics, skin with skin.  The labels are
@@ -806,58 +968,44 @@ class SharedAttnProcessor(nn.Module):
         call.  ``ref_stats`` is not consulted.  Raises, before anything is launched: without ``adain_n_regions`` (ValueError); with
         ``adain_weights`` (regional statistics over weighted tokens are a follow-up), with ``ref_lens`` (the labels index the
         uncompacted token axis; a follow-up) and with ``RefKVTable`` references (cached per-identity regional statistics are the
-        follow-up) - NotImplementedError."""
-        st = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
-        shared = self.self_attn_idx is not None and ref_keys is not None and ref_values is not None
-        regions = shared and region_labels is not None
-        if regions:     # refused before anything is launched
-            if region_allow is None:
-                raise ValueError("region_labels needs region_allow: the (C, C) bool matrix or the (C,) bitmasks of ops.region_masks")
-            if st.mask is not None or ref_weights is not None or ref_token_keep is not None:
-                raise NotImplementedError("region_labels together with an attention mask, ref_weights or ref_token_keep: the kernel carries either "
-                                          "the key bias or the region test; regions with a key bias are a follow-up")
-            if ref_lens is not None and ref_lens[self.self_attn_idx] is not None:
-                raise NotImplementedError("region_labels together with ref_lens: key_region indexes the packed uniform key axis; regions with "
-                                          "per-reference counts are a follow-up")
-            readouts = [n for n in ("attention_rows_index", "attention_match_index", "attention_topk_index", "attention_transfer_payload",
-                                    "attention_received_weights", "attention_key_match_reduce") if getattr(self, n, None) is not None]
-            if self.save_self_attentions or readouts:
-                raise NotImplementedError(f"region_labels together with {', '.join((['save_self_attentions'] if self.save_self_attentions else []) + readouts)}: "
-                                          "the read-out kernels do not take regions yet (their exp(s - lse) would count the pairs the forward "
-                                          "left out; follow-up); save_attention_mass honours the regions")
-        # the GEMM's statistics tail (style partials of this layer's own V) only pays when the content statistics arrive
-        # precomputed (``ref_stats``): without them ir_adain_stats reads every V anyway and would throw the partials away
-        have_cstats = bool(shared and ref_stats is not None and ref_stats[self.self_attn_idx] is not None)
-        bi = bool(getattr(self, "batch_invariant", False))
-        weighted = bool(shared and self.use_adain and adain_weights is not None)    # mask-aware AdaIN: a branch of its own below
-        regional = bool(shared and self.use_adain and adain_regions is not None)    # per-region AdaIN: applied to V, a branch of its own below
-        if regional:    # refused before anything is launched
-            if adain_n_regions is None:
-                raise ValueError("adain_regions needs adain_n_regions (1 ... 32): inferring it from the labels would need a device sync")
-            if adain_weights is not None:
-                raise NotImplementedError("adain_regions together with adain_weights: regional statistics over weighted tokens are a follow-up")
-            if ref_lens is not None and ref_lens[self.self_attn_idx] is not None:
-                raise NotImplementedError("adain_regions together with ref_lens: the labels index the uncompacted token axis; regions "
-                                          "over compacted references are a follow-up")
-            if isinstance(ref_values[self.self_attn_idx], _RefKVTable):
-                raise NotImplementedError("adain_regions with RefKVTable references: the regional statistics and the renormalised V need "
-                                          "dense references; cached per-identity regional statistics are the follow-up")
-        query, key, value, presc, vstats = _project_qkv(attn, st, want_stats=bool(self.use_adain and have_cstats and not weighted and not regional),
-                                                        bi=bi)
+        follow-up) - NotImplementedError.
 
-        ref_k = ref_v = None
-        include_self = True
-        affine = None
-        counts = None     # ref_lens of this shared layer
+        Every refusal above that the kwargs and the processor's attributes decide comes before anything is launched (``_refuse``):
+        the q/k/v projection of a refused call does not run.  The read-outs and what each needs are the rows of ``_READOUTS``."""
+        st = _prologue(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
+        idx = self.self_attn_idx
+        shared = idx is not None and ref_keys is not None and ref_values is not None
+        bi = bool(getattr(self, "batch_invariant", False))
+        use_adain = bool(shared and self.use_adain)
+        ref_k = ref_v = cstats = counts = None     # this layer's entries of ref_keys / ref_values / ref_stats / ref_lens
         if shared:
-            ref_k = ref_keys[self.self_attn_idx]
-            ref_v = ref_values[self.self_attn_idx]
-            cstats = ref_stats[self.self_attn_idx] if ref_stats is not None else None
-            if ref_events is not None and ref_events[self.self_attn_idx] is not None:
+            ref_k, ref_v = ref_keys[idx], ref_values[idx]
+            cstats = ref_stats[idx] if ref_stats is not None else None
+            counts = ref_lens[idx] if ref_lens is not None else None
+        else:       # a layer that shares nothing ignores what belongs to the references
+            ref_valid = ref_weights = ref_token_keep = region_labels = None
+        if not use_adain:
+            adain_weights = adain_regions = None
+        on = _readouts_on(self, shared)
+        if on or counts is not None or region_labels is not None or adain_regions is not None:      # (no rule is about anything else)
+            _refuse(self, on, biased=st.mask is not None or ref_weights is not None or ref_token_keep is not None, counts=counts,
+                    cstats=cstats, ref_v=ref_v, ref_valid=ref_valid, region_labels=region_labels, region_allow=region_allow,
+                    adain_weights=adain_weights, adain_regions=adain_regions, adain_n_regions=adain_n_regions)
+
+        # the GEMM's statistics tail (style partials of this layer's own V) only pays when the content statistics arrive
+        # precomputed (``ref_stats``): without them ir_adain_stats reads every V anyway and would throw the partials away.
+        # Mask-aware and per-region AdaIN take statistics passes of their own
+        query, key, value, presc, vstats = _project_qkv(
+            attn, st, want_stats=use_adain and cstats is not None and adain_weights is None and adain_regions is None, bi=bi)
+
+        include_self = True
+        if shared:
+            include_self = bool(self.train_input)
+            if ref_events is not None and ref_events[idx] is not None:
                 # the reference UNet runs on another HIP stream (kv_harvest with_events): this layer needs
                 # capture layer `self_attn_idx` and nothing later
                 cur = torch.cuda.current_stream(ref_k.device)
-                cur.wait_event(ref_events[self.self_attn_idx])
+                cur.wait_event(ref_events[idx])
                 ref_k.record_stream(cur)
                 ref_v.record_stream(cur)
                 if hasattr(cstats, "finished"):
@@ -867,126 +1015,16 @@ class SharedAttnProcessor(nn.Module):
                     cstats[1].record_stream(cur)
             elif hasattr(cstats, "sync_to_current"):
                 cstats.sync_to_current()      # no event handed over: order this stream behind the partials' producer (no-op on one stream)
-            include_self = bool(self.train_input)
-            if ref_lens is not None:
-                counts = ref_lens[self.self_attn_idx]
-            if counts is not None:
-                if ref_valid is not None:
-                    raise ValueError("ref_lens with ref_valid: a count of 0 says the reference is absent, ref_valid says it is zero-filled "
-                                     "(its tokens keep exp(0)) - pass one of the two")
-                if st.mask is not None or ref_weights is not None or ref_token_keep is not None:
-                    raise NotImplementedError("ref_lens together with an attention mask, ref_weights or ref_token_keep: the key bias indexes the "
-                                              "packed uniform key axis; counts with a bias are a follow-up (compact the kept tokens instead)")
-                if self.save_self_attentions or getattr(self, "attention_rows_index", None) is not None:
-                    raise NotImplementedError("ref_lens together with save_self_attentions / attention_rows_index: ir_attn_probs and ir_attn_rows "
-                                              "would walk the tails behind the counts (follow-up); save_attention_mass honours the counts")
-                if getattr(self, "attention_match_index", None) is not None:
-                    raise NotImplementedError("ref_lens together with attention_match_index: ir_attn_match would walk the tails behind the "
-                                              "counts (follow-up)")
-                if getattr(self, "attention_transfer_payload", None) is not None:
-                    raise NotImplementedError("ref_lens together with attention_transfer_payload: ir_attn_transfer would walk the tails "
-                                              "behind the counts (follow-up)")
-                if getattr(self, "attention_received_weights", None) is not None:
-                    raise NotImplementedError("ref_lens together with attention_received_weights: ir_attn_received would walk the tails "
-                                              "behind the counts (follow-up)")
-                if getattr(self, "attention_topk_index", None) is not None:
-                    raise NotImplementedError("ref_lens together with attention_topk_index: ir_attn_topk would walk the tails behind the "
-                                              "counts (follow-up)")
-                if getattr(self, "attention_key_match_reduce", None) is not None:
-                    raise NotImplementedError("ref_lens together with attention_key_match_reduce: ir_attn_key_match would walk the tails "
-                                              "behind the counts (follow-up)")
-                if self.use_adain and cstats is None:
-                    raise ValueError("ref_lens with use_adain needs ref_stats: the AdaIN content statistics are those of the full reference, "
-                                     "taken before compaction - computing them here would read the packed rows and whatever lies behind them")
-            if self.use_adain:
-                # style = this image's own post-projection V; content = each reference V.  With the content statistics
-                # handed over (``ref_stats``: computed once per identity by the K/V-capture layer, kv_harvest with_stats)
-                # only V_self is read here - 1/(N+1) of the bytes, the same (a, b) bit for bit
-                # Round 4: the style statistics arrive as the partials this layer's own q/k/v GEMM left behind (``vstats``):
-                # with them and the content statistics nothing of V is read here at all - one small launch
-                if regional:
-                    # per-region AdaIN: one affine per (reference, region) cannot ride the fold (it applies a * sum(p v) + b * sum(p)
-                    # once per segment), so the renormalised V is formed here - the reference's own order of operations - and
-                    # the attention below runs without an affine
-                    R = int(adain_n_regions)
-                    q_lab, r_lab = _adain_region_labels(adain_regions, value.shape[0], value.shape[1], ref_v.shape[1], ref_v.shape[2], value.device)
-                    v1 = value.unsqueeze(1)
-                    style_g = _ops.token_stats(v1, heads=attn.heads)
-                    style_r = _ops.token_stats_regions(v1, q_lab.unsqueeze(1), heads=attn.heads, n_regions=R, return_count=True)
-                    content_g = _ops.token_stats(ref_v, heads=attn.heads)
-                    content_r = _ops.token_stats_regions(ref_v, r_lab, heads=attn.heads, n_regions=R, return_count=True)
-                    table = _ops.adain_affine_regions(style_r, content_r, style_g, content_g,
-                                                      min_tokens=FOLD_MIN_REF_TOKENS if adain_region_min_tokens is None else adain_region_min_tokens)
-                    ref_v = _ops.adain_apply_regions(ref_v, r_lab, table[0], table[1], heads=attn.heads)
-                    ref_valid = None       # a zero-filled reference's V is the style mean now, not zero: its tiles are walked
-                elif weighted:
-                    # mask-aware AdaIN: the style statistics over this layer's weighted tokens; the content statistics as the
-                    # caller finished them (``ref_stats``), else over the dense references' weighted tokens
-                    self_w, ref_w = _adain_weight_pair(adain_weights, value.shape[0], value.shape[1], ref_v.shape[1], ref_v.shape[2], value.device)
-                    if hasattr(cstats, "finished"):
-                        content = cstats.finished()
-                    elif cstats is not None:
-                        content = cstats
-                    elif isinstance(ref_v, _RefKVTable):
-                        raise ValueError("use_adain with RefKVTable references needs ref_stats: cache the identities with their AdaIN content "
-                                         "statistics (get_conditioning_keys_values(..., with_stats=True[, stats_weights=...])) and pass the "
-                                         "stats of ReferenceKVCache.assemble_tables")
-                    else:
-                        content = _ops.token_stats_weighted(ref_v, heads=attn.heads, weights=ref_w)
-                    style = _ops.token_stats_weighted(value.unsqueeze(1), heads=attn.heads,
-                                                      weights=None if self_w is None else self_w.unsqueeze(1))
-                    affine = _ops.adain_affine(style, content)
-                elif hasattr(cstats, "finished"):
-                    if vstats is not None:    # both sides as partials: ONE launch merges them into the affine
-                        affine = _ops.adain_affine_from_partials(vstats, value.shape[0], value.shape[1], ref_v.shape[1], ref_v.shape[2],
-                                                                 content=cstats.part, valid=cstats.valid)
-                    else:
-                        affine = _stats_cached(value, cstats.finished(), attn.heads)
-                elif cstats is not None and vstats is not None:
-                    affine = _ops.adain_affine_from_partials(vstats, value.shape[0], value.shape[1], ref_v.shape[1], ref_v.shape[2],
-                                                             content_mean=cstats[0], content_std=cstats[1])
-                elif cstats is not None:
-                    affine = _stats_cached(value, cstats, attn.heads)
-                elif isinstance(ref_v, _RefKVTable):
-                    # the content statistics would need a pass over every reference V, and ir_adain_stats reads a dense tensor:
-                    # a table is never densified behind the caller's back
-                    raise ValueError("use_adain with RefKVTable references needs ref_stats: cache the identities with their AdaIN content "
-                                     "statistics (get_conditioning_keys_values(..., with_stats=True)) and pass the stats of "
-                                     "ReferenceKVCache.assemble_tables")
-                else:
-                    affine = _ops.adain_stats(value, ref_v, heads=attn.heads)
         _same_16bit(query, key, value, ref_k, ref_v)
-        if affine is not None and ref_v.shape[2] < FOLD_MIN_REF_TOKENS and isinstance(ref_v, _RefKVTable):
-            raise ValueError(f"RefKVTable references of fewer than {FOLD_MIN_REF_TOKENS} tokens with use_adain: this branch forms the "
-                             "renormalised V as a dense tensor; pass dense ref_values (the model's own axes never come here)")
-        if affine is not None and ref_v.shape[2] < FOLD_MIN_REF_TOKENS:
-            # a handful of reference tokens: a channel whose few values lie ulps apart gets a ratio in the thousands, and the
-            # fold's a * sum(p~ v) + b * sum(p) would amplify the 16-bit rounding of P by a * |mean|.  Here the
-            # renormalised V is formed once (ir_adain_apply, fp32 arithmetic, one rounding - what the reference's adain()
-            # does, attn_processors.py:7-18) and the attention runs without an affine.  Never taken by the model's own axes (>= 256).
-            ref_v = _ops.adain_apply(ref_v, affine[0], affine[1], heads=attn.heads)
-            affine = None
-            ref_valid = None       # a zero-filled reference's V is the style mean now, not zero: its tiles are walked
 
-        want_probs = bool(self.save_self_attentions)
-        want_mass = bool(getattr(self, "save_attention_mass", False))
-        rows_index = getattr(self, "attention_rows_index", None) if shared else None
-        match_index = getattr(self, "attention_match_index", None) if shared else None
-        transfer_payload = getattr(self, "attention_transfer_payload", None) if shared else None
-        received_weights = getattr(self, "attention_received_weights", None) if shared else None
-        if isinstance(received_weights, str) and received_weights != "ones":          # before anything is launched
-            raise ValueError(f"attention_received_weights must be None, \"ones\" or an fp32 tensor, got {received_weights!r}")
-        topk_index = getattr(self, "attention_topk_index", None) if shared else None
-        if isinstance(topk_index, str) and topk_index != "all":                       # before anything is launched
-            raise ValueError(f"attention_topk_index must be None, \"all\" or an integer tensor, got {topk_index!r}")
-        key_match_reduce = getattr(self, "attention_key_match_reduce", None) if shared else None
-        if key_match_reduce is not None and key_match_reduce not in ("none", "head_mean"):    # before anything is launched
-            raise ValueError(f"attention_key_match_reduce must be None, \"none\" or \"head_mean\", got {key_match_reduce!r}")
-        want_lse = want_probs or rows_index is not None or match_index is not None or transfer_payload is not None or \
-            received_weights is not None or topk_index is not None or key_match_reduce is not None
+        affine = None
+        if use_adain:
+            affine, ref_v, ref_valid = _adain_step(attn, value, ref_v, ref_valid, cstats, vstats, adain_weights, adain_regions,
+                                                   adain_n_regions, adain_region_min_tokens)
+
         kw = {"q_prescaled": True} if presc else {}
         kw.update(_bi_kw(bi))
-        if shared and ref_valid is not None:
+        if ref_valid is not None:
             kw["valid_refs"] = ref_valid
         if counts is not None:
             kw["ref_lens"] = counts
@@ -997,32 +1035,16 @@ class SharedAttnProcessor(nn.Module):
             row = _ref_bias_row(ref_weights, ref_token_keep, query.shape[0], len_self, ref_k.shape[1], ref_k.shape[2], include_self, query.device)
             if row is not None:
                 bias = row if bias is None else (bias + (row if bias.dim() == 2 else row.unsqueeze(1)))
-        if regions:
+        if bias is not None:
+            kw["key_bias"] = bias
+        if region_labels is not None:
             kw["q_allow"], kw["key_region"] = _region_pair(region_labels, region_allow, query.shape[0],
                                                            query.shape[1], len_self, ref_k.shape[1], ref_k.shape[2], include_self, query.device)
-        if bias is not None:
-            if want_probs or rows_index is not None:
-                raise NotImplementedError("save_self_attentions / attention_rows_index together with an attention mask, ref_weights or "
-                                          "ref_token_keep: ir_attn_probs and ir_attn_rows do not take the key bias yet (follow-up); "
-                                          "save_attention_mass honours it")
-            if match_index is not None:
-                raise NotImplementedError("attention_match_index together with an attention mask, ref_weights or ref_token_keep: "
-                                          "ir_attn_match does not take the key bias yet (follow-up)")
-            if transfer_payload is not None:
-                raise NotImplementedError("attention_transfer_payload together with an attention mask, ref_weights or ref_token_keep: "
-                                          "ir_attn_transfer does not take the key bias yet (follow-up)")
-            if received_weights is not None:
-                raise NotImplementedError("attention_received_weights together with an attention mask, ref_weights or ref_token_keep: "
-                                          "ir_attn_received does not take the key bias yet (follow-up)")
-            if topk_index is not None:
-                raise NotImplementedError("attention_topk_index together with an attention mask, ref_weights or ref_token_keep: "
-                                          "ir_attn_topk does not take the key bias yet (follow-up)")
-            if key_match_reduce is not None:
-                raise NotImplementedError("attention_key_match_reduce together with an attention mask, ref_weights or ref_token_keep: "
-                                          "ir_attn_key_match does not take the key bias yet (follow-up)")
-            kw["key_bias"] = bias
+
         # the masses are a by-product of the attention launch itself (ABI v9 ``seg_mass``: the kernels hold the row sums at every
-        # segment boundary): no second pass over Q and K
+        # segment boundary): no second pass over Q and K.  Every read-out works from the one LSE of this launch
+        want_lse = bool(on)
+        want_mass = bool(getattr(self, "save_attention_mass", False))
         res = _ops.shared_attention(query, key, value, ref_k, ref_v, heads=attn.heads, scale=attn.scale,
                                     include_self=include_self, adain=affine, return_lse=want_lse, return_mass=want_mass, **kw)
         if want_mass:
@@ -1032,52 +1054,10 @@ class SharedAttnProcessor(nn.Module):
             tokens, lse = res
         else:
             tokens = res
-        if rows_index is not None:
-            # the rows of the chosen tokens from the same LSE (pre-scaled query: as for the dump below)
-            self.attention_rows = _ops.attn_rows(query, key, ref_k, lse, rows_index, heads=attn.heads,
-                                                 scale=0.6931471805599453 if presc else attn.scale, include_self=include_self,
-                                                 reduce=getattr(self, "attention_rows_reduce", "head_mean"), **_bi_kw(bi))
-        if match_index is not None:
-            # the best key of every segment for the chosen tokens ("all": every token) from the same LSE
-            if isinstance(match_index, str) and match_index != "all":
-                raise ValueError(f"attention_match_index must be None, \"all\" or an integer tensor, got {match_index!r}")
-            self.attention_match = _ops.attn_match(query, key, ref_k, lse, None if isinstance(match_index, str) else match_index,
-                                                   heads=attn.heads, scale=0.6931471805599453 if presc else attn.scale,
-                                                   include_self=include_self,
-                                                   reduce=getattr(self, "attention_match_reduce", "head_mean"), **_bi_kw(bi))
-        if transfer_payload is not None:
-            # the attention-weighted sums of the payload per segment for the chosen tokens (None / "all": every token), same LSE
-            transfer_index = getattr(self, "attention_transfer_index", None)
-            if isinstance(transfer_index, str) and transfer_index != "all":
-                raise ValueError(f"attention_transfer_index must be None, \"all\" or an integer tensor, got {transfer_index!r}")
-            self.attention_transfer = _ops.attn_transfer(query, key, ref_k, lse, transfer_payload,
-                                                         None if isinstance(transfer_index, str) else transfer_index,
-                                                         heads=attn.heads, scale=0.6931471805599453 if presc else attn.scale,
-                                                         include_self=include_self,
-                                                         reduce=getattr(self, "attention_transfer_reduce", "head_mean"), **_bi_kw(bi))
-        if received_weights is not None:
-            # what every key receives from all query tokens ("ones": unweighted), same LSE
-            self.attention_received = _ops.attn_received(query, key, ref_k, lse, None if isinstance(received_weights, str) else received_weights,
-                                                         heads=attn.heads, scale=0.6931471805599453 if presc else attn.scale,
-                                                         include_self=include_self,
-                                                         reduce=getattr(self, "attention_received_reduce", "head_mean"), **_bi_kw(bi))
-        if topk_index is not None:
-            # the k best keys of every segment for the chosen tokens ("all": every token) from the same LSE
-            self.attention_topk = _ops.attn_topk(query, key, ref_k, lse, None if isinstance(topk_index, str) else topk_index,
-                                                 k=getattr(self, "attention_topk_k", 4), heads=attn.heads,
-                                                 scale=0.6931471805599453 if presc else attn.scale, include_self=include_self,
-                                                 reduce=getattr(self, "attention_topk_reduce", "head_mean"), **_bi_kw(bi))
-        if key_match_reduce is not None:
-            # the best query token of every key over all query tokens, same LSE
-            self.attention_key_match = _ops.attn_key_match(query, key, ref_k, lse, heads=attn.heads,
-                                                           scale=0.6931471805599453 if presc else attn.scale,
-                                                           include_self=include_self, reduce=key_match_reduce, **_bi_kw(bi))
-        if want_probs:
-            # (B, H, L, Lkv), columns [self?] ++ ref0 ++ ... ++ refN-1, in the compute dtype.  A pre-scaled query
-            # already carries scale * log2(e): its scores are exponents, ln 2 turns them into the logits of the LSE
-            self.attention_probs = _ops.attn_probs(query, key, ref_k, lse, heads=attn.heads,
-                                                   scale=0.6931471805599453 if presc else attn.scale,
-                                                   include_self=include_self, **_bi_kw(bi))
+
+        if on:
+            _read_out(self, on, query, key, ref_k, lse, heads=attn.heads, scale=LN2 if presc else attn.scale, include_self=include_self,
+                      **_bi_kw(bi))
         return _epilogue(attn, st, tokens, bi)
 
 

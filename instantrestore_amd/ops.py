@@ -247,6 +247,11 @@ def _is_table(t) -> bool:
     return isinstance(t, RefKVTable)
 
 
+def _nseg(include_self: bool, ref_k) -> int:
+    """the K/V segments of a call: ``[self (iff include_self)] ++ ref 0 ++ ... ++ ref N-1``"""
+    return (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
+
+
 def _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, lse, split=True,
                q_prescaled=False, valid_refs=None, batch_invariant=False, key_bias=None, ref_lens=None, q_allow=None, key_region=None):
     if ref_lens is not None:   # validated before anything else is touched
@@ -649,8 +654,7 @@ def shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: int, s
                       batch_invariant, key_bias, ref_lens, q_allow, key_region)
     mass = None
     if return_mass:
-        nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
-        mass = torch.empty((q.shape[0], heads, q.shape[1], nseg), dtype=torch.float32, device=q.device)
+        mass = torch.empty((q.shape[0], heads, q.shape[1], _nseg(include_self, ref_k)), dtype=torch.float32, device=q.device)
         args.seg_mass = mass.data_ptr()
     if batch_invariant:
         _bi_workspace(args, q.device)
@@ -681,8 +685,7 @@ def time_shared_attention(q, k_self, v_self, ref_k=None, ref_v=None, *, heads: i
     args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, None, split, q_prescaled, valid_refs,
                       batch_invariant, key_bias, ref_lens, q_allow, key_region)
     if return_mass:
-        nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
-        mass = torch.empty((q.shape[0], heads, q.shape[1], nseg), dtype=torch.float32, device=q.device)
+        mass = torch.empty((q.shape[0], heads, q.shape[1], _nseg(include_self, ref_k)), dtype=torch.float32, device=q.device)
         args.seg_mass = mass.data_ptr()
     if batch_invariant:
         _bi_workspace(args, q.device)
@@ -722,8 +725,7 @@ def shared_attention_kernel_name(q, k_self, v_self, ref_k=None, ref_v=None, *, h
     args = _fill_args(q, k_self, v_self, ref_k, ref_v, heads, scale, include_self, adain, out, None, True, q_prescaled, valid_refs,
                       batch_invariant, key_bias, ref_lens, q_allow, key_region)
     if return_mass:   # never written: the name is all this call computes
-        nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
-        mass = torch.empty((q.shape[0], heads, q.shape[1], nseg), dtype=torch.float32, device=q.device)
+        mass = torch.empty((q.shape[0], heads, q.shape[1], _nseg(include_self, ref_k)), dtype=torch.float32, device=q.device)
         args.seg_mass = mass.data_ptr()
     return _lib.lib().ir_shared_attn_kernel_name(C.byref(args)).decode()
 
@@ -791,7 +793,9 @@ def shared_attention_plan(batch: int, len_q: int, heads: int, *, len_self: int =
 PROBS_KERNELS = {"auto": 0, "generic": 1, "lines64": 2, "lines32": 3, "lines32k128": 4, "lines64k128": 5, "lines32k256": 6}   # IR_PROBS_*
 
 
-def _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled=False, batch_invariant=False):
+def _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled=False, batch_invariant=False, one_kernel=False):
+    """the argument block of a read-out from the LSE.  ``one_kernel``: the entry point has one kernel, so the A/B hook of the
+    forward (``tuning``) does not apply"""
     q, k_self, _, ref_k, _ = _prep(q, k_self, k_self, ref_k, ref_k, heads, include_self, None)
     B, Lq, _ = q.shape
     lkv = (k_self.shape[1] if include_self else 0) + (ref_k.shape[1] * ref_k.shape[2] if ref_k is not None else 0)
@@ -799,7 +803,19 @@ def _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled=F
         raise ValueError("lse must be contiguous fp32 (B, H, Lq)")
     args = _fill_args(q, k_self, k_self, ref_k, ref_k, heads, scale, include_self, None, None, lse, True, q_prescaled, None,
                       batch_invariant)
+    if one_kernel:
+        args.tuning = 0
     return args, q, B, Lq, lkv, (q, k_self, ref_k, lse)
+
+
+def _check_reduce(reduce: str, codes: dict) -> None:
+    if reduce not in codes:
+        raise ValueError(f"reduce must be one of {sorted(codes)}, got {reduce!r}")
+
+
+def _all_rows(batch: int, len_q: int, device: torch.device) -> torch.Tensor:
+    """``rows=None`` of a read-out - every query token, in order - as the index tensor :func:`_row_index` makes of a list"""
+    return torch.arange(len_q, dtype=torch.int32, device=device).unsqueeze(0).expand(batch, -1).contiguous()
 
 
 @_on_tensor_device
@@ -824,8 +840,7 @@ def attn_segment_mass(q, k_self, ref_k, lse, *, heads: int, scale: float, includ
     (``ir_attn_segment_mass``): what gradio_demo.py:119-127 reduces ``attention_probs`` to.  ``batch_invariant`` as in
     :func:`attn_probs`."""
     args, q, B, Lq, _, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant)
-    nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
-    mass = torch.empty((B, heads, Lq, nseg), dtype=torch.float32, device=q.device)
+    mass = torch.empty((B, heads, Lq, _nseg(include_self, ref_k)), dtype=torch.float32, device=q.device)
     _lib.check(_lib.lib().ir_attn_segment_mass(C.byref(args), mass.data_ptr(), _stream()), "ir_attn_segment_mass")
     return mass
 
@@ -862,10 +877,8 @@ def attn_rows(q, k_self, ref_k, lse, rows, *, heads: int, scale: float, include_
     of :func:`attn_probs`; ``"head_mean"`` - fp32 ``(B, R, Lkv)``, ``attn.mean(dim=1)[b][rows]``; ``"map"`` - fp32 ``(B, Lkv)``,
     the sum of those rows (the landmark heat map before its reshape, :func:`instantrestore_amd.attn_maps.landmark_picture`).
     ``q_prescaled`` as in :func:`attn_probs`.  Batch invariant by construction; ``batch_invariant`` is accepted and changes nothing."""
-    if reduce not in ROWS_REDUCE:
-        raise ValueError(f"reduce must be one of {sorted(ROWS_REDUCE)}, got {reduce!r}")
-    args, q, B, Lq, lkv, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant)
-    args.tuning = 0   # one kernel: the A/B hook of the forward does not apply
+    _check_reduce(reduce, ROWS_REDUCE)
+    args, q, B, Lq, lkv, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant, one_kernel=True)
     idx = _row_index(rows, B, Lq, q.device)
     R = idx.shape[1]
     if reduce == "none":
@@ -896,16 +909,11 @@ def attn_match(q, k_self, ref_k, lse, rows=None, *, heads: int, scale: float, in
     for bit - and ``index`` the lowest key, counted inside its segment, that attains it
     (:func:`instantrestore_amd.attn_maps.match_coordinates` turns it into ``(y, x)``).  ``q_prescaled`` as in :func:`attn_probs`.
     Batch invariant by construction; ``batch_invariant`` is accepted and changes nothing."""
-    if reduce not in MATCH_REDUCE:
-        raise ValueError(f"reduce must be one of {sorted(MATCH_REDUCE)}, got {reduce!r}")
-    args, q, B, Lq, _, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant)
-    args.tuning = 0   # one kernel: the A/B hook of the forward does not apply
-    if rows is None:
-        idx = torch.arange(Lq, dtype=torch.int32, device=q.device).unsqueeze(0).expand(B, -1).contiguous()
-    else:
-        idx = _row_index(rows, B, Lq, q.device)
+    _check_reduce(reduce, MATCH_REDUCE)
+    args, q, B, Lq, _, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant, one_kernel=True)
+    idx = _all_rows(B, Lq, q.device) if rows is None else _row_index(rows, B, Lq, q.device)
     R = idx.shape[1]
-    nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
+    nseg = _nseg(include_self, ref_k)
     shape = (B, heads, R, nseg) if reduce == "none" else (B, R, nseg)
     index = torch.empty(shape, dtype=torch.int32, device=q.device)
     prob = torch.empty(shape, dtype=torch.float32, device=q.device)
@@ -933,16 +941,11 @@ def attn_topk(q, k_self, ref_k, lse, rows=None, *, k: int, heads: int, scale: fl
     nothing."""
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _lib.IR_TOPK_MAX:
         raise ValueError(f"k must be an integer in 1 ... {_lib.IR_TOPK_MAX}, got {k!r}")
-    if reduce not in MATCH_REDUCE:
-        raise ValueError(f"reduce must be one of {sorted(MATCH_REDUCE)}, got {reduce!r}")
-    args, q, B, Lq, _, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant)
-    args.tuning = 0   # one kernel: the A/B hook of the forward does not apply
-    if rows is None:
-        idx = torch.arange(Lq, dtype=torch.int32, device=q.device).unsqueeze(0).expand(B, -1).contiguous()
-    else:
-        idx = _row_index(rows, B, Lq, q.device)
+    _check_reduce(reduce, MATCH_REDUCE)
+    args, q, B, Lq, _, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant, one_kernel=True)
+    idx = _all_rows(B, Lq, q.device) if rows is None else _row_index(rows, B, Lq, q.device)
     R = idx.shape[1]
-    nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
+    nseg = _nseg(include_self, ref_k)
     shape = (B, heads, R, nseg, k) if reduce == "none" else (B, R, nseg, k)
     index = torch.empty(shape, dtype=torch.int32, device=q.device)
     prob = torch.empty(shape, dtype=torch.float32, device=q.device)
@@ -996,17 +999,12 @@ def attn_transfer(q, k_self, ref_k, lse, payload, rows=None, *, heads: int, scal
     summed over the same keys in the same order: a channel of ones IS the mass, a one-hot channel IS that key's fp32 probability
     (what :func:`attn_rows` rounds to q's dtype).  ``q_prescaled`` as in :func:`attn_probs`.  Batch invariant by construction;
     ``batch_invariant`` is accepted and changes nothing."""
-    if reduce not in TRANSFER_REDUCE:
-        raise ValueError(f"reduce must be one of {sorted(TRANSFER_REDUCE)}, got {reduce!r}")
-    args, q, B, Lq, lkv, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant)
-    args.tuning = 0   # one kernel: the A/B hook of the forward does not apply
+    _check_reduce(reduce, TRANSFER_REDUCE)
+    args, q, B, Lq, lkv, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant, one_kernel=True)
     payload, sb, sj, nch = _transfer_payload(payload, B, lkv, q.device)
-    if rows is None:
-        idx = torch.arange(Lq, dtype=torch.int32, device=q.device).unsqueeze(0).expand(B, -1).contiguous()
-    else:
-        idx = _row_index(rows, B, Lq, q.device)
+    idx = _all_rows(B, Lq, q.device) if rows is None else _row_index(rows, B, Lq, q.device)
     R = idx.shape[1]
-    nseg = (1 if include_self else 0) + (ref_k.shape[1] if ref_k is not None else 0)
+    nseg = _nseg(include_self, ref_k)
     shape = (B, heads, R, nseg) if reduce == "none" else (B, R, nseg)
     sums = torch.empty(shape + (nch,), dtype=torch.float32, device=q.device)
     mass = torch.empty(shape, dtype=torch.float32, device=q.device)
@@ -1071,10 +1069,8 @@ def attn_received(q, k_self, ref_k, lse, weights=None, *, heads: int, scale: flo
     one-hot channel at row ``i`` IS that row's fp32 probabilities (what :func:`attn_rows` rounds to q's dtype), ``None`` IS a
     channel of ones.  ``q_prescaled`` as in :func:`attn_probs`.  Batch invariant by construction; ``batch_invariant`` is accepted
     and changes nothing."""
-    if reduce not in RECEIVED_REDUCE:
-        raise ValueError(f"reduce must be one of {sorted(RECEIVED_REDUCE)}, got {reduce!r}")
-    args, q, B, Lq, lkv, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant)
-    args.tuning = 0   # one kernel: the A/B hook of the forward does not apply
+    _check_reduce(reduce, RECEIVED_REDUCE)
+    args, q, B, Lq, lkv, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant, one_kernel=True)
     if weights is None:
         wptr, sb, si, nch = None, 0, 1, 1
     else:
@@ -1103,10 +1099,8 @@ def attn_key_match(q, k_self, ref_k, lse, *, heads: int, scale: float, include_s
     gives ``index 0``, ``prob 0``.  :func:`instantrestore_amd.attn_maps.keep_from_key_match` turns ``prob`` into a ``keep`` mask
     for :func:`compact_refs`.  ``q_prescaled`` as in :func:`attn_probs`.  Batch invariant by construction; ``batch_invariant`` is
     accepted and changes nothing."""
-    if reduce not in MATCH_REDUCE:
-        raise ValueError(f"reduce must be one of {sorted(MATCH_REDUCE)}, got {reduce!r}")
-    args, q, B, Lq, lkv, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant)
-    args.tuning = 0   # one kernel: the A/B hook of the forward does not apply
+    _check_reduce(reduce, MATCH_REDUCE)
+    args, q, B, Lq, lkv, _keep = _probs_args(q, k_self, ref_k, lse, heads, scale, include_self, q_prescaled, batch_invariant, one_kernel=True)
     shape = (B, heads, lkv) if reduce == "none" else (B, lkv)
     index = torch.empty(shape, dtype=torch.int32, device=q.device)
     prob = torch.empty(shape, dtype=torch.float32, device=q.device)

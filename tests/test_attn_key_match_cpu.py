@@ -120,8 +120,10 @@ def test_ops_attn_key_match_has_no_cpu_path_and_checks_its_arguments():
     with pytest.raises(RuntimeError, match="CPU"):
         ops.attn_key_match(q, q, None, lse, heads=1, scale=0.125, reduce="head_mean")
     src = inspect.getsource(ops.attn_key_match)
-    assert "_probs_args(" in src and "MATCH_REDUCE[reduce]" in src and "args.tuning = 0" in src
-    assert src.index("reduce not in MATCH_REDUCE") < src.index("_probs_args(")                  # the form is checked before anything else
+    assert "_probs_args(" in src and "MATCH_REDUCE[reduce]" in src and "one_kernel=True" in src
+    # (the one-kernel decision is _probs_args' argument: there the forward's A/B hook is switched off)
+    assert re.search(r"if one_kernel:\n\s+args\.tuning = 0\n", inspect.getsource(ops._probs_args))
+    assert src.index("_check_reduce(reduce, MATCH_REDUCE)") < src.index("_probs_args(")                  # the form is checked before anything else
 
 
 def test_ops_signature():

@@ -117,7 +117,9 @@ def test_ops_attn_topk_checks_k_first_and_has_no_cpu_path():
     with pytest.raises(RuntimeError, match="CPU"):
         ops.attn_topk(q, q, None, lse, torch.tensor([0]), k=8, heads=1, scale=0.125, reduce="head_mean")
     src = inspect.getsource(ops.attn_topk)
-    assert "_row_index(rows, B, Lq, q.device)" in src and "_probs_args(" in src and "args.tuning = 0" in src
+    assert "_row_index(rows, B, Lq, q.device)" in src and "_probs_args(" in src and "one_kernel=True" in src
+    # (the one-kernel decision is _probs_args' argument: there the forward's A/B hook is switched off)
+    assert re.search(r"if one_kernel:\n\s+args\.tuning = 0\n", inspect.getsource(ops._probs_args))
 
 
 def test_ops_signature_has_no_bias_and_no_counts():
@@ -358,11 +360,15 @@ def test_processor_raises_with_a_bias_or_counts(shim):
 
 
 def test_the_real_ops_is_passed_the_batch_invariant_keyword():
-    """the processor hands _bi_kw through, as it does for the match read-out"""
+    """the processor hands the mode's keyword through, as it does for the match read-out, and only when the mode is on"""
+    import processor_trace
     import instantrestore_amd.attn_processors as ap
-    src = inspect.getsource(ap)
-    call = src[src.index("_ops.attn_topk("):]
-    assert "**_bi_kw(bi))" in call[:call.index("if want_probs")]
+    for mode in (True, False):
+        case = dict(own=True, attrs=dict(batch_invariant=mode, attention_topk_index="all", attention_match_index="all",
+                                         save_self_attentions=True))
+        calls = {c[0]: c[2] for c in processor_trace.run_case(ap, case)["calls"]}
+        for name in ("shared_attention", "attn_match", "attn_topk", "attn_probs"):
+            assert calls[name].get("batch_invariant") is (True if mode else None), (mode, name)
 
 
 # ---- the build's register report -------------------------------------------------------------------------------------------
