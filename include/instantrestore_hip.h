@@ -359,6 +359,9 @@ size_t ir_shared_attn_workspace_bytes_for(const ir_shared_attn_args* args);
  * Uses the same args as ir_shared_attn_fwd (out / adain_* are ignored) plus the `lse` that
  * call produced:  probs[b,h,i,j] = exp(scale*<q_i,k_j> - lse[b,h,i]), stored in `dtype`,
  * contiguous, column order as above.
+ * Accuracy: this fp32 probability - shared by every read-out below - is held by the tests to a relative error of 8 * 2^-23 *
+ * max(1, |lse|, scale * sum_d |q_d k_d|) against float64 with the same lse, ahead of the one rounding to `dtype`
+ * (tests/prob_bounds.py has the bound and the measured table).
  *
  * HBM-write bound (H*L*Lkv*2 bytes per identity).  When len_self and len_ref are multiples of 8 keys (every row of
  * probs then starts 16-byte aligned) the line kernel runs: whole 128-byte lines per store instruction (round 5); other

@@ -8,7 +8,8 @@ What is held to what:
      first argmax.  Per head, every case: ``prob`` rounded to the 16-bit type is ``attn_probs(...).max(-2)`` and the dump's element
      at ``index`` is that maximum;
   2. the float64 oracle, with ``TOL`` of tests/test_gpu_attn_rows.py used as tests/test_gpu_attn_match.py uses it:
-     ``|prob - p64[index, j]| <= TOL`` and ``p64[index, j] >= max_i p64[i, j] - 2 TOL``;
+     ``|prob - p64[index, j]| <= TOL`` and ``p64[index, j] >= max_i p64[i, j] - 2 TOL``; and under the relative fp32 bound of
+     tests/prob_bounds.py (reference B): ``prob`` at the returned row element by element, the row under its index rule;
   3. planted cases with exact indices: ties between rows (the LSE is written, not computed), the winner in the last row before the
      padding, a column of zeros, one query row;
   4. ``torch.equal`` with the plain call: pointer tables, pre-scaled Q, ``batch_invariant``, an entry of a batch alone, a replayed
@@ -23,7 +24,8 @@ import torch
 
 import oracle_ops_key_match as K
 from test_gpu_attn_match import _first_argmax
-from test_gpu_attn_rows import CASES, ODD_CASES, TOL, _case_inputs, _gpu_lse, _ids, _oracle_probs, _rand
+import prob_bounds as PB
+from test_gpu_attn_rows import CASES, ODD_CASES, TOL, _case_inputs, _gpu_lse, _ids, _oracle_probs, _oracle_side, _rand
 from test_gpu_ref_table import _pool_grid, _stack
 
 pytestmark = pytest.mark.gpu
@@ -64,7 +66,8 @@ def _setup(case, dtype):
     B, H, Lq, Ls, N, Lr, inc = case
     q, k, v, rk, rv = _case_inputs(case, dtype)
     qd, kd, rkd, lse = _gpu_lse(ops, q, k, v, rk, rv, H, inc)
-    return dict(q=qd, k=kd, rk=rkd, lse=lse, p64=_oracle_probs(q, k, v, rk, rv, H, inc), edges=K.segment_edges(Ls, N, Lr, inc),
+    E, delta = _oracle_side(q, k, rk, H, inc)
+    return dict(q=qd, k=kd, rk=rkd, lse=lse, p64=_oracle_probs(q, k, v, rk, rv, H, inc), E=E, delta=delta, edges=K.segment_edges(Ls, N, Lr, inc),
                 kw=dict(heads=H, scale=0.125, include_self=inc))
 
 
@@ -173,6 +176,12 @@ def test_against_the_float64_oracle(ops, case, dtype):
         print(f"attn_key_match {_ids([case])[0]} {dtype} {form}: max |prob - p64[index, j]| {worst_v:.3e} (bound {tol:.0e}), "
               f"max (max_i p64 - p64[index, j]) {worst_gap:.3e} (bound {2 * tol:.0e})")
         assert worst_v <= tol and worst_gap <= 2 * tol, (form, worst_v, worst_gap)
+        t = lambda a: np.swapaxes(a, -1, -2)                                  # the query axis as the one segment of every key
+        cal, der, ref = (*PB.terms(t(s["p64"]), t(s["E"]), None, t(s["delta"])), t(s["p64"]))
+        if form == "head_mean":
+            cal, der, ref = PB.head_mean_terms(cal, der, ref)
+        PB.check_ranked(index[..., None, None], prob[..., None, None], ref, cal, der, [0, s["p64"].shape[2]], np.zeros(ref.shape[:-1], dtype=bool),
+                        f"attn_key_match {_ids([case])[0]} {dtype} {form}", kind=f"key_match_{form}B")
 
 
 # ---- 3: planted cases, exact indices ---------------------------------------------------------------------------------------------

@@ -6,7 +6,8 @@ What is held to what:
      ``attn_rows(reduce="head_mean")`` bit for bit and ``index`` its first argmax (same expression, same order, monotone rounding);
   2. the float64 oracle, with ``TOL`` of tests/test_gpu_probs.py (1e-3 fp16 / 8e-3 bf16, the project's stated bound for
      probabilities): ``|prob - p64[index]| <= TOL`` and ``p64[index] >= max_j p64[j] - 2 TOL`` (every key's probability is within
-     TOL, so the chosen key is a maximiser up to twice that);
+     TOL, so the chosen key is a maximiser up to twice that); and under the relative fp32 bound of tests/prob_bounds.py
+     (reference B): ``prob`` at the returned index element by element, the index under its index rule;
   3. planted winners, ties, invalid rows: exact indices;
   4. pointer tables, graph replay, pre-scaled Q, batch invariance, the processor: ``torch.equal`` with the plain call.
 The inputs, the LSE and the float64 probabilities of a (case, dtype) are computed once and shared by the tests that need them."""
@@ -17,7 +18,8 @@ import pytest
 import torch
 
 import oracle_ops_match as M
-from test_gpu_attn_rows import CASES, ODD_CASES, TOL, _case_inputs, _gpu_lse, _ids, _indices, _oracle_probs, _rand
+import prob_bounds as PB
+from test_gpu_attn_rows import CASES, ODD_CASES, TOL, _case_inputs, _gpu_lse, _ids, _indices, _oracle_probs, _oracle_side, _rand
 from test_gpu_ref_table import _pool_grid, _stack
 
 pytestmark = pytest.mark.gpu
@@ -42,7 +44,8 @@ def _setup(case, dtype):
     B, H, Lq, Ls, N, Lr, inc = case
     q, k, v, rk, rv = _case_inputs(case, dtype)
     qd, kd, rkd, lse = _gpu_lse(ops, q, k, v, rk, rv, H, inc)
-    return dict(q=qd, k=kd, rk=rkd, lse=lse, p64=_oracle_probs(q, k, v, rk, rv, H, inc), edges=M.segment_edges(Ls, N, Lr, inc),
+    E, delta = _oracle_side(q, k, rk, H, inc)
+    return dict(q=qd, k=kd, rk=rkd, lse=lse, p64=_oracle_probs(q, k, v, rk, rv, H, inc), E=E, delta=delta, edges=M.segment_edges(Ls, N, Lr, inc),
                 kw=dict(heads=H, scale=0.125, include_self=inc))
 
 
@@ -105,10 +108,16 @@ def test_against_the_float64_oracle(ops, case, dtype):
     tol = TOL[dtype]
     for idx in _row_lists(B, Lq):
         p_rows = M.gather_rows(s["p64"], _idx_np(idx, B, Lq))
+        E_rows, d_rows = M.gather_rows(s["E"], _idx_np(idx, B, Lq)), M.gather_rows(s["delta"], _idx_np(idx, B, Lq))
         dev_idx = None if idx is None else idx.cuda()
         for form in FORMS:
             index, prob = ops.attn_match(s["q"], s["k"], s["rk"], s["lse"], dev_idx, reduce=form, **s["kw"])
             index, prob = index.cpu().numpy().astype(np.int64), prob.cpu().numpy().astype(np.float64)
+            cal, der, ref = (*PB.terms(p_rows, E_rows, None, d_rows), p_rows)
+            if form == "head_mean":
+                cal, der, ref = PB.head_mean_terms(cal, der, p_rows)
+            PB.check_ranked(index[..., None], prob[..., None], ref, cal, der, s["edges"], np.zeros(ref.shape[:-1], dtype=bool),
+                            f"attn_match {_ids([case])[0]} {dtype} R={'all' if idx is None else idx.shape[1]} {form}", kind=f"match_{form}B")
             x = p_rows.mean(axis=1) if form == "head_mean" else p_rows
             best, _, _ = M.match_np(p_rows, s["edges"], form == "head_mean")
             worst_v = worst_gap = 0.0

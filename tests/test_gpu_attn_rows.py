@@ -7,7 +7,8 @@ What is held to what (u = unit roundoff of the 16-bit output format: 2^-8 bf16, 
      one rounding that separates the two (the 1e-7 covers fp16 subnormals and the fp32 sum over <= 20 heads);
   3. form "map" against form "head_mean": ``|map - sum_r hm| <= R * 2^-23 * sum_r hm``, the fp32 summation bound;
   4. all forms against the float64 oracle: ``TOL[dtype]`` of tests/test_gpu_probs.py (1e-3 fp16 / 8e-3 bf16) for forms 0 and 1,
-     ``R * TOL`` for form 2 - the project's stated bound for probabilities (the LSE of the fused forward limits it).
+     ``R * TOL`` for form 2 - the project's stated bound for probabilities (the LSE of the fused forward limits it);
+  5. all forms against the float64 oracle element by element under the relative fp32 bound of tests/prob_bounds.py (reference B).
 Each test prints the maxima it saw before it asserts (``pytest -s``; tools/gpu_attn_rows_ab.py records them)."""
 import ctypes as C
 
@@ -15,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+import prob_bounds as PB
 from oracle import shared_attn_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -108,8 +110,13 @@ def _gather(p, idx):
     return torch.stack([p[b][:, idx[b].to(p.device).long()] for b in range(p.shape[0])])
 
 
-def _check_forms(got, P0, p_ref_rows, dtype, R, what):
-    """items 1-4 of the module docstring on one set of rows; returns the maxima against the oracle"""
+def _oracle_side(q, k, rk, H, inc, scale=0.125, presc=False):
+    """(E, delta) of tests/prob_bounds.py's reference B for the 16-bit inputs of a call (``q`` pre-scaled with scale = ln 2 and ``presc``)"""
+    return PB.oracle_side(_np64(q), PB.pack_keys(k.cpu(), None if rk is None else rk.cpu(), inc), H, scale, presc)
+
+
+def _check_forms(got, P0, p_ref_rows, dtype, R, what, E_rows, delta_rows, klass="plain"):
+    """items 1-5 of the module docstring on one set of rows; returns the maxima against the oracle"""
     assert got["none"].dtype == dtype and got["head_mean"].dtype == torch.float32 and got["map"].dtype == torch.float32
     assert torch.equal(got["none"], P0), f"{what}: form none is not the dump's rows"
     mean0 = P0.double().mean(dim=1)
@@ -130,6 +137,11 @@ def _check_forms(got, P0, p_ref_rows, dtype, R, what):
     assert bool((d2 <= bound2).all()), f"{what}: map vs head_mean, worst {float(d2.max())}"
     assert np.isfinite(got["none"].float().cpu().numpy()).all()
     assert e0 <= TOL[dtype] and e1 <= TOL[dtype] and e2 <= R * TOL[dtype], (what, e0, e1, e2)
+    PB.check_probs(got["none"], p_ref_rows, E_rows, dtype, f"{what} R={R} none", delta=delta_rows, klass=klass)
+    cal, der, ref = PB.head_mean_terms(*PB.terms(p_ref_rows, E_rows, None, delta_rows, klass), p_ref_rows)
+    PB.check_terms(got["head_mean"], ref, cal, der, f"{what} R={R} head_mean", klass, "head_meanB")
+    cal2, der2, ref2 = PB.map_terms(cal, der, ref)
+    PB.check_terms(got["map"], ref2, cal2, der2, f"{what} R={R} map", klass, "mapB")
     return e0, e1, e2
 
 
@@ -139,6 +151,7 @@ def test_three_forms_against_the_dump_and_the_oracle(ops, case, dtype):
     B, H, Lq, Ls, N, Lr, inc = case
     q, k, v, rk, rv = _case_inputs(case, dtype)
     p_ref = _oracle_probs(q, k, v, rk, rv, H, inc)
+    E, delta = _oracle_side(q, k, rk, H, inc)
     qd, kd, rkd, lse = _gpu_lse(ops, q, k, v, rk, rv, H, inc)
     dump = ops.attn_probs(qd, kd, rkd, lse, heads=H, scale=0.125, include_self=inc)
     for R in _row_counts(Lq):
@@ -146,7 +159,7 @@ def test_three_forms_against_the_dump_and_the_oracle(ops, case, dtype):
         got = {f: ops.attn_rows(qd, kd, rkd, lse, idx.cuda(), heads=H, scale=0.125, include_self=inc, reduce=f) for f in FORMS}
         lkv = p_ref.shape[-1]
         assert got["none"].shape == (B, H, R, lkv) and got["head_mean"].shape == (B, R, lkv) and got["map"].shape == (B, lkv)
-        _check_forms(got, _gather(dump, idx), _gather(p_ref, idx), dtype, R, f"{_ids([case])[0]} {dtype}")
+        _check_forms(got, _gather(dump, idx), _gather(p_ref, idx), dtype, R, f"{_ids([case])[0]} {dtype}", _gather(E, idx), _gather(delta, idx))
         # the same list from the CPU, and a shared (R,) list: both are conveniences of the wrapper over the same call
         again = ops.attn_rows(qd, kd, rkd, lse, idx.long(), heads=H, scale=0.125, include_self=inc, reduce="none")
         assert torch.equal(again, got["none"])
@@ -238,7 +251,8 @@ def test_prescaled_q(ops, dtype, shape):
     R = min(68, L)
     idx = _indices(B, L, R, seed=31)
     got = {f: ops.attn_rows(qs, k, rk, lse, idx.cuda(), heads=H, scale=0.125, include_self=True, reduce=f, q_prescaled=True) for f in FORMS}
-    _check_forms(got, _gather(dump, idx), _gather(p_ref, idx), dtype, R, f"prescaled {shape} {dtype}")
+    E, delta = _oracle_side(qs, k, rk, H, True, scale=0.6931471805599453, presc=True)
+    _check_forms(got, _gather(dump, idx), _gather(p_ref, idx), dtype, R, f"prescaled {shape} {dtype}", _gather(E, idx), _gather(delta, idx), klass="presc")
 
 
 def test_capturable_and_follows_the_index_tensor(ops):

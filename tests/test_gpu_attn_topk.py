@@ -10,7 +10,8 @@ What is held to what:
      ranks and among equal fp32 ``prob`` the indices ascend.  Ranks beyond the segment's keys are ``-1`` / ``0``;
   3. the float64 oracle, with ``TOL`` of tests/test_gpu_probs.py (1e-3 fp16 / 8e-3 bf16, the project's stated bound for
      probabilities): for every rank t ``|prob_t - p64[index_t]| <= TOL`` and ``p64[index_t] >= (t-th largest p64) - 2 TOL`` (every
-     key is within TOL, and an order statistic moves by at most the sup-norm error - hence twice);
+     key is within TOL, and an order statistic moves by at most the sup-norm error - hence twice); and under the relative fp32
+     bound of tests/prob_bounds.py (reference B): every ``prob_t`` at its returned index, every index under the index rule;
   4. planted graded winners and ties: exact indices; row groups against calls of one row; invalid rows;
   5. pointer tables, pre-scaled Q, graph replay, batch invariance, the processor, repeated calls: ``torch.equal`` with the plain call.
 The inputs, the LSE and the float64 probabilities of a (case, dtype) are computed once and shared by the tests that need them.
@@ -25,7 +26,8 @@ import torch
 
 import oracle_ops_topk as M
 from test_gpu_attn_match import _plant, _planted_inputs
-from test_gpu_attn_rows import CASES, ODD_CASES, TOL, _case_inputs, _gpu_lse, _ids, _indices, _oracle_probs, _rand
+import prob_bounds as PB
+from test_gpu_attn_rows import CASES, ODD_CASES, TOL, _case_inputs, _gpu_lse, _ids, _indices, _oracle_probs, _oracle_side, _rand
 from test_gpu_ref_table import _pool_grid, _stack
 
 pytestmark = pytest.mark.gpu
@@ -53,7 +55,8 @@ def _setup(case, dtype):
     B, H, Lq, Ls, N, Lr, inc = case
     q, k, v, rk, rv = _case_inputs(case, dtype)
     qd, kd, rkd, lse = _gpu_lse(ops, q, k, v, rk, rv, H, inc)
-    return dict(q=qd, k=kd, rk=rkd, lse=lse, p64=_oracle_probs(q, k, v, rk, rv, H, inc), edges=M.segment_edges(Ls, N, Lr, inc),
+    E, delta = _oracle_side(q, k, rk, H, inc)
+    return dict(q=qd, k=kd, rk=rkd, lse=lse, p64=_oracle_probs(q, k, v, rk, rv, H, inc), E=E, delta=delta, edges=M.segment_edges(Ls, N, Lr, inc),
                 kw=dict(heads=H, scale=0.125, include_self=inc))
 
 
@@ -157,13 +160,20 @@ def test_against_the_float64_oracle(ops, case, dtype):
     tol = TOL[dtype]
     for idx in _row_lists(B, Lq):
         p_rows = M.gather_rows(s["p64"], _idx_np(idx, B, Lq))
+        E_rows, d_rows = M.gather_rows(s["E"], _idx_np(idx, B, Lq)), M.gather_rows(s["delta"], _idx_np(idx, B, Lq))
         for form in FORMS:
             x = p_rows.mean(axis=1) if form == "head_mean" else p_rows
             best, _ = M.topk_np(p_rows, s["edges"], max(KS), form == "head_mean")                # (..., S, 8): the t-th largest p64
+            cal, der, ref = (*PB.terms(p_rows, E_rows, None, d_rows), p_rows)
+            if form == "head_mean":
+                cal, der, ref = PB.head_mean_terms(cal, der, p_rows)
+            tops = {}
             worst_v = worst_gap = 0.0
             for k in KS:
                 index, prob = _topk(ops, s, idx, form, k)
                 index, prob = index.cpu().numpy().astype(np.int64), prob.cpu().numpy().astype(np.float64)
+                PB.check_ranked(index, prob, ref, cal, der, s["edges"], np.zeros(ref.shape[:-1], dtype=bool),
+                                f"attn_topk {_what(case, dtype, idx, form)} k={k}", kind=f"topk_{form}B", tops=tops)
                 for si, (a, b) in enumerate(zip(s["edges"][:-1], s["edges"][1:])):
                     n = min(k, b - a)
                     at = np.take_along_axis(x, a + index[..., si, :n], axis=-1)                  # p64[index_t]

@@ -5,11 +5,13 @@ Tolerance (floating point): probabilities are in [0, 1], so the bound of tests/t
 ``max|P - P_ref| <= TOL[dtype]`` (1e-3 fp16, 8e-3 bf16: one ulp of the 16-bit output at 1.0); rows sum to 1 within 4x that.
 The kernels of one call are also compared with each other BIT FOR BIT: they evaluate the same expression
 (exp2(fma(s, scale*log2e, -lse*log2e)) on the fp32 MFMA result), only the store shape differs.
+Every kernel's dump is also held element by element to the relative fp32 bound of tests/prob_bounds.py (reference B).
 """
 import numpy as np
 import pytest
 import torch
 
+import prob_bounds as PB
 from lse_bounds import check_mass, oracle_lse_and_mass, pack_keys, row_scale
 from oracle import shared_attn_oracle as O
 
@@ -88,6 +90,7 @@ def test_every_probs_kernel_against_the_oracle(ops, case, dtype):
     q, k, v, rk, rv = _case_inputs(case, dtype)
     p_ref = _oracle_probs(q, k, v, rk, rv, H, inc)
     qd, kd, rkd, lse = _gpu_lse(ops, q, k, v, rk, rv, H, inc)
+    E, delta = PB.oracle_side(_np64(q), pack_keys(k, rk, inc), H, 0.125)
     got = {}
     for kern in ("auto", "generic") + LINE_KERNELS:
         probs = ops.attn_probs(qd, kd, rkd, lse, heads=H, scale=0.125, include_self=inc, kernel=kern)
@@ -96,6 +99,7 @@ def test_every_probs_kernel_against_the_oracle(ops, case, dtype):
         assert np.isfinite(p).all(), kern
         assert np.abs(p - p_ref).max() <= TOL[dtype], (kern, np.abs(p - p_ref).max())
         np.testing.assert_allclose(p.sum(-1), 1.0, atol=4 * TOL[dtype])
+        PB.check_probs(probs, p_ref, E, dtype, f"attn_probs {kern} {_ids([case])[0]} {dtype}", delta=delta)
         got[kern] = probs
     for kern in ("auto",) + LINE_KERNELS:
         assert torch.equal(got[kern], got["generic"]), f"{kern} differs from the 2-byte-store kernel"
